@@ -37,6 +37,40 @@ PEAK_HBM_GBS = 8000.0                          # MI355X_MICROARCH.md: HBM3E
 FFT_LOADER_BYTES_PER_SF = 786432 + 2097152      # = 2 883 584: a1 + a2, fp32 (8 Doppler x 2 x 64 x 64 x 8) out
 FFT_MEANS_BYTES_PER_SF = 786432 + 262144        # = 1 048 576: ... with HuPRNet's elevation mean folded in (what the step runs)
 STRONG_GLOBAL_BATCH = 256                      # BASELINE.json configs[3]
+DUMP_MAX_BYTES = 64 << 20                      # --dump-outputs: all files together
+DUMP_SAMPLE_PER_TENSOR = 16384                 # --dump-outputs: fixed sample of each weight / buffer (the model is 142 MB in fp32)
+
+
+def _host(t):
+    """A result tensor as a host array: float64 and integer results as float64, every other float type as float32."""
+    t = t.detach()
+    exact = t.dtype == torch.float64 or not (t.is_floating_point() or t.is_complex())
+    return t.to(torch.float64 if exact else torch.float32).cpu().numpy()
+
+
+def state_sample(module):
+    """Every parameter and floating-point buffer of ``module``, in registration order, each flattened and reduced to
+    DUMP_SAMPLE_PER_TENSOR elements at sorted indices drawn from a generator seeded by the tensor's position."""
+    tensors = [p for _, p in module.named_parameters()] + [b for _, b in module.named_buffers() if b.is_floating_point()]
+    parts = []
+    for i, t in enumerate(tensors):
+        flat = t.detach().reshape(-1)
+        if flat.numel() > DUMP_SAMPLE_PER_TENSOR:
+            idx = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(i))[:DUMP_SAMPLE_PER_TENSOR]
+            flat = flat[idx.sort().values.to(flat.device)]
+        parts.append(flat.float())
+    return torch.cat(parts)
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs DIR: write each host array of ``arrays`` as DIR/<name>.npy (float32 / float64, DUMP_MAX_BYTES in all)."""
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit("bench.py: --dump-outputs would write %d bytes (limit %d)" % (total, DUMP_MAX_BYTES))
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def cpu_baseline():
@@ -115,6 +149,7 @@ def bench_inference(args, cfg, dev, rank, world, peak, steps=None, batch=None, e
     from hupr_amd.models import HuPRNet
     B = batch if batch is not None else (1 if args.batch == 32 else args.batch)
     steps = steps if steps is not None else args.steps
+    torch.manual_seed(0)      # the same weights in every run (--dump-outputs compares runs output for output)
     net = HuPRNet(cfg).to(dev).eval()
     h, v = (torch.from_numpy(t).to(dev) for t in synth.model_inputs(B, 5 + rank))
     with torch.no_grad():
@@ -139,9 +174,12 @@ def bench_inference(args, cfg, dev, rank, world, peak, steps=None, batch=None, e
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(steps):
-            run()
+            last = run()
         torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if emit and rank == 0 and args.dump_outputs:
+        heatmap, gcn_heatmap = g_out if mode == "hipGraph replay" else last
+        dump_outputs(args.dump_outputs, {"heatmap": _host(heatmap), "gcn_heatmap": _host(gcn_heatmap)})
     value = world * B * steps / dt
     # bounds of a single-sample forward: the matrix pipe (137.09 GF at the dense peak), the weights it must read
     # at least once (35.5 M parameters as bf16 packed layouts + the fp32 PRGCN matrices: HBM), and the launch floor — a dependent
@@ -309,7 +347,13 @@ def main():
     ap.add_argument("--dtype", choices=["f32", "bf16"], default="bf16",
                     help="matrix-pipe arithmetic of the GEMM-shaped ops (fp32 accumulate either way); bf16 also stores the "
                          "encoder/decoder activations as bf16 in HBM, f32 is the bit-faithful parity path")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy: c3 = loss, "
+                         "loss2, both arg-max decodes (index and maximum) and a fixed sample of the updated weights and BatchNorm "
+                         "buffers (state_sample); c2 = the two heat-maps (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     launched = "RANK" in os.environ and "WORLD_SIZE" in os.environ
     if args.gpus > 1 and not launched:
@@ -387,7 +431,7 @@ def main():
     n_launch0 = F_.rt.lib().hupr_launch_count()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss, _ = one_step()
+        loss, loss2 = one_step()
     t_enq = time.perf_counter() - t0          # host time to enqueue all steps (GPU still running)
     launches_native = (F_.rt.lib().hupr_launch_count() - n_launch0) / float(args.steps)
     barrier()
@@ -398,6 +442,13 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     dt = float(t.item())
     loss_value = float(loss.item())
+    if rank == 0 and args.dump_outputs:
+        # before anything else runs a step: the graph's output buffers, the decodes and the weights hold the last timed step
+        (pred_idx, pred_max), (gt_idx, gt_max) = eng.last_decode      # functional.argmax_rows: (B*K,) index and maximum
+        dump_outputs(args.dump_outputs, {"loss": _host(loss), "loss2": _host(loss2),
+                                         "pred2d_index": _host(pred_idx), "pred2d_max": _host(pred_max),
+                                         "gt2d_index": _host(gt_idx), "gt2d_max": _host(gt_max),
+                                         "state_sample": _host(state_sample(eng.model))})
     enq_ranks = [t_enq / args.steps * 1e3]
     if dist.is_initialized():
         enq_ranks = [None] * world

@@ -4,7 +4,7 @@
 File = int16 stream in groups of four [I(2k), I(2k+1), Q(2k), Q(2k+1)] (2 LVDS lanes, complex).  Complex sample n of
 the stream sits at I = raw[4*(n//2) + n%2], Q = raw[4*(n//2) + 2 + n%2].  Per chirp the stream holds
 [rx0 x 256][rx1 x 256][rx2 x 256][rx3 x 256]; result shape (4 rx, total chirps, 256 samples) complex128.
-Pinned against the imported reference in tests/test_oracle_golden.py (skipped when /root/reference is absent)
+Pinned against the imported reference's output (tests/golden/reference_pins.npz, tests/test_oracle_golden.py)
 and by tests/golden/dca1000_small.npz.
 """
 import numpy as np

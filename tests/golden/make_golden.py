@@ -16,6 +16,8 @@ Fixtures are data (inputs are regenerable from seeds; expected outputs are store
                                        (datasets/dataset.py:17-165, datasets/base.py:26-92; `python make_golden.py dataset`)
   oks_eval.json                        COCOeval('keypoints') stats on a synthetic set (misc/coco.py, misc/cocoeval.py)
   contract.json                        state_dict keys/shapes, YAML dump, Runner helper outputs (tools/base.py)
+  reference_pins.npz                   generateHeatmap on seed 11, getadcDataFromDCA1000 on the dca1000_small.npz capture,
+                                       HuPRNet's GCN adjacency (models/layers.py:97-112; `python make_golden.py pins`)
 """
 import hashlib
 import json
@@ -492,6 +494,28 @@ def make_oks():
     print("oks stats", stats[:5])
 
 
+def make_reference_pins():
+    """What the CPU tests once compared against the live reference tree, stored so that they run without it."""
+    import contextlib
+    import io
+    import tempfile
+    ro = ref_import.radar_object()
+    fft11 = ro.generateHeatmap(synth.adc_cube_complex(synth.adc_cube_int16(11))[0])
+    g = np.load(os.path.join(HERE, "dca1000_small.npz"))
+    raw = synth.randint((int(g["n_int16"]),), -2048, 2048, str(g["seed_key"])).astype(np.int16)
+    assert sha(raw) == str(g["sha_in"])
+    with tempfile.TemporaryDirectory() as d:
+        raw.tofile(os.path.join(d, "adc_data.bin"))
+        with contextlib.redirect_stdout(io.StringIO()):
+            dca = ro.getadcDataFromDCA1000(d)
+    net = ref_import.model_module().HuPRNet(ref_import.load_cfg())
+    np.savez_compressed(os.path.join(HERE, "reference_pins.npz"),
+                        fft_seed=11, fft_shape=np.array(fft11.shape), fft_dtype=str(fft11.dtype), fft_sha256=sha(fft11),
+                        dca_shape=np.array(dca.shape), dca_dtype=str(dca.dtype), dca_sha256=sha(dca),
+                        adjacency=net.radarDecoder.gcn.A.detach().numpy().copy())
+    print("pins: fft", fft11.shape, fft11.dtype, "dca", dca.shape, dca.dtype)
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "plot":
         make_plot()
@@ -509,6 +533,9 @@ if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "dataset":
         make_dataset()
         sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "pins":
+        make_reference_pins()
+        sys.exit(0)
     ro = make_fft()
     make_loader(ro)
     net, cfg = make_model()
@@ -516,3 +543,4 @@ if __name__ == "__main__":
     make_oks()
     make_dataset()
     make_trained()
+    make_reference_pins()

@@ -9,7 +9,6 @@ import pytest
 import torch
 import yaml
 
-from oracle import ref_import
 
 G = os.path.join(os.path.dirname(__file__), "golden")
 CONTRACT = json.load(open(os.path.join(G, "contract.json")))
@@ -129,12 +128,13 @@ def test_checkpoint_roundtrip_keys(tmp_path):
     r.args.eval = True
 
 
-@pytest.mark.skipif(not ref_import.available(), reason="reference tree not mounted")
 def test_adjacency_equals_live_reference():
+    """The product's and the oracle's GCN adjacency equal the reference HuPRNet's, captured by make_golden.py."""
     from hupr_amd.models import HuPRNet
     from oracle.model import adjacency
+    ref = torch.from_numpy(np.load(os.path.join(G, "reference_pins.npz"))["adjacency"])
     net = HuPRNet(_cfg())
-    assert torch.equal(net.radarDecoder.gcn.A, adjacency())
+    assert torch.equal(net.radarDecoder.gcn.A, ref) and torch.equal(adjacency(), ref)
 
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
