@@ -48,8 +48,25 @@ __device__ __forceinline__ void halo_store_partial(const HaloArgs& p, const f32x
     }
 }
 
-// 256-voxel persistent variant; returns false when the geometry is not supported
-bool launch_conv_halo256(HaloArgs a, int Bn, bool abf, hipStream_t s);
+// Route codes of a hupr_conv3x3_halo_bf16(act)(_ws|_stats) call (hupr_debug_halo_route): which kernel instantiation it launches.
+// 1-8: the 256-voxel kernel (conv_halo256m_bf16.hip) — template <TD, TH, TW, KD, NCOT, NWN, KC> in the comment;
+// kRoute128 + 16 * slices + 8 * (BN == 64) + 4 * (KC == 64) + 2 * (kd == 3) + abf: the 128-voxel kernel hupr_k_conv_halo_bf16
+// <BN, KC, abf, kd == 3> over `slices` K slices (1: the one-launch form; > 1: the K-sliced form and its reduction).
+enum HaloRoute {
+    kRouteCi32 = 1,             // <4, 8, 8, 3, 0, 2, 32>: 32 input channels, 64-byte rows
+    kRouteCo32 = 2,             // <8, 8, 8, 3, 0, 1>: 32 output channels
+    kRoute1x16x16 = 3,          // <1, 16, 16, 1>: 1 x 3 x 3 taps
+    kRouteStats4x8x8One = 4,    // <4, 8, 8, 3, 1>: fused statistics, one output tile per workgroup
+    kRouteStats4x8x8Two = 5,    // <4, 8, 8, 3, 2>: fused statistics, two
+    kRouteStats2x8x16 = 6,      // <2, 8, 16, 3, 1>: fused statistics, depth 2
+    kRoute4x8x8 = 7,            // <4, 8, 8, 3>
+    kRoute2x8x16 = 8,           // <2, 8, 16, 3>
+    kRoute128 = 256,
+};
+
+// 256-voxel persistent variant: conv_halo256_route picks the instantiation (0: none applies) and fills the tile fields of `a`
+int conv_halo256_route(HaloArgs& a, int Bn, bool abf);
+void launch_conv_halo256(const HaloArgs& a, int route, hipStream_t s);
 bool conv_halo256_supported(const HaloArgs& a, int Bn, bool abf);
 bool conv_halo256_stats_ok(const HaloArgs& a, int Bn);                         // fused BatchNorm statistics available for this launch?
 void set_halo_tiles(int mask);                                                // test aid: which tiles of the 256-voxel kernel are in use (conv_halo256m_bf16.hip)

@@ -545,23 +545,18 @@ __global__ __launch_bounds__(512) void hupr_k_conv_halo256m_bf16(HaloArgs p) {
 #undef HUPR_VMCNT_LGKM0
 }
 
-static void launch_conv_halo256m(const HaloArgs& a, hipStream_t s) {
+void launch_conv_halo256(const HaloArgs& a, int route, hipStream_t s) {      // one persistent workgroup per CU
     const dim3 grid(kHalo256Grid), wg(512);
-    if (a.Ci == 32) HUPR_LAUNCH((hupr_k_conv_halo256m_bf16<4, 8, 8, 3, 0, 2, 32>), grid, wg, 0, s, a);
-    else if (a.TD == 8) HUPR_LAUNCH((hupr_k_conv_halo256m_bf16<8, 8, 8, 3, 0, 1>), grid, wg, 0, s, a);
-    else if (a.kd == 1) HUPR_LAUNCH((hupr_k_conv_halo256m_bf16<1, 16, 16, 1>), grid, wg, 0, s, a);
-    else if (a.stats) {                       // fused BatchNorm statistics: 1 or 2 distinct output tiles per workgroup (conv_halo256_stats_ok)
-        const long tiles = (long)a.Bn * a.nd * a.nh * a.nw * a.n_co_tiles;
-        const long per_wg = (tiles + kHalo256Grid - 1) / kHalo256Grid;
-        const bool one = per_wg == 1 || a.n_co_tiles == 1;
-        if (a.TD == 4) {
-            if (one) HUPR_LAUNCH((hupr_k_conv_halo256m_bf16<4, 8, 8, 3, 1>), grid, wg, 0, s, a);
-            else HUPR_LAUNCH((hupr_k_conv_halo256m_bf16<4, 8, 8, 3, 2>), grid, wg, 0, s, a);
-        } else {
-            HUPR_LAUNCH((hupr_k_conv_halo256m_bf16<2, 8, 16, 3, 1>), grid, wg, 0, s, a);      // per_wg == 1 (conv_halo256_stats_ok)
-        }
-    } else if (a.TD == 4) HUPR_LAUNCH((hupr_k_conv_halo256m_bf16<4, 8, 8, 3>), grid, wg, 0, s, a);
-    else HUPR_LAUNCH((hupr_k_conv_halo256m_bf16<2, 8, 16, 3>), grid, wg, 0, s, a);
+    switch (route) {
+    case kRouteCi32: HUPR_LAUNCH((hupr_k_conv_halo256m_bf16<4, 8, 8, 3, 0, 2, 32>), grid, wg, 0, s, a); break;
+    case kRouteCo32: HUPR_LAUNCH((hupr_k_conv_halo256m_bf16<8, 8, 8, 3, 0, 1>), grid, wg, 0, s, a); break;
+    case kRoute1x16x16: HUPR_LAUNCH((hupr_k_conv_halo256m_bf16<1, 16, 16, 1>), grid, wg, 0, s, a); break;
+    case kRouteStats4x8x8One: HUPR_LAUNCH((hupr_k_conv_halo256m_bf16<4, 8, 8, 3, 1>), grid, wg, 0, s, a); break;
+    case kRouteStats4x8x8Two: HUPR_LAUNCH((hupr_k_conv_halo256m_bf16<4, 8, 8, 3, 2>), grid, wg, 0, s, a); break;
+    case kRouteStats2x8x16: HUPR_LAUNCH((hupr_k_conv_halo256m_bf16<2, 8, 16, 3, 1>), grid, wg, 0, s, a); break;
+    case kRoute4x8x8: HUPR_LAUNCH((hupr_k_conv_halo256m_bf16<4, 8, 8, 3>), grid, wg, 0, s, a); break;
+    case kRoute2x8x16: HUPR_LAUNCH((hupr_k_conv_halo256m_bf16<2, 8, 16, 3>), grid, wg, 0, s, a); break;
+    }
 }
 
 // ---- which launches the 256-voxel kernel takes (bf16-stored activations only; everything else: the 128-voxel kernel) ----------
@@ -599,54 +594,59 @@ bool conv_halo256_stats_ok(const HaloArgs& a, int Bn) {
     return (long)Bn * (a.D / 2) * (a.H / 8) * (a.W / 16) * n == 256;
 }
 
-bool launch_conv_halo256(HaloArgs a, int Bn, bool abf, hipStream_t s) {
-    if (!abf || !offsets_fit(a, Bn)) return false;
+// Which instantiation takes the launch: sets the tile fields of `a` and returns its route code (conv_halo.h), or 0 when no form of
+// this kernel applies (conv3x3_halo's plan, the one decision behind both its launches and hupr_debug_halo_route).
+int conv_halo256_route(HaloArgs& a, int Bn, bool abf) {
+    if (!abf || !offsets_fit(a, Bn)) return 0;
     if (a.Ci == 32) {
         // 32 input channels (the encoders' first convolution): the 4 x 8 x 8 tile on 64-byte rows, one K-step per tap
         if (!(g_halo_tiles & 16) || a.kd != 3 || a.D % 4 != 0 || a.H % 8 != 0 || a.W % 8 != 0 || a.Co % 64 != 0 || a.stats ||
             (a.in_ld & 7) || (long)a.Co * 27 * a.Ci * 2 >= 0x7ffffff0L)
-            return false;
+            return 0;
         a.n_co_tiles = a.Co / 64;
         a.TD = 4; a.log2TW = 3;
         a.nd = a.D / 4; a.nh = a.H / 8; a.nw = a.W / 8;
         const long tiles_ = (long)Bn * a.nd * a.nh * a.nw * a.n_co_tiles;
-        if (tiles_ < 256 || tiles_ >= (1L << 31)) return false;
-        launch_conv_halo256m(a, s);
-        return true;
+        if (tiles_ < 256 || tiles_ >= (1L << 31)) return 0;
+        return kRouteCi32;
     }
-    if (a.Ci % 64 != 0) return false;
+    if (a.Ci % 64 != 0) return 0;
     if (a.Co == 32) {
         // 32 output channels (the first layer's input gradient): the 8 x 8 x 8 tile, every wave with all the channels
-        if (!(g_halo_tiles & 8) || a.kd != 3 || a.D != 8 || a.H % 8 != 0 || a.W % 8 != 0 || a.stats || (a.out_ld & 7)) return false;
+        if (!(g_halo_tiles & 8) || a.kd != 3 || a.D != 8 || a.H % 8 != 0 || a.W % 8 != 0 || a.stats || (a.out_ld & 7)) return 0;
         a.n_co_tiles = 1;
         a.TD = 8; a.log2TW = 3;
         a.nd = a.D / 8; a.nh = a.H / 8; a.nw = a.W / 8;
         const long tiles32 = (long)Bn * a.nd * a.nh * a.nw;
-        if (tiles32 < 256 || tiles32 >= (1L << 31)) return false;
-        launch_conv_halo256m(a, s);
-        return true;
+        if (tiles32 < 256 || tiles32 >= (1L << 31)) return 0;
+        return kRouteCo32;
     }
-    if (a.Co % 64 != 0) return false;
+    if (a.Co % 64 != 0) return 0;
     a.n_co_tiles = a.Co / 64;
     if (a.kd == 3 && a.D % 4 == 0) {
-        if (!conv_halo256_supported(a, Bn, abf)) return false;
+        if (!conv_halo256_supported(a, Bn, abf)) return 0;
         a.TD = 4; a.log2TW = 3;
         a.nd = a.D / 4; a.nh = a.H / 8; a.nw = a.W / 8;
     } else if (a.kd == 3) {
         // depth not a multiple of four (encoder level 3: D = 2): the 2 x 8 x 16 tile
-        if (!(g_halo_tiles & 2) || a.D % 2 != 0 || a.H % 8 != 0 || a.W % 16 != 0) return false;
+        if (!(g_halo_tiles & 2) || a.D % 2 != 0 || a.H % 8 != 0 || a.W % 16 != 0) return 0;
         a.TD = 2; a.log2TW = 4;
         a.nd = a.D / 2; a.nh = a.H / 8; a.nw = a.W / 16;
     } else {
         // 1 x 3 x 3 convolutions of the decoder: the 1 x 16 x 16 tile (no fused statistics)
-        if (!(g_halo_tiles & 4) || a.kd != 1 || a.D != 1 || a.H % 16 != 0 || a.W % 16 != 0 || a.stats) return false;
+        if (!(g_halo_tiles & 4) || a.kd != 1 || a.D != 1 || a.H % 16 != 0 || a.W % 16 != 0 || a.stats) return 0;
         a.TD = 1; a.log2TW = 4;
         a.nd = 1; a.nh = a.H / 16; a.nw = a.W / 16;
     }
     const long tiles = (long)Bn * a.nd * a.nh * a.nw * a.n_co_tiles;
-    if (tiles < 256 || tiles >= (1L << 31)) return false;
-    launch_conv_halo256m(a, s);      // one persistent workgroup per CU
-    return true;
+    if (tiles < 256 || tiles >= (1L << 31)) return 0;
+    if (a.TD == 1) return kRoute1x16x16;
+    if (a.stats) {                            // fused BatchNorm statistics: 1 or 2 distinct output tiles per workgroup (conv_halo256_stats_ok)
+        const long per_wg = (tiles + kHalo256Grid - 1) / kHalo256Grid;
+        if (a.TD == 4) return (per_wg == 1 || a.n_co_tiles == 1) ? kRouteStats4x8x8One : kRouteStats4x8x8Two;
+        return kRouteStats2x8x16;             // per_wg == 1 (conv_halo256_stats_ok)
+    }
+    return a.TD == 4 ? kRoute4x8x8 : kRoute2x8x16;
 }
 
 }  // namespace hupr

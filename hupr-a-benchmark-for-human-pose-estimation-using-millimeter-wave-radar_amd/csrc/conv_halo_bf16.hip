@@ -443,36 +443,27 @@ static int halo_k_slices(int Bn, int D, int H, int W, int Ci, int Co, int kd, in
 static int g_halo_no_res_prefetch = 0;
 extern "C" void hupr_debug_halo_res_prefetch(int on) { g_halo_no_res_prefetch = on ? 0 : 1; }
 
-static int conv3x3_halo(const void* x, const void* wp_bf16, const float* bias, const void* res, void* y, int Bn, int D,
-                        int H, int W, int Ci, int in_ld, int Co, int out_ld, int res_ld, int kd, bool abf,
-                        hupr_stream_t stream, const char* who, double* stats = nullptr, void* ws = nullptr, size_t ws_bytes = 0,
-                        bool partial_only = false) {
-    HUPR_REQUIRE(x && wp_bf16 && y, "%s: null pointer", who);
+// The launch a call makes, decided once for conv3x3_halo and hupr_debug_halo_route: checks the arguments (HUPR_ERR_ARG, before any
+// launch) and returns the route code (conv_halo.h) with the tile fields of `a` — and, for the 128-voxel kernel, the slice count and
+// units per slice — filled.  `ws_bytes`: usable workspace of a K-sliced call (0: none, the one-launch form).
+static int halo_plan(HaloArgs& a, bool abf, size_t ws_bytes, bool partial_only, int* n_slices, const char* who) {
+    const int Bn = a.Bn, D = a.D, H = a.H, W = a.W, Ci = a.Ci, Co = a.Co, kd = a.kd;
+    *n_slices = 1;
     HUPR_REQUIRE(hupr_conv3x3_halo_supported(D, H, W, Ci, kd, 3, 3, kd / 2, 1, 1), "%s: unsupported geometry", who);
     const int al = abf ? 8 : 4;                      // 16-byte halo loads, 4-channel output vectors
-    HUPR_REQUIRE(Bn > 0 && Co > 0 && Co % 4 == 0 && in_ld % al == 0 && out_ld % 4 == 0 && (!res || res_ld % 4 == 0),
+    HUPR_REQUIRE(Bn > 0 && Co > 0 && Co % 4 == 0 && a.in_ld % al == 0 && a.out_ld % 4 == 0 && (!a.res || a.res_ld % 4 == 0),
                  "%s: bad argument (Co, leading dimensions must be multiples of 4; bf16 in_ld of 8)", who);
-    HaloArgs a;
-    a.x = x; a.wp = reinterpret_cast<const __bf16*>(wp_bf16); a.bias = bias; a.res = res; a.y = y;
-    a.Bn = Bn; a.D = D; a.H = H; a.W = W; a.Ci = Ci; a.in_ld = in_ld; a.Co = Co; a.out_ld = out_ld; a.res_ld = res_ld;
-    a.kd = kd;
-    a.ablate = g_halo_ablate;
-    a.trace = g_halo_trace;
-    a.stats = stats;
-    a.part = nullptr;
-    a.units_per_slice = 0;
-    a.no_res_prefetch = g_halo_no_res_prefetch;
-    if (stats) {
-        HUPR_REQUIRE(abf && !bias && !res && conv_halo256_stats_ok(a, Bn),
+    if (a.stats) {
+        HUPR_REQUIRE(abf && !a.bias && !a.res && conv_halo256_stats_ok(a, Bn),
                      "%s: fused statistics need the 256-voxel kernel (see hupr_conv3x3_halo_stats_supported), no bias / residual", who);
-        HUPR_REQUIRE(launch_conv_halo256(a, Bn, abf, as_stream(stream)), "%s: 256-voxel kernel refused the launch", who);
-        HUPR_LAUNCH_OK("hupr_k_conv_halo256m_bf16<stats>");
-        return HUPR_OK;
+        const int route = conv_halo256_route(a, Bn, abf);
+        HUPR_REQUIRE(route, "%s: 256-voxel kernel refused the launch", who);
+        return route;
     }
     // variants: 0 auto (the 256-voxel kernel where one of its forms applies, else the 128-voxel kernel), 1 force the 128-voxel kernel (A/B comparisons)
-    if (!partial_only && g_halo_variant != 1 && launch_conv_halo256(a, Bn, abf, as_stream(stream))) {
-        HUPR_LAUNCH_OK("hupr_k_conv_halo256m_bf16");
-        return HUPR_OK;
+    if (!partial_only && g_halo_variant != 1) {
+        const int route = conv_halo256_route(a, Bn, abf);
+        if (route) return route;
     }
     if (kd == 3) { a.TD = 2; a.log2TW = 3; } else { a.TD = 1; a.log2TW = 4; }
     a.nd = D / a.TD; a.nh = H / 8; a.nw = W >> a.log2TW;
@@ -484,20 +475,46 @@ static int conv3x3_halo(const void* x, const void* wp_bf16, const float* bias, c
     a.n_co_tiles = (Co + bn - 1) / bn;
     const long blocks = (long)Bn * a.nd * a.nh * a.nw * a.n_co_tiles;
     HUPR_REQUIRE(blocks < (1L << 31), "%s: grid too large", who);
-    hipStream_t s = as_stream(stream);
-    int n_slices = 1;
-    if (ws && abf && n32) {                                       // K-sliced form (bf16 activations, caller supplied the workspace)
+    if (ws_bytes && abf && n32) {                                 // K-sliced form (bf16 activations, caller supplied the workspace)
         int per = 0;
         const int want = halo_k_slices(Bn, D, H, W, Ci, Co, kd, &per);
         const size_t need = (size_t)want * Bn * D * H * W * Co * sizeof(float);
-        if (want > 1 && ws_bytes >= need && ((uintptr_t)ws & 15) == 0) {
-            n_slices = want;
-            a.part = static_cast<float*>(ws);
+        if (want > 1 && ws_bytes >= need) {
+            *n_slices = want;
             a.units_per_slice = per;
         }
     }
-    HUPR_REQUIRE(!partial_only || n_slices > 1,
+    HUPR_REQUIRE(!partial_only || *n_slices > 1,
                  "%s: this geometry is not K-sliced (hupr_conv3x3_halo_splitk_ws_bytes() == 0) or the workspace is too small", who);
+    return kRoute128 + 16 * *n_slices + 8 * (bn == 64) + 4 * (Ci % 64 == 0) + 2 * (kd == 3) + (abf ? 1 : 0);
+}
+
+static int conv3x3_halo(const void* x, const void* wp_bf16, const float* bias, const void* res, void* y, int Bn, int D,
+                        int H, int W, int Ci, int in_ld, int Co, int out_ld, int res_ld, int kd, bool abf,
+                        hupr_stream_t stream, const char* who, double* stats = nullptr, void* ws = nullptr, size_t ws_bytes = 0,
+                        bool partial_only = false) {
+    HUPR_REQUIRE(x && wp_bf16 && y, "%s: null pointer", who);
+    HaloArgs a;
+    a.x = x; a.wp = reinterpret_cast<const __bf16*>(wp_bf16); a.bias = bias; a.res = res; a.y = y;
+    a.Bn = Bn; a.D = D; a.H = H; a.W = W; a.Ci = Ci; a.in_ld = in_ld; a.Co = Co; a.out_ld = out_ld; a.res_ld = res_ld;
+    a.kd = kd;
+    a.ablate = g_halo_ablate;
+    a.trace = g_halo_trace;
+    a.stats = stats;
+    a.part = nullptr;
+    a.units_per_slice = 0;
+    a.no_res_prefetch = g_halo_no_res_prefetch;
+    int n_slices = 1;
+    const int route = halo_plan(a, abf, (ws && ((uintptr_t)ws & 15) == 0) ? ws_bytes : 0, partial_only, &n_slices, who);
+    if (route < 0) return route;
+    hipStream_t s = as_stream(stream);
+    if (route < kRoute128) {
+        launch_conv_halo256(a, route, s);
+        HUPR_LAUNCH_OK(stats ? "hupr_k_conv_halo256m_bf16<stats>" : "hupr_k_conv_halo256m_bf16");
+        return HUPR_OK;
+    }
+    if (n_slices > 1) a.part = static_cast<float*>(ws);
+    const long blocks = (long)Bn * a.nd * a.nh * a.nw * a.n_co_tiles;
 #define HUPR_HALO_LAUNCH(BN_, KC_)                                                                                       \
     do {                                                                                                                 \
         const dim3 grid_((unsigned)blocks, (unsigned)n_slices);                                                          \
@@ -509,7 +526,8 @@ static int conv3x3_halo(const void* x, const void* wp_bf16, const float* bias, c
             else HUPR_LAUNCH((hupr_k_conv_halo_bf16<BN_, KC_, false, false>), grid_, dim3(256), 0, s, a);         \
         }                                                                                                                \
     } while (0)
-    if (Ci % 64 == 0) {
+    const bool n32 = !(route & 8);
+    if (route & 4) {
         if (n32) HUPR_HALO_LAUNCH(32, 64); else HUPR_HALO_LAUNCH(64, 64);
     } else {
         if (n32) HUPR_HALO_LAUNCH(32, 32); else HUPR_HALO_LAUNCH(64, 32);
@@ -523,6 +541,20 @@ static int conv3x3_halo(const void* x, const void* wp_bf16, const float* bias, c
         HUPR_LAUNCH_OK("hupr_k_conv_partial_reduce");
     }
     return HUPR_OK;
+}
+
+// Test aid (include/hupr_debug.h): the route code (conv_halo.h) of the launch hupr_conv3x3_halo_bf16(act) would make — with a fused
+// statistics buffer (stats, the _stats entry) or a large enough workspace (sliced_ws, the _ws entry) — or HUPR_ERR_ARG where it
+// refuses the call.  Nothing is launched; no bias, no residual.
+extern "C" int hupr_debug_halo_route(int Bn, int D, int H, int W, int Ci, int in_ld, int Co, int out_ld, int kd, int abf, int stats,
+                                     int sliced_ws) {
+    static double no_stats_buffer;          // only its presence is read: the plan decides, nothing is written
+    HaloArgs a{};
+    a.Bn = Bn; a.D = D; a.H = H; a.W = W; a.Ci = Ci; a.in_ld = in_ld; a.Co = Co; a.out_ld = out_ld; a.res_ld = Co;
+    a.kd = kd;
+    a.stats = stats ? &no_stats_buffer : nullptr;
+    int n_slices = 1;
+    return halo_plan(a, abf != 0, sliced_ws ? SIZE_MAX : 0, false, &n_slices, "hupr_debug_halo_route");
 }
 
 // y = conv3x3(x) (+bias) (+res): stride 1, "same" padding; kd = 3 (pad 1) or kd = 1.

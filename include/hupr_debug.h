@@ -20,6 +20,13 @@ void hupr_debug_attn_split(int mode);    /* 0 (default): split for Bn == 1 only;
 void hupr_debug_halo_split_k(int on);     /* A/B aid: 0 = never slice the reduction of small grids */
 void hupr_debug_halo_tiles(int mask);     /* test aid: which tiles of the 256-voxel convolution kernel (conv_halo256m_bf16.hip) are in use — bit 0: 4 x 8 x 8, bit 1: 2 x 8 x 16 (D % 4 != 0), bit 2: 1 x 16 x 16 (1 x 3 x 3 taps), bit 3: 8 x 8 x 8 (32 output channels, D = 8), bit 4: 4 x 8 x 8 on 64-byte rows (32 input channels); default 31.  A cleared bit sends those layers to the 128-voxel kernel (the comparison the parity tests make) */
 
+int hupr_debug_halo_route(int Bn, int D, int H, int W, int Ci, int in_ld, int Co, int out_ld, int kd, int abf, int stats, int sliced_ws);
+    /* test aid: which kernel instantiation hupr_conv3x3_halo_bf16 (abf = 0) / _bf16act (abf = 1) would launch for this call (stats: the _stats
+     * entry; sliced_ws: the _ws entry with a large enough workspace), under the switches above; nothing is launched.  HUPR_ERR_ARG where the
+     * call is refused.  1-8: the 256-voxel kernel — 1 the 4 x 8 x 8 tile on 64-byte rows (32 input channels), 2 the 8 x 8 x 8 tile (32 output
+     * channels), 3 the 1 x 16 x 16 tile, 4 / 5 the 4 x 8 x 8 tile with fused statistics of one / two output tiles per workgroup, 6 the 2 x 8 x 16
+     * tile with fused statistics, 7 the 4 x 8 x 8 tile, 8 the 2 x 8 x 16 tile; else the 128-voxel kernel: 256 + 16 * slices + 8 * (BN == 64)
+     * + 4 * (KC == 64) + 2 * (kd == 3) + abf (slices > 1: the K-sliced form) */
 #ifdef __cplusplus
 }
 #endif

@@ -733,9 +733,30 @@ def test_conv_halo256_persistent_kernel_matches_128_voxel_kernel(bf16_math):
     close(ncdhw(y256.cpu())[:1] - ncdhw(res.cpu())[:1].double(), ref, 2e-5, "halo256 vs fp64")
 
 
-@pytest.mark.parametrize("shape", [(8, 64, 64, 8, 32, 32, 3), (5, 128, 128, 4, 32, 32, 3), (16, 64, 64, 1, 64, 64, 1), (9, 320, 64, 1, 64, 64, 1),
-                                   (32, 256, 128, 2, 16, 16, 3)])
-def test_conv_residual_prefetched_under_the_last_stage_equals_the_immediate_epilogue(shape, bf16_math):
+def halo_route(L, B, Ci, Co, D, H, W, kd):
+    """The kernel instantiation a dense bf16-activation halo convolution launches (hupr_debug_halo_route; route codes in
+    include/hupr_debug.h: 1 Ci = 32, 2 Co = 32 (8 x 8 x 8), 3 the 1 x 16 x 16 tile, 7 the 4 x 8 x 8 tile, 8 the 2 x 8 x 16 tile; >= 256 the
+    128-voxel kernel)."""
+    return L.hupr_debug_halo_route(B, D, H, W, Ci, Ci, Co, Co, kd, 1, 0, 0)
+
+
+# (shape, route under the default tile mask): every case reaches the 256-voxel form its test names (>= 256 tiles); checked without a
+# GPU by tests/test_conv_halo_route.py
+RESIDUAL_PREFETCH_CASES = [((8, 64, 64, 8, 32, 32, 3), 7), ((9, 128, 128, 4, 32, 32, 3), 7), ((16, 64, 64, 1, 64, 64, 1), 3),
+                           ((17, 320, 64, 1, 64, 64, 1), 3), ((64, 256, 128, 2, 16, 16, 3), 8)]
+HALO256M_4X8X8_CASES = [((4, 64, 64, 8, 64, 64), 7), ((9, 128, 128, 4, 32, 32), 7), ((3, 64, 128, 8, 32, 64), 7)]
+HALO256M_CO32_CASES = [((4, 64, 8, 64, 64), 2), ((9, 128, 8, 32, 64), 2), ((7, 64, 8, 64, 40), 2)]
+HALO256M_TWO_SLICE_CASES = [((32, 64, 256, 2, 16, 16), 8), ((33, 128, 128, 2, 16, 32), 8), ((16, 320, 64, 1, 64, 64), 3),
+                            ((15, 64, 192, 1, 32, 48), 3)]
+FIRST_LAYER_CASES = [((32, 64, 8, 64, 64, True), 1), ((7, 128, 4, 32, 48, False), 1)]
+
+
+def _shape_ids(cases):
+    return ["shape%d" % i for i in range(len(cases))]
+
+
+@pytest.mark.parametrize("shape,route", RESIDUAL_PREFETCH_CASES, ids=_shape_ids(RESIDUAL_PREFETCH_CASES))
+def test_conv_residual_prefetched_under_the_last_stage_equals_the_immediate_epilogue(shape, route, bf16_math):
     """256-voxel 16 x 16 x 32 convolution with a residual (the second input gradient of a block's pair, the decoder's conv + residual):
     the residual elements are fetched into registers under the tile's last stage and the tile is parked like any other, instead of
     being read in an immediate epilogue — the same fp32 sum rounded once: identical bits; also with the output written over the
@@ -743,6 +764,7 @@ def test_conv_residual_prefetched_under_the_last_stage_equals_the_immediate_epil
     from hupr_amd import functional as F_
     L = F_.rt.lib()
     B, Ci, Co, D, H, W, kd = shape
+    assert halo_route(L, B, Ci, Co, D, H, W, kd) == route
     x = rnd(B, D, H, W, Ci, seed=56).cuda().bfloat16()
     w = rnd(Co, Ci, kd, 3, 3, seed=57, scale=(Ci * 9 * kd) ** -0.5).cuda()
     res = rnd(B, D, H, W, Co, seed=58).cuda().bfloat16()
@@ -767,8 +789,8 @@ def test_conv_residual_prefetched_under_the_last_stage_equals_the_immediate_epil
     assert not torch.equal(y0, out[1][0])
 
 
-@pytest.mark.parametrize("shape", [(4, 64, 64, 8, 64, 64), (9, 128, 128, 4, 32, 32), (3, 64, 128, 8, 32, 64)])
-def test_conv_halo256m_4x8x8_tile_matches_the_128_voxel_kernel(shape, bf16_math):
+@pytest.mark.parametrize("shape,route", HALO256M_4X8X8_CASES, ids=_shape_ids(HALO256M_4X8X8_CASES))
+def test_conv_halo256m_4x8x8_tile_matches_the_128_voxel_kernel(shape, route, bf16_math):
     """The 256-voxel kernel's 4 x 8 x 8 tile (v_mfma_f32_16x16x32_bf16, persistent workgroups, fragment pipeline across stage and item
     boundaries) against the 128-voxel kernel (hupr_debug_halo_tiles(0): 32 x 32 x 16, another fp32 order inside a 32-channel group —
     a handful of outputs one bf16 step apart) and against fp64: one and two channel chunks, one and two output-channel tiles, a tile
@@ -776,10 +798,12 @@ def test_conv_halo256m_4x8x8_tile_matches_the_128_voxel_kernel(shape, bf16_math)
     from hupr_amd import functional as F_
     L = F_.rt.lib()
     B, Ci, Co, D, H, W = shape
+    assert halo_route(L, B, Ci, Co, D, H, W, 3) == route
     x = rnd(B, D, H, W, Ci, seed=54).cuda().bfloat16()
     w = rnd(Co, Ci, 3, 3, 3, seed=55, scale=(Ci * 27) ** -0.5).cuda()
     try:
         L.hupr_debug_halo_tiles(0)
+        assert halo_route(L, B, Ci, Co, D, H, W, 3) >= 256
         y_128 = F_._conv_raw(x, w, 0, None, None, Co, (3, 3, 3), (1, 1, 1), (D, H, W))
         L.hupr_debug_halo_tiles(31)
         y_m16 = F_._conv_raw(x, w, 0, None, None, Co, (3, 3, 3), (1, 1, 1), (D, H, W))
@@ -794,8 +818,8 @@ def test_conv_halo256m_4x8x8_tile_matches_the_128_voxel_kernel(shape, bf16_math)
     close(ncdhw(y_m16.float().cpu())[:1], ref, 1e-2, "halo256m (bf16 store) vs fp64")
 
 
-@pytest.mark.parametrize("shape", [(4, 64, 8, 64, 64), (5, 128, 8, 32, 64), (7, 64, 8, 64, 40)])
-def test_conv_halo256m_32_output_channels_match_the_128_voxel_kernel(shape, bf16_math):
+@pytest.mark.parametrize("shape,route", HALO256M_CO32_CASES, ids=_shape_ids(HALO256M_CO32_CASES))
+def test_conv_halo256m_32_output_channels_match_the_128_voxel_kernel(shape, route, bf16_math):
     """32 output channels (the input gradient of the encoders' first convolution, `layers.py:194` Conv3d(32 -> 64) seen from its output):
     the 16 x 16 x 32 kernel's 8 x 8 x 8 tile — eight waves = eight depth slices, every wave with all the channels, the halo's padding
     planes zeroed once — against the 128-voxel kernel these launches ran on before (hupr_debug_halo_tiles(7)) and against fp64; one and two
@@ -804,6 +828,7 @@ def test_conv_halo256m_32_output_channels_match_the_128_voxel_kernel(shape, bf16
     L = F_.rt.lib()
     B, Ci, D, H, W = shape
     Co = 32
+    assert halo_route(L, B, Ci, Co, D, H, W, 3) == route
     x = rnd(B, D, H, W, Ci, seed=154).cuda().bfloat16()
     w = rnd(Co, Ci, 3, 3, 3, seed=155, scale=(Ci * 27) ** -0.5).cuda()
     res = rnd(B, D, H, W, Co, seed=156).cuda().bfloat16()
@@ -811,6 +836,7 @@ def test_conv_halo256m_32_output_channels_match_the_128_voxel_kernel(shape, bf16
     try:
         for mode in (7, 31):
             L.hupr_debug_halo_tiles(mode)
+            assert (halo_route(L, B, Ci, Co, D, H, W, 3) == route) == (mode == 31)
             out[mode] = (F_._conv_raw(x, w, 0, None, None, Co, (3, 3, 3), (1, 1, 1), (D, H, W)),
                          F_._conv_raw(x, w, 0, None, res, Co, (3, 3, 3), (1, 1, 1), (D, H, W)))
         again = F_._conv_raw(x, w, 0, None, None, Co, (3, 3, 3), (1, 1, 1), (D, H, W))
@@ -826,8 +852,8 @@ def test_conv_halo256m_32_output_channels_match_the_128_voxel_kernel(shape, bf16
     close(ncdhw(out[31][1].float().cpu())[:2], ref + ncdhw(res.float().cpu())[:2].double(), 1e-2, "halo256m 8x8x8, Co = 32 + residual vs fp64")
 
 
-@pytest.mark.parametrize("shape", [(32, 64, 256, 2, 16, 16), (17, 128, 128, 2, 16, 32), (8, 320, 64, 1, 64, 64), (9, 64, 192, 1, 32, 48)])
-def test_conv_halo256m_two_slice_tile_matches_the_128_voxel_kernel(shape, bf16_math):
+@pytest.mark.parametrize("shape,route", HALO256M_TWO_SLICE_CASES, ids=_shape_ids(HALO256M_TWO_SLICE_CASES))
+def test_conv_halo256m_two_slice_tile_matches_the_128_voxel_kernel(shape, route, bf16_math):
     """Depth 2 (encoder level 3) and depth 1 with 1 x 3 x 3 taps (decoder): the 16 x 16 x 32 kernel's 2 x 8 x 16 / 1 x 16 x 16 tiles against the 128-voxel kernel these layers ran on before
     (hupr_debug_halo_tiles(1)) — same products, another fp32 order: a few outputs one bf16 step apart — and against fp64; with and
     without the residual epilogue; even and uneven tile counts over the 256 workgroups."""
@@ -835,6 +861,7 @@ def test_conv_halo256m_two_slice_tile_matches_the_128_voxel_kernel(shape, bf16_m
     L = F_.rt.lib()
     B, Ci, Co, D, H, W = shape
     k3, pad = ((3, 3, 3), (1, 1, 1)) if D > 1 else ((1, 3, 3), (0, 1, 1))      # D = 1: the decoder's 1 x 3 x 3 taps on the 1 x 16 x 16 tile
+    assert halo_route(L, B, Ci, Co, D, H, W, k3[0]) == route
     x = rnd(B, D, H, W, Ci, seed=56).cuda().bfloat16()
     w = rnd(Co, Ci, *k3, seed=57, scale=(Ci * 9 * k3[0]) ** -0.5).cuda()
     res = rnd(B, D, H, W, Co, seed=58).cuda().bfloat16()
@@ -842,6 +869,7 @@ def test_conv_halo256m_two_slice_tile_matches_the_128_voxel_kernel(shape, bf16_m
     try:
         for mode in (1, 31):                # 7: all tiles, 1: the 4 x 8 x 8 tile only
             L.hupr_debug_halo_tiles(mode)
+            assert (halo_route(L, B, Ci, Co, D, H, W, k3[0]) == route) == (mode == 31)
             out[mode] = (F_._conv_raw(x, w, 0, None, None, Co, k3, pad, (D, H, W)),
                          F_._conv_raw(x, w, 0, None, res, Co, k3, pad, (D, H, W)))
     finally:
@@ -1521,8 +1549,8 @@ def test_interp_mnet_cast_bf16_activations():
     assert torch.equal(m[torch.bfloat16][1], m[torch.float32][1]) and torch.equal(m[torch.bfloat16][2], m[torch.float32][2])
 
 
-@pytest.mark.parametrize("shape", [(32, 64, 8, 64, 64, True), (7, 128, 4, 32, 48, False)])
-def test_conv_first_layer_shape_32_input_channels(shape, bf16_math):
+@pytest.mark.parametrize("shape,route", FIRST_LAYER_CASES, ids=_shape_ids(FIRST_LAYER_CASES))
+def test_conv_first_layer_shape_32_input_channels(shape, route, bf16_math):
     """Ci = 32 (the encoders' first convolution, `layers.py:236`): the 256-voxel kernel's 64-byte-row form (one K-step per tap, a stage = one kz
     plane of nine taps, three fragment banks, bias added in front of the parked tile's rounding; round 6) against the 128-voxel kernel on
     the same bf16 operands — same products, another fp32 summation order: equal up to one rounding of the bf16 store — and against fp64;
@@ -1531,6 +1559,7 @@ def test_conv_first_layer_shape_32_input_channels(shape, bf16_math):
     L = F_.rt.lib()
     B, Co, D, H, W, with_bias = shape
     Ci = 32
+    assert halo_route(L, B, Ci, Co, D, H, W, 3) == route
     x = _q(rnd(B, D, H, W, Ci, seed=90)).cuda().bfloat16()
     w = rnd(Co, Ci, 3, 3, 3, seed=91, scale=(Ci * 27) ** -0.5).cuda()
     bias = rnd(Co, seed=92).cuda() if with_bias else None
@@ -1539,6 +1568,7 @@ def test_conv_first_layer_shape_32_input_channels(shape, bf16_math):
         y256 = run()
         y256b = run()
         L.hupr_debug_halo_tiles(15)           # bit 4 cleared: the 128-voxel kernel takes the launch
+        assert halo_route(L, B, Ci, Co, D, H, W, 3) >= 256
         y128 = run()
     finally:
         L.hupr_debug_halo_tiles(31)
