@@ -1228,6 +1228,29 @@ extern "C" size_t hupr_attn_fwd_split_ws_bytes(int Bn, int N, int C) {
     return S > 1 ? (size_t)S * Bn * N * (C + 2) * sizeof(float) : 0;
 }
 
+// The one place that picks the attention kernels of a call (hupr_attn_route: the same decision, nothing launched).  Forward: the
+// ping-pong kernel at the level-1 shape (bf16 operands, C = 64, N % 256 == 0, K addressable by 32-bit offsets), else the key-split
+// form when a workspace is given and attn_splits() asks for shares, else the one-pass kernel; dK / dV: the 512-thread kernel at the
+// level-1 shape, else hupr_k_attn_bwd_dkv<D, NH = 1> (C = 64, 128) or <256, NH = 2>; xmap: the batch-to-XCD remap of the backward.
+// The forward's single, batch and split launchers and the backward's single and batch launchers all launch from this code.
+static int attn_plan(int Bn, int N, int C, int ldk, bool bf16_operands, bool split_ws) {
+    if (Bn <= 0 || !hupr_attn_flash_supported(N, C) || ldk < C || ldk % 8 != 0) return HUPR_ERR_ARG;
+    const bool level1 = bf16_operands && C == 64 && N % 256 == 0;
+    const int S = split_ws ? attn_splits(Bn, N) : 1;
+    int fwd = HUPR_ATTN_FWD_ONE_PASS;
+    if (S <= 1 && level1 && (long)N * ldk * 2 < (1L << 31)) fwd = HUPR_ATTN_FWD_PP64;
+    else if (S > 1) fwd = HUPR_ATTN_FWD_SPLIT;
+    const int dkv = level1 ? HUPR_ATTN_DKV512 : (C == 256 ? HUPR_ATTN_DKV_NH2 : HUPR_ATTN_DKV_NH1);
+    return fwd | dkv | ((Bn % 8 == 0) ? HUPR_ATTN_XMAP : 0) | ((fwd == HUPR_ATTN_FWD_SPLIT ? S : 1) << 8);
+}
+static inline int plan_fwd(int route) { return route & 3; }
+static inline int plan_splits(int route) { return route >> 8; }
+static inline int plan_dkv(int route) { return route & 12; }
+static inline int plan_xmap(int route) { return (route & HUPR_ATTN_XMAP) ? 1 : 0; }
+extern "C" int hupr_attn_route(int Bn, int N, int C, int ldk, int bf16_operands, int split_ws) {
+    return attn_plan(Bn, N, C, ldk, bf16_operands != 0, split_ws != 0);
+}
+
 template <typename TI, bool QS = false>
 static int attn_fwd(const char* who, const TI* K, int ldk, const TI* Q, int ldq, const TI* V, const float* Vres, float* out,
                     float* lse, void* out16, int ld16, int Bn, int N, int C, hupr_stream_t stream, void* ws = nullptr,
@@ -1236,13 +1259,15 @@ static int attn_fwd(const char* who, const TI* K, int ldk, const TI* Q, int ldq,
     HUPR_REQUIRE(hupr_attn_flash_supported(N, C), "%s: unsupported shape N=%d C=%d", who, N, C);
     HUPR_REQUIRE(ldk >= C && ldq >= C && ldk % 8 == 0 && ldq % 8 == 0, "%s: bad row strides %d %d", who, ldk, ldq);
     HUPR_REQUIRE(!out16 || (ld16 >= C && ld16 % 4 == 0), "%s: bad bf16 output stride %d", who, ld16);
+    const int route = attn_plan(Bn, N, C, ldk, sizeof(TI) == 2, ws != nullptr);
+    HUPR_REQUIRE(route > 0, "%s: bad argument", who);
     dim3 grid(N / 128, Bn);
     __bf16* o16 = static_cast<__bf16*>(out16);
     float* const np = nullptr;
-    const int S = ws ? attn_splits(Bn, N) : 1;
+    const int S = plan_splits(route);
     if constexpr (sizeof(TI) == 2) {
         // level-1 shape: the ping-pong kernel (256 queries per 512-thread workgroup, LDS-DMA ring)
-        if (S <= 1 && C == 64 && N % 256 == 0 && N >= 256 && (long)N * ldk * 2 < (1L << 31)) {
+        if (plan_fwd(route) == HUPR_ATTN_FWD_PP64) {
 #define HUPR_PP_FWD() HUPR_LAUNCH(hupr_k_attn_fwd_pp64<false>, dim3((N / 256) * Bn), dim3(512), 0, as_stream(stream), K, Q, V, Vres, \
                                            out, lse, N, Bn, ldk, ldq, o16, ld16, g_attn_trace)
             if constexpr (QS) {
@@ -1257,7 +1282,7 @@ static int attn_fwd(const char* who, const TI* K, int ldk, const TI* Q, int ldq,
             return HUPR_OK;
         }
     }
-    if (S > 1) {
+    if (plan_fwd(route) == HUPR_ATTN_FWD_SPLIT) {
         HUPR_REQUIRE(ws_bytes >= hupr_attn_fwd_split_ws_bytes(Bn, N, C), "%s: workspace too small", who);
         const long rows = (long)Bn * N;
         float* part_o = static_cast<float*>(ws);
@@ -1311,8 +1336,16 @@ static int attn_fwd_batch(const char* who, const hupr_attn_item* items, int n_it
     HUPR_REQUIRE(items && n_items >= 1 && n_items <= 4 && Bn > 0, "%s: bad argument", who);
     HUPR_REQUIRE(hupr_attn_flash_supported(N, C), "%s: unsupported shape N=%d C=%d", who, N, C);
     HUPR_REQUIRE(ldk >= C && ldq >= C && ldk % 8 == 0 && ldq % 8 == 0, "%s: bad row strides %d %d", who, ldk, ldq);
-    const int S = ws ? attn_splits(Bn, N) : 1;
-    if (S == 1 && C == 64 && N % 256 == 0 && (long)N * ldk * 2 < (1L << 31)) {
+    const int route = attn_plan(Bn, N, C, ldk, true, ws != nullptr);
+    HUPR_REQUIRE(route > 0, "%s: bad argument", who);
+    const int S = plan_splits(route);
+    bool any16 = false;
+    for (int i = 0; i < n_items; ++i) {         // every item before anything is launched: a refused call leaves all outputs alone
+        HUPR_REQUIRE(items[i].K && items[i].Q && items[i].V && items[i].out && items[i].lse, "%s: null pointer in item %d", who, i);
+        any16 = any16 || items[i].out16;
+    }
+    HUPR_REQUIRE(!any16 || (ld16 >= C && ld16 % 4 == 0), "%s: bad bf16 output stride %d", who, ld16);
+    if (plan_fwd(route) == HUPR_ATTN_FWD_PP64) {
         // level-1 shape: each attention fills the chip by itself with the ping-pong kernel — one launch per item
         for (int i = 0; i < n_items; ++i) {
             const int rc = attn_fwd<__bf16, QS>(who, static_cast<const __bf16*>(items[i].K), ldk, static_cast<const __bf16*>(items[i].Q), ldq,
@@ -1326,15 +1359,11 @@ static int attn_fwd_batch(const char* who, const hupr_attn_item* items, int n_it
     AttnBatch b = AttnBatch();
     b.n = n_items;
     b.splits = S;
-    bool any16 = false;
     for (int i = 0; i < n_items; ++i) {
-        HUPR_REQUIRE(items[i].K && items[i].Q && items[i].V && items[i].out && items[i].lse, "%s: null pointer in item %d", who, i);
         b.K[i] = items[i].K; b.Q[i] = items[i].Q; b.V[i] = items[i].V; b.Vres[i] = items[i].Vres;
         b.out[i] = items[i].out; b.lse[i] = items[i].lse; b.out16[i] = static_cast<__bf16*>(items[i].out16);
-        any16 = any16 || items[i].out16;
     }
-    HUPR_REQUIRE(!any16 || (ld16 >= C && ld16 % 4 == 0), "%s: bad bf16 output stride %d", who, ld16);
-    if (S == 1) {                                   // one-pass kernel, blockIdx.z = item
+    if (plan_fwd(route) == HUPR_ATTN_FWD_ONE_PASS) {     // one-pass kernel, blockIdx.z = item
         const dim3 g1(N / 128, Bn, n_items);
         hipStream_t s1 = as_stream(stream);
         const __bf16* const k0 = nullptr;
@@ -1408,18 +1437,21 @@ static int attn_bwd(const char* who, const TI* K, int ldk, const TI* Q, int ldq,
                      lddk % 4 == 0 && lddq % 4 == 0,
                  "%s: bad row strides", who);
     HUPR_REQUIRE(!(residual && accumulate), "%s: accumulate is for the non-residual form", who);
+    const int route = attn_plan(Bn, N, C, ldk, sizeof(TI) == 2, false);
+    HUPR_REQUIRE(route > 0, "%s: bad argument", who);
     hipStream_t s = as_stream(stream);
     const long rows = (long)Bn * N;
     dim3 grid(N / 128, Bn);
     const float* add32 = residual ? dout32 : (accumulate ? dV : nullptr);
     const __bf16* add16 = (residual && !dout32) ? reinterpret_cast<const __bf16*>(dO) : nullptr;
     const dim3 pgrid((unsigned)((rows + 15) / 16));
-    const int xmap = (Bn % 8 == 0) ? 1 : 0;
+    const int xmap = plan_xmap(route);
+    const bool dkv512 = plan_dkv(route) == HUPR_ATTN_DKV512;
 #define HUPR_ATTN_BWD(D_, NH_)                                                                                             \
     if (dout32) HUPR_LAUNCH((hupr_k_attn_prep<D_, float>), pgrid, dim3(256), 0, s, dout32, C, out, V32, Dq, rows, residual); \
     else HUPR_LAUNCH((hupr_k_attn_prep<D_, __bf16>), pgrid, dim3(256), 0, s, reinterpret_cast<const __bf16*>(dO), lddo, out, V32, Dq, rows, residual); \
     HUPR_LAUNCH((hupr_k_attn_bwd_dq<D_, TI, QS>), grid, dim3(256), 0, s, K, Q, V, dO, lse, Dq, dQ, N, ldk, ldq, lddq, lddo, xmap);  \
-    if (D_ == 64 && sizeof(TI) == 2 && N % 256 == 0)                                                       \
+    if (dkv512)                                                                                                              \
         HUPR_LAUNCH(hupr_k_attn_bwd_dkv512<QS>, dim3(N / 256, Bn), dim3(512), 0, s, reinterpret_cast<const __bf16*>(K),       \
                            reinterpret_cast<const __bf16*>(Q), reinterpret_cast<const __bf16*>(V), reinterpret_cast<const __bf16*>(dO), \
                            add32, lse, Dq, dK, dV, N, ldk, ldq, lddk, lddo, add16, lddo, xmap);                                 \
@@ -1446,7 +1478,9 @@ static int attn_bwd_batch(const char* who, const hupr_attn_bwd_item* items, int 
         HUPR_REQUIRE(t.K && t.Q && t.V && t.dO && t.V32 && t.out && t.lse && t.dK && t.dQ && t.dV && t.Dq, "%s: null pointer in item %d", who, i);
         HUPR_REQUIRE(!(t.residual && t.accumulate), "%s: accumulate is for the non-residual form (item %d)", who, i);
     }
-    const bool level1 = C == 64 && N % 256 == 0;       // its 512-thread dK / dV kernel takes one attention per launch
+    const int route = attn_plan(Bn, N, C, ldk, true, false);
+    HUPR_REQUIRE(route > 0, "%s: bad row strides", who);
+    const bool level1 = plan_dkv(route) == HUPR_ATTN_DKV512;      // the 512-thread dK / dV kernel takes one attention per launch
     if (n_items == 1) {
         for (int i = 0; i < n_items; ++i) {
             const hupr_attn_bwd_item& t = items[i];
@@ -1461,7 +1495,7 @@ static int attn_bwd_batch(const char* who, const hupr_attn_bwd_item* items, int 
                      lddk % 4 == 0 && lddq % 4 == 0, "%s: bad row strides", who);
     hipStream_t s = as_stream(stream);
     const long rows = (long)Bn * N;
-    const int xmap = (Bn % 8 == 0) ? 1 : 0;
+    const int xmap = plan_xmap(route);
     AttnBwdBatch b = AttnBwdBatch();
     b.n = n_items;
     b.Bn = Bn;

@@ -331,6 +331,23 @@ int hupr_attn_fwd_bf16in_ld(const void* K, int ldk, const void* Q, int ldq, cons
  * the workspace that needs, or 0 when the one-pass kernel is used (ws may then be null): by default the split is taken for
  * single-sample calls only, so that batched runs keep the rounding their parity gates were measured with. */
 size_t hupr_attn_fwd_split_ws_bytes(int Bn, int N, int C);
+/* Which kernels an attention call of this shape launches (nothing is launched): bf16_operands = 0 for hupr_attn_fwd_bf16 /
+ * hupr_attn_bwd_bf16 (fp32 operands), else 1; split_ws != 0 for a forward given a workspace (the _ws entries with ws != NULL).  The
+ * single, batch, plain and _qs entries of one shape take the same route.  HUPR_ERR_ARG where (Bn, N, C, ldk) is refused.  Otherwise
+ *   route & 3  : the forward kernel — HUPR_ATTN_FWD_PP64 (the 512-thread ping-pong kernel), _ONE_PASS (hupr_k_attn_fwd<C>), _SPLIT
+ *                (hupr_k_attn_fwd<C> over key shares + hupr_k_attn_combine<C>)
+ *   route & 12 : the dK / dV kernel — HUPR_ATTN_DKV512 (512 threads, C = 64), _DKV_NH1 (hupr_k_attn_bwd_dkv<C, 1>), _DKV_NH2 (<256, 2>)
+ *   route & 16 : HUPR_ATTN_XMAP, the backward's batch-to-XCD remap (Bn % 8 == 0)
+ *   route >> 8 : the forward's key shares S (1 unless split)
+ * A backward batch call launches 2 + (dK / dV rounds) kernels, 2 + n_items with HUPR_ATTN_DKV512. */
+#define HUPR_ATTN_FWD_PP64 1
+#define HUPR_ATTN_FWD_ONE_PASS 2
+#define HUPR_ATTN_FWD_SPLIT 3
+#define HUPR_ATTN_DKV512 4
+#define HUPR_ATTN_DKV_NH1 8
+#define HUPR_ATTN_DKV_NH2 12
+#define HUPR_ATTN_XMAP 16
+int hupr_attn_route(int Bn, int N, int C, int ldk, int bf16_operands, int split_ws);
 /* Up to four independent attentions of one shape (the four of an MSCSA level, reference models/layers.py:150-163) in as few launches as
  * fill the chip.  Where hupr_attn_fwd_split_ws_bytes() > 0 (single-sample inference — bound by launches, not work): ONE split launch and
  * ONE merge launch, ws: n_items times that size.  Otherwise (training batches; ws may be NULL): ONE launch of the one-pass kernel over all

@@ -641,7 +641,10 @@ def test_flash_attention_bf16(N, C, residual, bf16_math):
     close(vg.grad, v2.grad, 1e-2, "flash vs materialised dV")
 
 
-@pytest.mark.parametrize("B,N,C", [(1, 4096, 64), (3, 1024, 128), (1, 256, 256), (2, 128, 64)])
+SPLIT_KEYS_CASES = [(1, 4096, 64), (3, 1024, 128), (1, 256, 256), (2, 128, 64)]     # (B, N, C): split under hupr_debug_attn_split(1)
+
+
+@pytest.mark.parametrize("B,N,C", SPLIT_KEYS_CASES)
 def test_attention_split_keys_matches_plain_forward(B, N, C, bf16_math):
     """Small batches walk the keys in shares (blockIdx.z) and merge them in a second launch; against the plain kernel on the same
     bf16 operands (output, bf16 copy, log-sum-exp) — the shares round P relative to their own running maxima, hence a tolerance —
@@ -1342,8 +1345,12 @@ def _qs_case(B, N, C, seed, kscale=None, profile=None):
     return (kb, qsb, vb, gb, v, g), (kr, qr, vr)
 
 
-@pytest.mark.parametrize("B,N,C,residual", [(2, 4096, 64, True), (8, 512, 64, False), (2, 384, 64, True), (2, 256, 128, True),
-                                            (3, 1024, 128, False), (2, 256, 256, True), (1, 384, 256, False)])
+# (B, N, C, residual); tests/test_attn_route.py asserts the routes the docstring below names (hupr_attn_route)
+QS_FP64_CASES = [(2, 4096, 64, True), (8, 512, 64, False), (2, 384, 64, True), (2, 256, 128, True), (3, 1024, 128, False),
+                 (2, 256, 256, True), (1, 384, 256, False)]
+
+
+@pytest.mark.parametrize("B,N,C,residual", QS_FP64_CASES)
 def test_flash_attention_qs_kernels_vs_fp64(B, N, C, residual, bf16_math):
     """The QS entry points (query operand = log2(e) Q as bf16; accumulator input = minus the deferred running maximum / minus the
     stored log-sum-exp) through the C ABI against fp64 on the SAME bf16 operands: forward, log-sum-exp in natural units, the bf16
@@ -1392,7 +1399,7 @@ def test_flash_attention_qs_deferred_maximum(bf16_math):
     with the backward kernels consuming the log-sum-exp it produced."""
     from hupr_amd import functional as F_
     L, rt = F_.rt.lib(), F_.rt
-    B, N, C = 8, 1024, 64
+    B, N, C = DEFERRED_MAXIMUM_SHAPE
     prof = torch.cat([torch.linspace(0.05, 0.3, 256), torch.linspace(0.3, 3.0, 256), torch.full((256,), 6.0), torch.linspace(6.0, 0.1, 256)])
     (kb, qsb, vb, gb, v32, g32), (kr, qr, vr) = _qs_case(B, N, C, 340, kscale=1.0, profile=prof)
     sref = torch.einsum("bjc,bkc->bjk", kr, qr)
@@ -1415,7 +1422,11 @@ def test_flash_attention_qs_deferred_maximum(bf16_math):
     close(dk, kr.grad, 3e-2, "dK")
 
 
-@pytest.mark.parametrize("B,N,C", [(1, 4096, 64), (1, 1024, 128), (1, 256, 256)])
+QS_SPLIT_KEYS_CASES = [(1, 4096, 64), (1, 1024, 128), (1, 256, 256)]                # (B, N, C): split under the default policy
+DEFERRED_MAXIMUM_SHAPE = (8, 1024, 64)                                                   # (B, N, C) of the ping-pong forward
+
+
+@pytest.mark.parametrize("B,N,C", QS_SPLIT_KEYS_CASES)
 def test_attention_qs_split_keys(B, N, C, bf16_math):
     """Single-sample inference: the key-split form of the QS forward (shares in binary orders, merged by hupr_k_attn_combine<QS>)."""
     from hupr_amd import functional as F_
