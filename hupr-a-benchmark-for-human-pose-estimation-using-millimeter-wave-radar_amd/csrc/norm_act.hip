@@ -1027,12 +1027,14 @@ extern "C" int hupr_prelu_bwd_partials_bf16act(const void* dy, const void* x, co
 // out[i][0] = sum of the n[i] doubles at partial[i], i < n_items, in ceil(n_items / 16) launches; each sum as hupr_prelu_bwd_* forms it
 extern "C" int hupr_sum_partials_multi(const hupr_sum_item* items, int n_items, hupr_stream_t stream) {
     HUPR_REQUIRE(items && n_items > 0, "hupr_sum_partials_multi: bad argument");
+    // every item is checked before the first launch: a refused call launches nothing
+    for (int i = 0; i < n_items; ++i)
+        HUPR_REQUIRE(items[i].partial && items[i].out && items[i].n > 0, "hupr_sum_partials_multi: bad item %d", i);
     for (int i0 = 0; i0 < n_items; i0 += 16) {
         SumItems t{};
         t.n_items = n_items - i0 < 16 ? n_items - i0 : 16;
         for (int i = 0; i < t.n_items; ++i) {
             const hupr_sum_item& it = items[i0 + i];
-            HUPR_REQUIRE(it.partial && it.out && it.n > 0, "hupr_sum_partials_multi: bad item %d", i0 + i);
             t.partial[i] = static_cast<const double*>(it.partial);
             t.n[i] = it.n;
             t.out[i] = it.out;
