@@ -1,4 +1,4 @@
-from .optim import FusedAdam  # noqa: F401
+from .optim import FusedAdam, FusedSGD  # noqa: F401
 
 
 def __getattr__(name):          # lazy: Runner pulls in datasets/models

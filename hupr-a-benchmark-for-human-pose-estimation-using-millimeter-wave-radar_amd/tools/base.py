@@ -127,7 +127,7 @@ class BaseRunner():
                   "process feeds them HUPR_FFT_ZERO_DOPPLER=%s" % _pre.ZERO_DOPPLER)
         if not self.args.eval and not getattr(self.args, "pretrained", False):
             print("==========>Load the previous optimizer")
-            self.optimizer.load_state_dict(ck["optimizer_state_dict"])      # torch.optim.Adam layout either way
+            self.optimizer.load_state_dict(ck["optimizer_state_dict"])      # TRAINING.optimizer's torch layout (optim.SGD / optim.Adam)
             self.start_epoch = ck["epoch"]
             self.logger.updateBestAcc(ck["accuracy"])
         print("==========>Load the model weight from %s, saved at epoch %d" % (self.dir, ck["epoch"]))

@@ -1,5 +1,5 @@
 """Training/inference engine shared by the Runner and bench.py: HuPRNet + LossComputer +
-flat gradient buckets (+ RCCL all-reduce when world_size > 1) + fused Adam, optionally fed by the
+flat gradient buckets (+ RCCL all-reduce when world_size > 1) + fused Adam or SGD, optionally fed by the
 on-GPU FFT loader (int16 ADC cubes -> normalised network input, config "C3" of BASELINE.json)."""
 
 import os
@@ -11,7 +11,7 @@ from ..misc.losses import LossComputer
 from ..models import HuPRNet
 from ..preprocessing.process_iwr1843 import fft_chain_loader, fft_chain_loader_means
 from .distributed import GradientBuckets
-from .optim import FusedAdam
+from .optim import make_optimizer
 
 
 class TrainEngine:
@@ -26,8 +26,7 @@ class TrainEngine:
         self.world_size = dist.get_world_size() if dist.is_initialized() else 1
         # (data-parallel runs keep the library default of two compute streams: with the stream-ordered hupr_allreduce_bucket the
         # side-stream branch gains 3 % with collectives in flight — 1 368 -> 1 412 frames/s with forced single-rank collectives)
-        self.optimizer = FusedAdam(self.model.parameters(), lr=lr if lr is not None else cfg.TRAINING.lr,
-                                   betas=(0.9, 0.999), weight_decay=1e-4)
+        self.optimizer = make_optimizer(cfg, self.model.parameters(), lr if lr is not None else cfg.TRAINING.lr)
         self.optimizer.attach_flat_buckets(self.buckets.flat_pairs(), self.buckets.layout())
         self.optimizer.grad_scale = 1.0 / self.world_size
         self.G = cfg.DATASET.numGroupFrames

@@ -1,50 +1,65 @@
-"""Adam with coupled L2 weight decay on the gfx950 fused kernel.
+"""Adam and SGD with momentum, both with coupled L2 weight decay, on the gfx950 fused kernels.
 
-Same update rule and ``state_dict`` layout as ``torch.optim.Adam`` (what the reference builds in
-tools/base.py:47: lr 1e-4, betas (0.9, 0.999), weight_decay 1e-4 on every parameter), so the
-reference's ``optimizer_state_dict`` checkpoints interchange.  One kernel launch per parameter
-tensor, or one per flat bucket when the parameters were flattened by ``tools.distributed``.
+The reference builds one of the two from ``TRAINING.optimizer`` (tools/base.py:44-47): ``optim.SGD(lr, momentum=0.9,
+weight_decay=1e-4)`` or ``optim.Adam(lr, betas=(0.9, 0.999), weight_decay=1e-4)`` on every parameter (``make_optimizer``).
+Each fused optimiser has the update rule and the ``state_dict`` layout of its torch counterpart, so the reference's
+``optimizer_state_dict`` checkpoints interchange.  One kernel launch per parameter tensor, or one per flat bucket when the
+parameters were flattened by ``tools.distributed``.
 """
 import torch
 
 from .. import runtime as rt
 
 
-class FusedAdam(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
-        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False,
-                        foreach=None, capturable=False, differentiable=False, fused=None)
+class _FlatBucketOptimizer(torch.optim.Optimizer):
+    """Flat-bucket bookkeeping shared by the fused optimisers: per bucket one flat tensor per state key (``_state_keys``) plus a
+    host step count, optionally the {lr, step} pair in device memory for graph-captured steps, and the scatter / gather of the
+    flat state through the bucket layout into torch's per-parameter ``state_dict`` layout."""
+    _state_keys = ()
+
+    def __init__(self, params, defaults):
         super().__init__(params, defaults)
         self.grad_scale = 1.0            # e.g. 1/world_size when gradients were sum-all-reduced
         self._flat = None                # optional [(param_flat, grad_flat)] installed by tools.distributed
 
     def attach_flat_buckets(self, buckets, layout=None):
         """buckets: list of (flat_param, flat_grad) fp32 GPU tensors covering all parameters in order.
-        layout: per bucket, the list of (parameter, offset, numel) it holds — needed to save / restore the moments in
-        ``torch.optim.Adam``'s per-parameter ``state_dict`` layout (``GradientBuckets.layout()``)."""
+        layout: per bucket, the list of (parameter, offset, numel) it holds — needed to save / restore the state in torch's
+        per-parameter ``state_dict`` layout (``GradientBuckets.layout()``)."""
         self._flat = buckets
         self._layout = layout
-        self._flat_state = [dict(step=0, exp_avg=torch.zeros_like(p), exp_avg_sq=torch.zeros_like(p)) for p, _ in buckets]
+        # per bucket: {step, <state key>: flat tensor}; step = steps taken (FusedAdam), see _host_step for FusedSGD
+        self._flat_state = [dict(step=0, **{k: torch.zeros_like(p) for k in self._state_keys}) for p, _ in buckets]
         self._dev_state = None           # {lr, step} on the device: set by use_device_state() for graph-captured steps
 
     def use_device_state(self):
         """Keep the learning rate and the step count in device memory (needed when step() is captured in a hipGraph:
-        launch arguments are frozen at capture, the bias corrections and LR schedule must keep moving)."""
+        launch arguments are frozen at capture, the step count and LR schedule must keep moving)."""
         dev = self._flat[0][0].device
         self._dev_state = torch.tensor([self.param_groups[0]["lr"], float(self._flat_state[0]["step"])], dtype=torch.float32,
                                        device=dev)
         self._dev_lr = self.param_groups[0]["lr"]
 
-    # -- checkpoint interchange with torch.optim.Adam (reference tools/base.py:76-81,113) ------------------------
+    # -- checkpoint interchange with torch.optim (reference tools/base.py:76-81,113) -----------------------------
     def _host_step(self, i):
+        """Bucket i's step count.  0 means no state yet (nothing saved).  FusedAdam's is the true count, restored from the
+        checkpoint's ``step``.  torch.optim.SGD saves no count, so FusedSGD restarts at 1 after ``load_state_dict`` and its count
+        only tells whether the next step is the first: not a number of steps taken (for an LR schedule or a log)."""
         if self._dev_state is not None:          # during graph replay only the device copy advances
             self._flat_state[i]["step"] = int(round(float(self._dev_state[1].item())))
         return self._flat_state[i]["step"]
 
+    def _param_entry(self, step, slices):
+        """torch's per-parameter state entry from the bucket's step count and the parameter's slices of the flat state."""
+        return slices
+
+    def _entry_step(self, entry):
+        """The step count a loaded per-parameter entry implies."""
+        raise NotImplementedError
+
     def state_dict(self):
-        """Same layout as ``torch.optim.Adam.state_dict()``: per parameter ``{step, exp_avg, exp_avg_sq}`` — the flat
-        moment buffers are scattered into per-parameter tensors (copies), so a checkpoint written here resumes under
-        ``torch.optim.Adam`` and vice versa."""
+        """torch's per-parameter layout: the flat state buffers are scattered into per-parameter tensors (copies), so a
+        checkpoint written here resumes under the torch optimiser and vice versa."""
         if self._flat is None:
             return super().state_dict()
         if self._layout is None:
@@ -55,12 +70,10 @@ class FusedAdam(torch.optim.Optimizer):
             for i, entries in enumerate(self._layout):
                 step = self._host_step(i)
                 if step == 0:
-                    continue                      # torch.optim.Adam has no state before its first step either
+                    continue                      # torch's optimisers have no state before their first step either
                 st = self._flat_state[i]
                 for p, off, n in entries:
-                    self.state[p] = {"step": torch.tensor(float(step)),
-                                     "exp_avg": st["exp_avg"][off:off + n].clone().view_as(p),
-                                     "exp_avg_sq": st["exp_avg_sq"][off:off + n].clone().view_as(p)}
+                    self.state[p] = self._param_entry(step, {k: st[k][off:off + n].clone().view_as(p) for k in self._state_keys})
             return super().state_dict()
         finally:
             self.state = saved
@@ -74,15 +87,15 @@ class FusedAdam(torch.optim.Optimizer):
         for i, entries in enumerate(self._layout):
             st = self._flat_state[i]
             step = 0
-            st["exp_avg"].zero_()
-            st["exp_avg_sq"].zero_()
+            for k in self._state_keys:
+                st[k].zero_()
             for p, off, n in entries:
                 ps = self.state.get(p)
                 if not ps:
                     continue
-                st["exp_avg"][off:off + n].copy_(ps["exp_avg"].reshape(-1))
-                st["exp_avg_sq"][off:off + n].copy_(ps["exp_avg_sq"].reshape(-1))
-                step = max(step, int(round(float(ps["step"]))))
+                for k in self._state_keys:
+                    st[k][off:off + n].copy_(ps[k].reshape(-1))
+                step = max(step, self._entry_step(ps))
             st["step"] = step
         self.state.clear()                       # the flat buffers are the state from here on
         if self._dev_state is not None:
@@ -94,6 +107,21 @@ class FusedAdam(torch.optim.Optimizer):
         if self._dev_state is not None and self.param_groups[0]["lr"] != self._dev_lr:
             self._dev_lr = self.param_groups[0]["lr"]
             self._dev_state[0] = self._dev_lr
+
+
+class FusedAdam(_FlatBucketOptimizer):
+    _state_keys = ("exp_avg", "exp_avg_sq")
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False,
+                        foreach=None, capturable=False, differentiable=False, fused=None)
+        super().__init__(params, defaults)
+
+    def _param_entry(self, step, slices):
+        return {"step": torch.tensor(float(step)), **slices}      # torch.optim.Adam: {step, exp_avg, exp_avg_sq}
+
+    def _entry_step(self, entry):
+        return int(round(float(entry["step"])))
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -138,3 +166,96 @@ class FusedAdam(torch.optim.Optimizer):
                                               p.numel(), group["lr"], b1, b2, group["eps"], group["weight_decay"],
                                               int(st["step"].item()), self.grad_scale, s))
         return loss
+
+
+class FusedSGD(_FlatBucketOptimizer):
+    """``torch.optim.SGD`` with momentum and coupled L2 weight decay, dampening 0, no Nesterov, not maximising — the
+    reference's ``optim.SGD(lr, momentum=0.9, weight_decay=1e-4)``.  State: one momentum buffer per parameter (flat per
+    bucket), ``{"momentum_buffer": tensor}`` per parameter in ``state_dict()``, nothing before the first step."""
+    _state_keys = ("momentum_buffer",)
+    # param_groups keys later torch versions added; the reference pins torch 1.4 (environment.yml), whose SGD saves only lr,
+    # momentum, dampening, weight_decay and nesterov: filled in on load as torch.optim.SGD.__setstate__ does
+    _LATER_GROUP_KEYS = dict(nesterov=False, maximize=False, foreach=None, differentiable=False, fused=None)
+
+    def __init__(self, params, lr=1e-3, momentum=0.9, dampening=0, weight_decay=0.0, nesterov=False, maximize=False):
+        if lr < 0.0 or weight_decay < 0.0:
+            raise ValueError("FusedSGD: invalid lr %r or weight_decay %r" % (lr, weight_decay))
+        defaults = dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov,
+                        maximize=maximize, foreach=None, differentiable=False, fused=None)
+        super().__init__(params, defaults)           # every group passes _check_group (add_param_group)
+
+    @staticmethod
+    def _check_group(group):
+        if not (group["momentum"] > 0 and group["dampening"] == 0 and not group["nesterov"] and not group["maximize"]):
+            raise ValueError("FusedSGD supports momentum > 0, dampening=0, nesterov=False, maximize=False (the reference's "
+                             "SGD(momentum=0.9, weight_decay=1e-4)); got momentum=%r, dampening=%r, nesterov=%r, maximize=%r"
+                             % (group["momentum"], group["dampening"], group["nesterov"], group["maximize"]))
+
+    def add_param_group(self, param_group):
+        super().add_param_group(param_group)
+        self._check_group(self.param_groups[-1])
+
+    def _entry_step(self, entry):
+        return 1              # torch.optim.SGD keeps no step count: a saved buffer only means "not the first step" (_host_step)
+
+    def load_state_dict(self, state_dict):
+        for entry in state_dict["state"].values():
+            if entry and entry.get("momentum_buffer") is None:
+                keys = sorted(entry)
+                writer = ("Adam (torch.optim.Adam or FusedAdam)" if "exp_avg" in entry else
+                          "SGD without momentum" if "momentum_buffer" in entry else "an optimiser with state keys %s" % keys)
+                raise ValueError("FusedSGD cannot load this optimizer state: it was written by %s (entries hold %s, not "
+                                 "'momentum_buffer'); TRAINING.optimizer must match the checkpoint's optimiser" % (writer, keys))
+        groups = [{**self._LATER_GROUP_KEYS, **group} for group in state_dict["param_groups"]]     # the caller's dict is kept
+        for group in groups:
+            self._check_group(group)
+        super().load_state_dict({**state_dict, "param_groups": groups})
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        L = rt.lib()
+        s = rt.stream()
+        from .. import functional as F_
+        F_.invalidate_packed()             # parameters change below without bumping torch's version counters
+        if self._flat is not None:
+            g0 = self.param_groups[0]
+            if self._dev_state is not None:
+                self._dev_state[1] += 1          # device-side step count (captured as a graph node): step 1 is the first
+                for (p, g), st in zip(self._flat, self._flat_state):
+                    st["step"] += 1              # host mirror (checkpoints); during replay only the device copy advances
+                    rt.check(L.hupr_sgd_step_dev_f32(rt.ptr(p), rt.ptr(g), rt.ptr(st["momentum_buffer"]), p.numel(),
+                                                     rt.ptr(self._dev_state), g0["momentum"], g0["weight_decay"],
+                                                     self.grad_scale, s))
+                return loss
+            for (p, g), st in zip(self._flat, self._flat_state):
+                st["step"] += 1
+                rt.check(L.hupr_sgd_step_f32(rt.ptr(p), rt.ptr(g), rt.ptr(st["momentum_buffer"]), p.numel(), g0["lr"],
+                                             g0["momentum"], g0["weight_decay"], int(st["step"] == 1), self.grad_scale, s))
+            return loss
+        for group in self.param_groups:
+            for p in group["params"]:
+                if p.grad is None:
+                    continue
+                st = self.state[p]
+                first = "momentum_buffer" not in st
+                if first:
+                    st["momentum_buffer"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
+                rt.check(L.hupr_sgd_step_f32(rt.ptr(p), rt.ptr(g), rt.ptr(st["momentum_buffer"]), p.numel(), group["lr"],
+                                             group["momentum"], group["weight_decay"], int(first), self.grad_scale, s))
+        return loss
+
+
+def make_optimizer(cfg, params, lr):
+    """The optimiser ``TRAINING.optimizer`` selects, built as the reference builds it (tools/base.py:44-47).  The reference
+    leaves ``self.optimizer`` unset for any other name and fails later; this raises here."""
+    name = cfg.TRAINING.optimizer
+    if name == "adam":
+        return FusedAdam(params, lr=lr, betas=(0.9, 0.999), weight_decay=1e-4)
+    if name == "sgd":
+        return FusedSGD(params, lr=lr, momentum=0.9, weight_decay=1e-4)
+    raise ValueError("TRAINING.optimizer must be 'sgd' or 'adam' (tools/base.py:44-47), got %r" % (name,))

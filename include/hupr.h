@@ -447,6 +447,14 @@ int hupr_adam_step_f32(float* p, const float* g, float* exp_avg, float* exp_avg_
 /* same, {learning rate, step count} read from device memory (2 floats): for steps replayed from a captured hipGraph */
 int hupr_adam_step_dev_f32(float* p, const float* g, float* exp_avg, float* exp_avg_sq, long n, const float* dev_state,
                            float beta1, float beta2, float eps, float weight_decay, float gscale, hupr_stream_t stream);
+/* (a10) SGD with momentum and coupled L2 weight decay (tools/base.py:44-45; torch.optim.SGD with dampening 0, no Nesterov),
+ * one flat launch.  first != 0 on the parameter's first step: the buffer is set to the decayed gradient (old contents
+ * ignored). */
+int hupr_sgd_step_f32(float* p, const float* g, float* momentum_buf, long n, float lr, float momentum,
+                      float weight_decay, int first, float gscale, hupr_stream_t stream);
+/* same, {learning rate, step count} read from device memory (the 2 floats of hupr_adam_step_dev_f32); step 1 is the first */
+int hupr_sgd_step_dev_f32(float* p, const float* g, float* momentum_buf, long n, const float* dev_state,
+                          float momentum, float weight_decay, float gscale, hupr_stream_t stream);
 
 /* ---- bf16-activation variants ("bf16act") -------------------------------------------------------------
  * Same operators with the ACTIVATION tensors (x, y, dy, dx, residual) stored as bf16 in HBM; parameters,
