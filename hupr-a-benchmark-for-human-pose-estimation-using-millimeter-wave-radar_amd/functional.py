@@ -4,7 +4,7 @@ chain of reference operators is cheaper as one (MSCSALevelFn, TemporalMergeFn, D
 Activations are channels-last 5-D tensors ``(B, D, H, W, C)`` (2-D maps use D == 1), contiguous, fp32 — or, with
 bf16 math and ``ACT_BF16``, bf16-stored inside the encoders / decoder stacks (arithmetic and parameters stay fp32).
 Parameters keep the reference's shapes; the packed layouts the convolution kernels read are cached per parameter and
-refreshed by ONE table-driven launch per optimiser step (``_packed`` / ``invalidate_packed``).  Parameter gradients
+refreshed by ONE table-driven launch per optimiser step (``weight_cache``; ``_packed`` / ``invalidate_packed``).  Parameter gradients
 are written straight into the flat all-reduce buckets when a gradient sink is installed (``GRAD_SINK``).
 
 Nothing here computes with torch ops except allocation, views, concatenation of small weight matrices and gradient
@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from . import runtime as rt
+from . import weight_cache as wcache
 
 _ws_cache = {}
 CONV_PROBE = None      # bench.py installs a callable(x, co, k) -> (start_event, end_event) | None
@@ -196,28 +197,11 @@ def two_streams_ok(t):
     return TWO_STREAMS and t.is_cuda
 
 
-def refresh_packed(device, params=None):
-    """Run the packed-weight table refresh now (on the current stream) if any cached entry is stale — called before
-    the branches fork so that the refresh is ordered in front of both.
-    params: the parameters of the model about to run, passed when that model sat idle for two or more optimiser epochs of ANOTHER
-    model (its entries then dropped out of the table pass's candidates): their stale entries are taken along here, in front of the
-    fork — otherwise the first stale read inside the fork would refresh them lazily on whichever stream got there first, and the
-    sibling stream would read packed buffers with no dependency on that launch."""
-    if params is not None:
-        cur = _pack_recent[0]
-        for p in params:
-            ptr = p.data_ptr()
-            for kind in (0, 1, 2, 3):
-                e = _pack_entries.get((ptr, kind))
-                if e is not None and e.wref() is p and e.stamp != (PACK_EPOCH, p._version):
-                    cur.setdefault(id(e), e)
-    for e in _pack_candidates():
-        w = e.wref()
-        if w is not None and w.device == device and e.stamp != (PACK_EPOCH, w._version):
-            _pack_refresh_all(device)
-            break
-    if not torch.cuda.is_current_stream_capturing():
-        _wc_refresh(device)
+# The derived copies of the parameters that the kernels read (packed layouts, concatenated projections, the padded head filter) live
+# in ``weight_cache``: ``invalidate_packed()`` after changing parameters behind torch's version counter, ``refresh_packed(device)``
+# to refill the stale ones in place — in front of a two-stream fork, or before replaying a captured inference graph.
+invalidate_packed = wcache.invalidate
+refresh_packed = wcache.refresh
 
 
 # Direct gradient sink (installed by tools.distributed.GradientBuckets): parameter gradients are written by the kernels
@@ -267,209 +251,50 @@ def pack_weights_bf16(w, mode):
     return wp
 
 
-# ---- packed-weight cache -------------------------------------------------------------------------------------
-# Parameters (leaf tensors that require grad) keep both packed layouts cached; the cache is stamped with PACK_EPOCH
-# (bumped by optimisers that update weights through the C ABI, i.e. behind torch's version counter) and the tensor's
-# own ``_version``.  The first stale hit of a step refreshes EVERY registered weight with one table-driven launch
-# (hupr_pack_conv_weights_table) instead of ~160 small pack launches per training step.
-import weakref
-
-PACK_EPOCH = 0
-PACK_CACHE = True          # debugging aid: False = repack on every call
-_pack_entries = {}      # (storage address, kind) -> entry
-_pack_table = None      # (device uint8 tensor, n, total) or None when dirty
-# The table pass refreshes the entries that were READ during the current or the previous epoch (= optimiser step), not every weight
-# the process ever registered: a process that holds several models (the GPU test suite: a dozen live networks by the time the pose
-# fits run; an application with a training and an evaluation copy) repacked all of them after every optimiser step of one — 20 ->
-# 34 ms per fit step inside the suite, most of it this module's Python loops over thousands of entries (round 5).  An entry that
-# drops out is refreshed when it is read again (the stale path of ``_packed`` / ``_proj_cat`` / ``_head_w16_cached`` touches it first).
-_pack_recent = [{}, {}]      # id(entry) -> entry: read during the current / the previous epoch
-_pack_pinned = {}            # entries a captured inference graph reads (it baked their addresses in): refreshed after every update
-_pack_sweeps = 0
+def _alloc_packed(ws, kinds):
+    pk = pack_weights_bf16 if kinds[0] == wcache.PACK_BF16 else pack_weights
+    wp = (pk(ws[0], 0), pk(ws[0], 1))
+    return wp, (wp,), True
 
 
-def invalidate_packed():
-    """Call after changing parameters behind torch's back (FusedAdam does)."""
-    global PACK_EPOCH
-    PACK_EPOCH += 1
-    _pack_recent[1] = _pack_recent[0]
-    _pack_recent[0] = {}
-
-
-class _PackEntry:
-    __slots__ = ("wref", "ptr", "kind", "shape", "wp", "stamp", "group")      # group: the epoch the entry was created in (~ its model)
-
-
-def _touch(e):
-    """Mark ``e`` as read in this epoch -> was it among the table pass's candidates already?  (False: a weight that dropped out —
-    its model sat idle for two optimiser steps of another one —: the caller's refresh then sweeps the stale entries of that
-    model, i.e. those created in the same epoch, in its one launch, so that the rest of the model does not come back one table
-    launch per weight; sweeping EVERY stale entry of the process made the GPU suite 150 s slower again.)"""
-    k = id(e)
-    known = k in _pack_recent[0] or k in _pack_recent[1] or k in _pack_pinned
-    _pack_recent[0][k] = e
-    if torch.cuda.is_current_stream_capturing():
-        _pack_pinned[k] = e
-    return known
-
-
-def _pack_candidates():
-    cur, prev = _pack_recent
-    return (list(cur.values()) + [e for k, e in prev.items() if k not in cur] +
-            [e for k, e in _pack_pinned.items() if k not in cur and k not in prev])
-
-
-def _pack_refresh_all(dev, full=None):
-    global _pack_table, _pack_sweeps
-    L = rt.lib()
-    _pack_sweeps += 1
-    if full is not None:                             # a dropped-out entry came back: take the stale entries of ITS model along — those
-        for e in list(_pack_entries.values()):       # created in the same epoch (a model's first forward registers all its weights)
-            w = e.wref()
-            if (getattr(e, "group", None) == full and w is not None and w.device == dev and w.data_ptr() == e.ptr
-                    and e.stamp != (PACK_EPOCH, w._version)):
-                _pack_recent[0].setdefault(id(e), e)
-    if _pack_sweeps % 256 == 0:                      # now and then: drop the entries (and packed copies) of weights that are gone
-        for key in [k for k, e in _pack_entries.items() if e.wref() is None]:
-            del _pack_entries[key]
-    live = []
-    for e in _pack_candidates():
-        w = e.wref()
-        if w is None or w.data_ptr() != e.ptr or w.device != dev:
-            if w is None:
-                _pack_entries.pop((e.ptr, e.kind), None) if _pack_entries.get((e.ptr, e.kind)) is e else None
-                _pack_recent[0].pop(id(e), None)
-                _pack_recent[1].pop(id(e), None)
-                _pack_pinned.pop(id(e), None)
-            continue
-        live.append((e, w))
-    if not live:
-        return
-    if _pack_table is None or _pack_table[3] != tuple(id(e) for e, _ in live):
-        rec = np.zeros(len(live), dtype=np.dtype([("w", "<u8"), ("wp0", "<u8"), ("wp1", "<u8"), ("first", "<i8"), ("co", "<i4"),
-                                                   ("ci", "<i4"), ("taps", "<i4"), ("kind", "<i4")]))
-        first = 0
-        blocks = []
-        for i, (e, w) in enumerate(live):
-            co, ci = w.shape[0], w.shape[1]
-            taps = int(np.prod(w.shape[2:]))
-            rec[i] = (w.data_ptr(), e.wp[0].data_ptr(), e.wp[1].data_ptr(), first, co, ci, taps, e.kind)
-            cnt = co * ci * taps
-            first += cnt
-            if e.kind >= 2:
-                # a projection weight -> its row block of the level's concatenated matrices (plain, query-scaled): block layout 3
-                blocks.extend((i, 3, st) for st in range(0, cnt, 2048))
-            elif e.kind == 1 and co % 32 == 0 and ci % 32 == 0 and taps <= 27:
-                # 32 x 32 x taps tiles, both layouts per tile through LDS (hupr_k_pack_table, block layout 2)
-                blocks.extend((i, 2, (c0 << 32) | i0) for c0 in range(0, co, 32) for i0 in range(0, ci, 32))
-            else:
-                for layout in (0, 1):
-                    blocks.extend((i, layout, st) for st in range(0, cnt, 2048))
-        blk = np.zeros(len(blocks), dtype=np.dtype([("entry", "<i4"), ("layout", "<i4"), ("start", "<i8")]))
-        blk["entry"], blk["layout"], blk["start"] = zip(*blocks)
-        tab = torch.from_numpy(rec.view(np.uint8).copy()).to(dev)
-        btab = torch.from_numpy(blk.view(np.uint8).copy()).to(dev)
-        _pack_table = (tab, btab, len(blocks), tuple(id(e) for e, _ in live))
-    tab, btab, n_blocks, _ = _pack_table
-    rt.check(L.hupr_pack_conv_weights_table(rt.ptr(tab), rt.ptr(btab), n_blocks, rt.stream()))
-    for e, w in live:
-        e.stamp = (PACK_EPOCH, w._version)
+_PACKED_KINDS = ((wcache.PACK_F32,), (wcache.PACK_BF16,))
 
 
 def _packed(weight, mode, kind):
-    """Packed layout ``mode`` (0 forward, 1 input gradient) of ``weight`` as fp32 (kind 0) or bf16 (kind 1).
-    During a hipGraph capture: a TRAINING graph (grad enabled) repacks inside the graph — its own optimiser node changes the
-    weights between replays; an INFERENCE graph (no_grad) reads the cached layouts when they are fresh — ~60 pack launches less
-    per replay — and those buffers are refreshed IN PLACE by the next eager refresh (``refresh_packed`` after a weight update
-    keeps a captured inference graph current, together with the in-place ``_wc_cache`` below)."""
-    global _pack_table
-    capturing = torch.cuda.is_current_stream_capturing()
-    if not (PACK_CACHE and weight.is_leaf and weight.requires_grad and weight.is_contiguous()) or \
-            (capturing and torch.is_grad_enabled()):
+    """Packed layout ``mode`` (0 forward, 1 input gradient) of ``weight`` as fp32 (kind 0) or bf16 (kind 1): the cached pair of a
+    parameter (``weight_cache``; an inference graph reads it too, ~60 pack launches less per replay), a single pack otherwise."""
+    wp = wcache.lookup((weight,), _PACKED_KINDS[kind], _alloc_packed)
+    if wp is None:
         return pack_weights_bf16(weight, mode) if kind else pack_weights(weight, mode)
-    key = (weight.data_ptr(), kind)
-    e = _pack_entries.get(key)
-    if e is not None and (e.wref() is None or e.shape != tuple(weight.shape)):     # the address was recycled by another tensor
-        e = None
-    if capturing:
-        if e is None or e.stamp != (PACK_EPOCH, weight._version):                  # nothing cached is created or refreshed mid-capture
-            return pack_weights_bf16(weight, mode) if kind else pack_weights(weight, mode)
-        _touch(e)
-        return e.wp[mode]
-    if e is None:
-        e = _PackEntry()
-        e.wref, e.ptr, e.kind, e.shape = weakref.ref(weight), weight.data_ptr(), kind, tuple(weight.shape)
-        pk = pack_weights_bf16 if kind else pack_weights
-        e.wp = (pk(weight, 0), pk(weight, 1))
-        e.stamp = (PACK_EPOCH, weight._version)
-        e.group = PACK_EPOCH
-        _pack_entries[key] = e
-        _pack_table = None
-        _touch(e)
-    elif e.stamp != (PACK_EPOCH, weight._version):
-        _pack_refresh_all(weight.device, full=None if _touch(e) else getattr(e, "group", None))
-        if e.stamp != (PACK_EPOCH, weight._version):          # not covered by the table pass (should not happen)
-            pk = pack_weights_bf16 if kind else pack_weights
-            pk_into = (pk(weight, 0), pk(weight, 1))
-            e.wp[0].copy_(pk_into[0])                           # in place: captured inference graphs hold these addresses
-            e.wp[1].copy_(pk_into[1])
-            e.stamp = (PACK_EPOCH, weight._version)
-    else:
-        _touch(e)
-    return e.wp[mode]
+    return wp[mode]
 
 
 # The eight 1x1 projection weights of an MSCSA level as the two (4C, C) matrices its two GEMMs read — [phi_cross | theta_cross |
-# phi_self | theta_self] per map — kept as ENTRIES OF THE PACK TABLE (kinds 2 / 3): the one table-driven launch after an optimiser
-# step refreshes them with everything else, where rounds 1-4 concatenated them with two ATen launches per level and step.  Two
-# copies per map: the plain one (backward GEMMs, GEMM-attention fallback) and the one whose query (theta) rows carry
-# log2(e) for the QS attention kernels (csrc/attention_bf16.hip, kDeferBits).
-_proj_cache = {}       # (addresses of the four weights) -> (Wc plain, Wc query-scaled, entries)
+# phi_self | theta_self] per map — kept as ENTRIES OF THE PACK TABLE: the one table-driven launch after an optimiser step refreshes
+# them with everything else, where rounds 1-4 concatenated them with two ATen launches per level and step.  Two copies per map: the
+# plain one (backward GEMMs, GEMM-attention fallback) and the one whose query (theta) rows carry log2(e) for the QS attention
+# kernels (csrc/attention_bf16.hip, kDeferBits).
+_PROJ_KINDS = (wcache.COPY, wcache.COPY_LOG2E, wcache.COPY, wcache.COPY_LOG2E)
 QS_ATTN = True             # test aid: False = the plain-Q kernels (fma per score)
+
+
+def _alloc_proj(ws, kinds):
+    C = ws[0].shape[0]
+    wc = torch.empty((4 * C, C), dtype=torch.float32, device=ws[0].device)
+    wq = torch.empty_like(wc)
+    return (wc, wq), [(wc[j * C:(j + 1) * C], wq[j * C:(j + 1) * C]) for j in range(4)], False
 
 
 def _proj_cat(ws, C):
     """-> (Wc, Wc_qs): (4C, C) fp32 concatenations of the four (C, C, 1, 1) projection weights ``ws`` of one map."""
-    capturing = torch.cuda.is_current_stream_capturing()
-    ok = PACK_CACHE and all(w.is_leaf and w.requires_grad and w.is_contiguous() for w in ws)
-    key = tuple(w.data_ptr() for w in ws)
-    ent = _proj_cache.get(key) if ok else None
-    if ent is not None and any(e.wref() is not w for e, w in zip(ent[2], ws)):          # addresses recycled by other tensors
-        ent = None
-    fresh = ent is not None and all(e.stamp == (PACK_EPOCH, w._version) for e, w in zip(ent[2], ws))
-    if not ok or (capturing and (torch.is_grad_enabled() or not fresh)):
-        # not cacheable, or inside a capture that must not create / refresh cache entries (a training graph's own optimiser node
-        # changes the weights between replays): computed in place, in the graph
+    cat = wcache.lookup(ws, _PROJ_KINDS, _alloc_proj)
+    if cat is None:
         wc = torch.cat([w.detach().reshape(C, C) for w in ws], 0)
         wq = wc.clone()
         wq[C:2 * C] *= 1.4426950408889634
         wq[3 * C:] *= 1.4426950408889634
         return wc, wq
-    if ent is None:
-        global _pack_table
-        for k in [k for k, v in _proj_cache.items() if any(e.wref() is None for e in v[2])]:
-            del _proj_cache[k]
-        wc = torch.empty((4 * C, C), dtype=torch.float32, device=ws[0].device)
-        wq = torch.empty_like(wc)
-        entries = []
-        for j, w in enumerate(ws):
-            e = _PackEntry()
-            e.wref, e.ptr, e.kind, e.shape = weakref.ref(w), w.data_ptr(), 3 if j in (1, 3) else 2, tuple(w.shape)
-            e.wp = (wc[j * C:(j + 1) * C], wq[j * C:(j + 1) * C])
-            e.stamp = None
-            e.group = PACK_EPOCH
-            _pack_entries[(w.data_ptr(), e.kind)] = e
-            entries.append(e)
-        ent = _proj_cache[key] = (wc, wq, entries)
-        _pack_table = None
-        fresh = False
-        created = True
-    else:
-        created = False
-    known = all([_touch(e) for e in ent[2]])
-    if not fresh:
-        _pack_refresh_all(ws[0].device, full=None if (known or created) else ent[2][0].group)
-    return ent[0], ent[1]
+    return cat
 
 
 USE_FLASH = True       # bf16 mode: fused attention kernels where supported (C in {64,128}, N % 128 == 0)
@@ -1369,87 +1194,7 @@ def level_cat_placement_ok(ra):
     return CAT_INPLACE and mscsa_level_fused_ok(ra) and USE_FLASH and CAT_FUSION and bool(rt.lib().hupr_attn_flash_supported(H * W, C))
 
 
-# Derived inference constants (concatenated projection weights, the zero-padded head filter): one entry per set of source
-# parameters, keyed by their addresses, stamped like the packed layouts and REFRESHED IN PLACE when stale — a captured
-# inference graph that baked in an entry's address keeps reading current values once ``refresh_packed`` has run after a weight
-# update (the first version keyed entries by epoch, so an update orphaned the tensor a graph was still reading,
-# and ``clear()`` at 64 entries could free it).  Entries die with their parameters (weak references), never by count.
-_wc_cache = {}
 ATTN_BATCH = True          # test aid: False = one launch pair per attention in single-sample inference
-
-
-class _WcEntry:
-    __slots__ = ("wrefs", "stamp", "build", "t")
-
-
-def _wc_stamp(ws):
-    return (PACK_EPOCH,) + tuple(w._version for w in ws)
-
-
-def _wc_get(tag, ws, build):
-    """-> the cached constant ``build(ws, out)`` derives from the parameters ``ws``.  ``build(ws, None)`` returns a fresh tensor,
-    ``build(ws, t)`` refills ``t`` in place.  Nothing is created or refreshed during a capture (a fresh entry would live in the
-    graph's private pool; a stale one means the caller skipped ``refresh_packed``): the capture then computes its own copy
-    inside the graph, which is always current."""
-    key = (tag,) + tuple(w.data_ptr() for w in ws)
-    e = _wc_cache.get(key)
-    if e is not None and any(r() is not w for r, w in zip(e.wrefs, ws)):            # an address recycled by another tensor
-        e = None
-    capturing = torch.cuda.is_current_stream_capturing()
-    if capturing:
-        return e.t if e is not None and e.stamp == _wc_stamp(ws) else build(ws, None)
-    if e is None:
-        for k in [k for k, v in _wc_cache.items() if any(r() is None for r in v.wrefs)]:
-            del _wc_cache[k]
-        e = _WcEntry()
-        e.wrefs, e.build, e.t = tuple(weakref.ref(w) for w in ws), build, build(ws, None)
-        e.stamp = _wc_stamp(ws)
-        _wc_cache[key] = e
-    elif e.stamp != _wc_stamp(ws):
-        build(ws, e.t)
-        e.stamp = _wc_stamp(ws)
-    return e.t
-
-
-def _wc_refresh(device):
-    """Refill every stale derived constant on ``device`` in place (part of ``refresh_packed``)."""
-    for k in list(_wc_cache):
-        e = _wc_cache[k]
-        ws = [r() for r in e.wrefs]
-        if any(w is None for w in ws):
-            del _wc_cache[k]
-        elif ws[0].device == device and e.stamp != _wc_stamp(ws):
-            e.build(ws, e.t)
-            e.stamp = _wc_stamp(ws)
-
-
-def _cat_build(ws, out):
-    C = ws[0].shape[0]
-    parts = [w.detach().reshape(C, C) for w in ws]
-    return torch.cat(parts, 0, out=out) if out is not None else torch.cat(parts, 0)
-
-
-def _cat_weights(ws, C, cache):
-    """The four (C, C, 1, 1) projection weights of a map as one (4C, C) matrix.  Inference (``cache``): kept across calls
-    (``_wc_get``) — six concatenation launches less per forward (37 us of config C2's 1.28 ms)."""
-    if not cache:
-        return torch.cat([w.reshape(C, C) for w in ws], 0)
-    return _wc_get("cat", tuple(ws), _cat_build)
-
-
-def head_weight16(weight, num_keypoints):
-    """The 1x1 head's filters zero-padded to 16 output channels (later kernels stay float4-aligned).  Under no_grad the padded copy is
-    kept across calls like the concatenated projection weights (one pad launch less per inference forward)."""
-    def build(ws, out):
-        w = ws[0].detach()
-        if out is None:
-            return torch.nn.functional.pad(w, (0, 0, 0, 0, 0, 0, 0, 16 - w.shape[0]))
-        out[:w.shape[0]].copy_(w)
-        return out
-    if torch.is_grad_enabled():                                 # training: an ordinary differentiable pad
-        return torch.nn.functional.pad(weight, (0, 0, 0, 0, 0, 0, 0, 16 - num_keypoints))
-    assert weight.shape[0] == num_keypoints
-    return _wc_get("head16", (weight,), build)
 
 
 @_math_scoped
@@ -1771,43 +1516,32 @@ class GCNLayerFn(torch.autograd.Function):
         return dx, dw, _pret(bias, dbias, db_direct), None, None
 
 
-_head_cache = {}       # address of the head weight -> (zero-padded (16, 32, 1, 1) copy, pack-table entry)
+def _alloc_head(ws, kinds):
+    buf = torch.zeros((16,) + tuple(ws[0].shape[1:]), dtype=torch.float32, device=ws[0].device)
+    rows = buf[:ws[0].shape[0]]
+    return buf, ((rows, rows),), False
+
+
+_HEAD_KINDS = (wcache.COPY,)
 
 
 def _head_w16_cached(weight):
-    """The 14 head filters zero-padded to 16 as a PACK-TABLE entry (kind 2: a plain copy into rows 0..K-1 of a persistent buffer whose
-    other rows stay zero), refreshed by the one table launch after an optimiser step — rounds 1-4 padded with ATen in every
-    training forward (a fill, a copy, and a slice + accumulate in the backward)."""
-    K = weight.shape[0]
-    capturing = torch.cuda.is_current_stream_capturing()
-    ok = PACK_CACHE and weight.is_leaf and weight.requires_grad and weight.is_contiguous() and tuple(weight.shape[1:]) == (32, 1, 1)
-    ent = _head_cache.get(weight.data_ptr()) if ok else None
-    if ent is not None and ent[1].wref() is not weight:
-        ent = None
-    fresh = ent is not None and ent[1].stamp == (PACK_EPOCH, weight._version)
-    if not ok or (capturing and (torch.is_grad_enabled() or not fresh)):
-        return torch.nn.functional.pad(weight.detach(), (0, 0, 0, 0, 0, 0, 0, 16 - K))
-    if ent is None:
-        global _pack_table
-        for k in [k for k, v in _head_cache.items() if v[1].wref() is None]:
-            del _head_cache[k]
-        buf = torch.zeros((16,) + tuple(weight.shape[1:]), dtype=torch.float32, device=weight.device)
-        e = _PackEntry()
-        e.wref, e.ptr, e.kind, e.shape = weakref.ref(weight), weight.data_ptr(), 2, tuple(weight.shape)
-        e.wp = (buf[:K], buf[:K])
-        e.stamp = None
-        e.group = PACK_EPOCH
-        _pack_entries[(weight.data_ptr(), 2)] = e
-        ent = _head_cache[weight.data_ptr()] = (buf, e)
-        _pack_table = None
-        fresh = False
-        created = True
-    else:
-        created = False
-    known = _touch(ent[1])
-    if not fresh:
-        _pack_refresh_all(weight.device, full=None if (known or created) else ent[1].group)
-    return ent[0]
+    """The 14 head filters zero-padded to 16 as a PACK-TABLE entry (a plain copy into rows 0..K-1 of a persistent buffer whose other
+    rows stay zero), refreshed by the one table launch after an optimiser step — rounds 1-4 padded with ATen in every training
+    forward (a fill, a copy, and a slice + accumulate in the backward)."""
+    w16 = wcache.lookup((weight,), _HEAD_KINDS, _alloc_head) if tuple(weight.shape[1:]) == (32, 1, 1) else None
+    if w16 is None:
+        return torch.nn.functional.pad(weight.detach(), (0, 0, 0, 0, 0, 0, 0, 16 - weight.shape[0]))
+    return w16
+
+
+def head_weight16(weight, num_keypoints):
+    """The 1x1 head's filters zero-padded to 16 output channels (later kernels stay float4-aligned).  Under no_grad the padded copy
+    is the pack-table entry of ``_head_w16_cached`` (one pad launch less per inference forward)."""
+    if torch.is_grad_enabled():                                 # training: an ordinary differentiable pad
+        return torch.nn.functional.pad(weight, (0, 0, 0, 0, 0, 0, 0, 16 - num_keypoints))
+    assert weight.shape[0] == num_keypoints
+    return _head_w16_cached(weight)
 
 
 @_math_scoped

@@ -421,7 +421,7 @@ def test_inference_constants_follow_weight_updates_eager_and_captured():
     the zero-padded head filter — must follow parameter updates made behind torch's version counters (FusedAdam, a replayed
     training graph), in eager calls AND in an inference hipGraph captured earlier: its nodes read the cached buffers (no pack
     launches inside the graph), and ``functional.refresh_packed`` refills exactly those buffers in place."""
-    from hupr_amd import functional as F_
+    from hupr_amd import functional as F_, weight_cache
     from hupr_amd.models import HuPRNet
     try:
         cfg, net = _net("bf16")
@@ -429,11 +429,13 @@ def test_inference_constants_follow_weight_updates_eager_and_captured():
         h, v = (torch.from_numpy(t).cuda() for t in synth.model_inputs(1, 17))
         with torch.no_grad():
             a0 = tuple(t.clone() for t in net(h, v))                 # fills every cache
-            n_const = lambda: len(F_._wc_cache) + len(F_._proj_cache) + len(F_._head_cache)
+            n_const = lambda: len(weight_cache.entries)              # the one registry: packed layouts, projections, head filter
             n_wc = n_const()
-            # 6 concatenations of projection weights (two maps x three levels) + the zero-padded head filter: pack-table entries since
-            # round 5 (functional._proj_cat / _head_w16_cached), refreshed in place by the same table launch as the packed layouts
-            assert len(F_._proj_cache) >= 6 and len(F_._head_cache) >= 1
+            # 6 concatenations of projection weights (two maps x three levels: sets of four entries) + the zero-padded head filter (a
+            # set of one plain-copy entry): pack-table entries since round 5 (functional._proj_cat / _head_w16_cached), refreshed in
+            # place by the same table launch as the packed layouts
+            sets = {id(e.members): e.members for e in weight_cache.entries.values() if e.kind >= weight_cache.COPY}.values()
+            assert sum(len(m) == 4 for m in sets) >= 6 and sum(len(m) == 1 for m in sets) >= 1
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):

@@ -249,12 +249,12 @@ def test_idle_model_repacks_in_front_of_the_two_stream_fork():
     candidates; its next forward must refresh its stale layouts BEFORE the encoder branches fork onto two streams (a lazy refresh
     inside the fork runs on whichever stream gets there first, unordered against the sibling's reads).  Every table launch of that
     forward happens on the main stream, and the outputs are those of a fresh model holding the same weights."""
-    from hupr_amd import functional as F_
+    from hupr_amd import functional as F_, weight_cache
     g = np.load(os.path.join(G, "model_eval.npz"))
     h, v = _inputs(g)
     saved = F_.TWO_STREAMS
     calls = []
-    orig = F_._pack_refresh_all
+    orig = weight_cache._refresh_all
     try:
         F_.set_math("bf16")
         F_.TWO_STREAMS = True
@@ -270,12 +270,12 @@ def test_idle_model_repacks_in_front_of_the_two_stream_fork():
             a.load_state_dict(sd)                    # the idle model's weights change (e.g. copied from a training model)
             main = torch.cuda.current_stream().cuda_stream
 
-            def logged(dev, full=None):
+            def logged(dev, group=None):
                 calls.append(torch.cuda.current_stream().cuda_stream)
-                return orig(dev, full=full)
-            F_._pack_refresh_all = logged
+                return orig(dev, group=group)
+            weight_cache._refresh_all = logged
             p1, p2 = a(h, v)
-            F_._pack_refresh_all = orig
+            weight_cache._refresh_all = orig
             torch.cuda.synchronize()
             assert calls and all(c == main for c in calls), (calls, main)
             _, fresh = _build(g)
@@ -285,7 +285,7 @@ def test_idle_model_repacks_in_front_of_the_two_stream_fork():
             torch.cuda.synchronize()
         assert torch.equal(p1, q1) and torch.equal(p2, q2)
     finally:
-        F_._pack_refresh_all = orig
+        weight_cache._refresh_all = orig
         F_.TWO_STREAMS = saved
         F_.set_math("f32")
         F_.invalidate_packed()

@@ -1058,7 +1058,7 @@ def test_pack_table_covers_recent_readers_and_brings_idle_models_back_in_one_lau
     """The table pass after an optimiser step refreshes the weights READ during the current or previous step — not every weight the
     process holds (a second, idle model used to be repacked after every step of the first) — and a model that sat idle comes back with
     ONE table launch at its first read, not one per weight; contents always equal the one-weight pack kernels."""
-    from hupr_amd import functional as F_
+    from hupr_amd import functional as F_, weight_cache
     L = F_.rt.lib()
     mk = lambda seed: [torch.nn.Parameter(rnd(64, 64, 3, 3, 3, seed=seed + i).cuda()) for i in range(6)]
     wa, wb = mk(700), mk(720)
@@ -1076,7 +1076,7 @@ def test_pack_table_covers_recent_readers_and_brings_idle_models_back_in_one_lau
         n = L.hupr_launch_count() - n0 - len(wa)              # (minus the reference packs)
         assert n == 1, n                                      # one table launch per step
         if step >= 2:                                         # B dropped out of the table: not repacked, its entries stale
-            assert all(F_._pack_entries[(w.data_ptr(), 1)].stamp[0] != F_.PACK_EPOCH for w in wb)
+            assert all(weight_cache.entries[(w.data_ptr(), weight_cache.PACK_BF16)].stamp[0] != weight_cache.epoch for w in wb)
     n0 = L.hupr_launch_count()
     got = [F_._packed(w, 1, 1) for w in wb]                   # B comes back
     assert L.hupr_launch_count() - n0 == 1
@@ -1645,6 +1645,16 @@ def test_head1x1_fp32_kernels(B, H):
     with torch.no_grad():
         w.mul_(2.0)
     assert torch.equal(F_._head_w16_cached(w)[:14], w.detach())
+    # the no-grad route of the generic head (functional.head_weight16) serves the same table entry: one padded buffer per head
+    # weight, and it follows an update made behind torch's version counter after invalidate + refresh
+    with torch.no_grad():
+        assert F_.head_weight16(w, 14).data_ptr() == F_._head_w16_cached(w).data_ptr() == w16.data_ptr()
+        w.data.mul_(0.5).add_(0.125)                                         # (.data: torch's version counter does not move)
+        F_.invalidate_packed()
+        F_.refresh_packed(w.device)
+        assert torch.equal(w16[:14], w.detach()) and w16[14:].abs().max().item() == 0.0      # refilled in place by the refresh
+        assert F_.head_weight16(w, 14).data_ptr() == F_._head_w16_cached(w).data_ptr() == w16.data_ptr()
+    assert F_.head_weight16(w, 14).data_ptr() != w16.data_ptr()              # grad enabled: the differentiable pad
     with torch.no_grad():
         w.copy_(w0)
     F_._head_w16_cached(w)
