@@ -66,31 +66,55 @@ class HuPRNet(nn.Module):
         self._pack_epoch_seen = now
 
     def _forward(self, VRDAEmaps_hori, VRDAEmaps_vert):
+        return self._branches_and_heads(VRDAEmaps_hori, VRDAEmaps_vert, chirp=True)
+
+    def _branches_and_heads(self, hori, vert, chirp):
+        """The two branches (chirp net when ``chirp``, 3-D encoder) on two streams where possible, then decoder and heads.
+        hori / vert: the network inputs, or — ``chirp=False`` — the two MNet feature windows."""
         F_._conv_stats.clear()                  # no fused-statistics hand-over survives a forward pass
-        if F_.two_streams_ok(VRDAEmaps_hori):
+        if F_.two_streams_ok(hori):
             # vertical branch on the side stream, horizontal branch on the current one (see functional.TWO_STREAMS)
-            dev = VRDAEmaps_hori.device
+            dev = hori.device
             capturing = torch.cuda.is_current_stream_capturing()     # graph capture: fork / join become graph edges; the
             if not capturing:                                       # private pool is not recycled, no record_stream needed
                 self._refresh_packed(dev)                           # (and the packed-weight cache is bypassed anyway)
             main, side = torch.cuda.current_stream(dev), F_.side_stream(dev)
             side.wait_stream(main)
             if not capturing:
-                VRDAEmaps_vert.record_stream(side)
+                vert.record_stream(side)
             with torch.cuda.stream(side):
-                REl1feat, REl2feat, REfeat = self.REradarEncoder(self.REchirpNet(VRDAEmaps_vert))
-            RAl1feat, RAl2feat, RAfeat = self.RAradarEncoder(self.RAchirpNet(VRDAEmaps_hori))
+                REl1feat, REl2feat, REfeat = self.REradarEncoder(self.REchirpNet(vert) if chirp else vert)
+            RAl1feat, RAl2feat, RAfeat = self.RAradarEncoder(self.RAchirpNet(hori) if chirp else hori)
             main.wait_stream(side)
             if not capturing:
                 for t in (REl1feat, REl2feat, REfeat):
                     t.record_stream(main)             # allocated on the side stream, consumed by the decoder
         else:
-            if VRDAEmaps_hori.is_cuda and not torch.cuda.is_current_stream_capturing():
-                self._refresh_packed(VRDAEmaps_hori.device)         # stale cached layouts / derived constants are refilled in place
-            RAmaps, REmaps = self.forward_chirp(VRDAEmaps_hori, VRDAEmaps_vert)
+            if hori.is_cuda and not torch.cuda.is_current_stream_capturing():
+                self._refresh_packed(hori.device)                   # stale cached layouts / derived constants are refilled in place
+            RAmaps, REmaps = self.forward_chirp(hori, vert) if chirp else (hori, vert)
             RAl1feat, RAl2feat, RAfeat = self.RAradarEncoder(RAmaps)
             REl1feat, REl2feat, REfeat = self.REradarEncoder(REmaps)
         maps16, gcn_heatmap = self.radarDecoder(RAl1feat, RAl2feat, RAfeat, REl1feat, REl2feat, REfeat)
         B, _, H, W, ld = maps16.shape
         heatmap = F_.SigmoidHeadFn.apply(maps16.reshape(B, H * W, ld), self.numKeypoints)
         return heatmap.reshape(B, self.numKeypoints, 1, H, W), gcn_heatmap
+
+    def forward_chirp_maps(self, RAmaps, REmaps):
+        """Encoders, decoder and heads from the two MNet feature windows (B, G, R, A, numFilters) channels-last — what ``forward_chirp``
+        returns, produced elsewhere (the live stream keeps a ring of mean planes and runs the MNet over its window itself:
+        tools.stream).  Same outputs as ``forward``; same two-stream fork, packed-weight refresh and ``math_mode`` pinning."""
+        if self.math_mode is not None:
+            with F_.math_mode(self.math_mode):
+                return self._forward_maps(RAmaps, REmaps)
+        return self._forward_maps(RAmaps, REmaps)
+
+    def _forward_maps(self, RAmaps, REmaps):
+        with F_.region("mnet"):
+            want = torch.bfloat16 if F_.act_bf16() else torch.float32
+        shape = (RAmaps.shape[0], self.numGroupFrames, self.rangeSize, self.azimuthSize, self.numFilters)
+        for t in (RAmaps, REmaps):
+            if not t.is_cuda or t.dtype != want or tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError("MNet feature windows must be contiguous GPU tensors %r of %s under this precision mode, got %r %s"
+                                 % (shape, want, tuple(t.shape), t.dtype))
+        return self._branches_and_heads(RAmaps, REmaps, chirp=False)

@@ -44,6 +44,13 @@ SIGNATURES = {
     "hupr_fft_chain_loader_means_f32": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "hupr_mnet_fwd_means_f32": (c_int, [c_void_p] * 5 + [c_long, c_int, c_void_p]),
     "hupr_mnet_fwd_means_bf16act": (c_int, [c_void_p] * 5 + [c_long, c_int, c_void_p]),
+    # live stream (csrc/stream_window.hip)
+    "hupr_stream_state_bytes": (c_size_t, []),
+    "hupr_stream_reset": (c_int, [c_void_p, c_void_p]),
+    "hupr_stream_advance": (c_int, [c_void_p, c_int, c_int, c_void_p]),
+    "hupr_mnet_stream_f32": (c_int, [c_void_p] * 3 + [c_int, c_int] + [c_void_p] * 6 + [c_int] * 3 + [c_void_p]),
+    "hupr_mnet_stream_bf16act": (c_int, [c_void_p] * 3 + [c_int, c_int] + [c_void_p] * 6 + [c_int] * 3 + [c_void_p]),
+    "hupr_stream_keypoints_f32": (c_int, [c_void_p] * 3 + [c_long, c_int, c_float, c_void_p]),
     "hupr_fft_chain_opts": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "hupr_loader_normalize_c64": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
     "hupr_dca1000_deinterleave": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),

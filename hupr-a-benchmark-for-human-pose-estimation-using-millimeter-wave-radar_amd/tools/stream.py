@@ -1,0 +1,375 @@
+"""Live pose streaming: one hori + vert radar frame in per frame period, one pose out.
+
+The offline route treats every frame like a dataset item: gather its G-frame window (datasets.window_indices), upload and transform
+all 2 G sensor-frames, run HuPRNet.  Consecutive windows share all but one frame, and everything in front of the 3-D encoders is a
+pure function of ONE sensor-frame (the FFT chain with its frame-keyed dither, the fused loader, the MNet front end on the 16
+elevation-mean planes).  ``PoseStream`` therefore keeps a ring of mean planes on the device (256 KB per sensor-frame), transforms only
+the new frame, and runs the MNet over the window straight from the ring (csrc/stream_window.hip) — bit-identical to the offline route.
+
+Window rule: ``stream_window_sources(center, newest, G)``.  With ``lookahead = L`` the pose of frame ``n - L`` is emitted once frame
+``n`` has been pushed; ``flush()`` emits the last ``min(L, frames pushed)`` poses with ``newest`` held at the last frame.  The default
+``L = G // 2 - 1`` reproduces ``window_indices`` for every frame of a sequence; ``L = 0`` answers every push at once, the upper half of
+the window repeating the newest frame (what the reference's loader does at the end of a sequence).
+
+The frame and pose counters the kernels read live on the device and are advanced by a launch of their own, so no launch argument
+depends on the frame number: with ``graph=True`` the steady-state push is ONE hipGraph replay (upload from pinned staging, FFT chain,
+window MNet, state advance, encoders / decoder / heads, arg-max, keypoint decode).
+
+    python -m hupr_amd.tools.stream --config mscsa_prgcn.yaml --dir <logs name> --raw <dir with hori/ and vert/ adc_data.bin>
+                                    [--lookahead N] [--math f32|bf16] [--no-graph] [--out poses.json]
+"""
+import argparse
+import json
+import os
+
+import numpy as np
+import torch
+
+from .. import functional as F_
+from .. import runtime as rt
+
+ADC_SHAPE = (4, 192, 256, 2)           # one sensor-frame: rx, chirp, sample, I/Q (int16)
+WARMUP_PUSHES = 2                      # eager pose-emitting pushes in front of the capture
+
+
+class StreamError(ValueError):
+    """Base of the session's argument errors."""
+
+
+class LookaheadError(StreamError):
+    """``lookahead`` outside 0 .. G // 2 - 1."""
+
+
+class FrameShapeError(StreamError):
+    """A pushed frame is not (lanes, 4, 192, 256, 2), or hori and vert differ."""
+
+
+class FrameDtypeError(StreamError):
+    """A pushed frame is not int16."""
+
+
+class StreamEndedError(StreamError):
+    """push() after flush(): the sequence has ended, reset() starts the next one."""
+
+
+def stream_window_sources(center, newest, G):
+    """Frame numbers (counted from the start of the stream) of the G-frame window around ``center`` when ``newest`` is the last frame
+    that exists: frames before the start repeat frame 0, frames that have not arrived repeat the newest."""
+    return [min(max(center - G // 2 + j, 0), newest) for j in range(G)]
+
+
+def check_lookahead(lookahead, G):
+    """-> the session's lookahead (None: G // 2 - 1, every window complete on its future side)."""
+    if G < 2 or G % 2:
+        raise StreamError("numGroupFrames must be even and >= 2, got %r" % (G,))
+    if lookahead is None:
+        return G // 2 - 1
+    if isinstance(lookahead, bool) or not isinstance(lookahead, (int, np.integer)) or not 0 <= lookahead <= G // 2 - 1:
+        raise LookaheadError("lookahead must be an integer in 0..%d for %d-frame windows, got %r" % (G // 2 - 1, G, lookahead))
+    return int(lookahead)
+
+
+def check_frames(adc_hori, adc_vert, lanes):
+    """The two tensors of one push: int16 (lanes, 4, 192, 256, 2) each, on the same kind of device."""
+    for name, t in (("adc_hori", adc_hori), ("adc_vert", adc_vert)):
+        if not isinstance(t, torch.Tensor):
+            raise FrameDtypeError("%s must be a torch int16 tensor, got %s" % (name, type(t).__name__))
+        if t.dtype != torch.int16:
+            raise FrameDtypeError("%s must be int16, got %s" % (name, t.dtype))
+    if tuple(adc_hori.shape) != tuple(adc_vert.shape):
+        raise FrameShapeError("hori / vert frames differ in shape: %r vs %r" % (tuple(adc_hori.shape), tuple(adc_vert.shape)))
+    if tuple(adc_hori.shape) != (lanes,) + ADC_SHAPE:
+        raise FrameShapeError("a pushed frame must be %r, got %r" % ((lanes,) + ADC_SHAPE, tuple(adc_hori.shape)))
+    if adc_hori.is_cuda != adc_vert.is_cuda:
+        raise FrameShapeError("hori / vert frames must both be host or both be device tensors")
+
+
+class StreamSchedule:
+    """The emission schedule as host arithmetic (the mirror of the device counters): which frame a push answers and from which
+    source frames, and what a flush still owes."""
+
+    def __init__(self, G, lookahead=None):
+        self.G = G
+        self.lookahead = check_lookahead(lookahead, G)
+        self.reset()
+
+    def reset(self):
+        self.frames_pushed = 0
+        self.frames_emitted = 0
+        self.ended = False
+
+    def push(self):
+        """Count one pushed frame -> (center, window sources) of the pose it answers, or None during the first ``lookahead`` pushes."""
+        if self.ended:
+            raise StreamEndedError("flush() ended this sequence; reset() starts a new one")
+        n = self.frames_pushed
+        self.frames_pushed += 1
+        c = n - self.lookahead
+        if c < 0:
+            return None
+        self.frames_emitted += 1
+        return c, stream_window_sources(c, n, self.G)
+
+    def flush(self):
+        """-> [(center, window sources)] of the min(lookahead, frames pushed) poses still owed; ends the sequence."""
+        out = []
+        newest = self.frames_pushed - 1
+        while self.frames_emitted < self.frames_pushed:
+            c = self.frames_emitted
+            self.frames_emitted += 1
+            out.append((c, stream_window_sources(c, newest, self.G)))
+        self.ended = True
+        return out
+
+
+class PoseFrame:
+    """One emitted pose.  ``frame``: its number in the stream; ``keypoints`` (lanes, K, 2) fp32 image pixels (x, y); ``scores``
+    (lanes, K) the GCN head's maxima; ``indices`` (lanes, K) int32 arg-max positions; ``heatmap`` (lanes, K, 1, H, W) and
+    ``gcn_heatmap`` (lanes, 1, K, H, W).  Device tensors owned by the session, valid until its next push / flush / reset."""
+    __slots__ = ("frame", "keypoints", "scores", "indices", "heatmap", "gcn_heatmap")
+
+    def __init__(self, frame, keypoints, scores, indices, heatmap, gcn_heatmap):
+        self.frame, self.keypoints, self.scores, self.indices = frame, keypoints, scores, indices
+        self.heatmap, self.gcn_heatmap = heatmap, gcn_heatmap
+
+    def _map(self, fn):
+        return PoseFrame(self.frame, *[fn(getattr(self, k)) for k in self.__slots__[1:]])
+
+    def clone(self):
+        return self._map(torch.clone)
+
+    def cpu(self):
+        """Host copies (synchronises)."""
+        return self._map(lambda t: t.cpu())
+
+
+class PoseStream:
+    """Streaming session around a HuPRNet.  ``push(adc_hori, adc_vert)`` takes the new int16 frame of both sensors,
+    (lanes, 4, 192, 256, 2) each — device tensors are used directly, host tensors go through the session's pinned staging and an
+    asynchronous copy — and returns the ``PoseFrame`` that is due (None during the first ``lookahead`` pushes).  ``flush()`` returns the
+    poses still owed at the end of a sequence (independent copies), ``reset()`` starts the next one.  ``lanes`` radars advance in lock
+    step (the model's batch axis).  The precision mode is the model's ``math_mode`` or, without one, the calling thread's at
+    construction; it holds for the session.  Weights changed between pushes are honoured: the packed copies are refreshed in front of
+    the replay.  A push waits for the previous one to finish before it reuses the pinned staging.  Side effect: like ``engine.infer``,
+    ``push`` and ``flush`` put a model that is in training mode into eval mode (``model.eval()``) and leave it there.  ``lanes = 2`` is
+    the model at batch 2: bit-identical to the offline route on a batch of 2, not to two ``lanes = 1`` sessions (the existing kernels
+    take other launch routes for a single sample)."""
+
+    def __init__(self, model, cfg, lanes=1, lookahead=None, graph=True, device=None):
+        D = cfg.DATASET
+        self.G = D.numGroupFrames
+        self.schedule = StreamSchedule(self.G, lookahead)
+        self.lookahead = self.schedule.lookahead
+        if not isinstance(lanes, int) or lanes < 1:
+            raise StreamError("lanes must be a positive integer, got %r" % (lanes,))
+        self.device = torch.device(device) if device is not None else next(model.parameters()).device
+        if self.device.type != "cuda":
+            raise rt.HuprError("PoseStream needs a GPU model (no CPU fallback), got %s" % self.device)
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        if (D.rangeSize, D.azimuthSize) != (64, 64) or (D.numFrames, model.numFilters) != (8, 32):
+            raise StreamError("the FFT chain and the MNet kernels are specialised for 64 x 64 maps, 8 chirp steps and 32 filters")
+        self.model, self.cfg, self.lanes, self.graph = model, cfg, lanes, bool(graph)
+        self.mode = model.math_mode if model.math_mode is not None else F_.MATH
+        with F_.math_mode(self.mode), F_.region("mnet"):
+            self._bf16 = F_.act_bf16()
+        self.K, self.H, self.W = D.numKeypoints, D.heatmapSize, D.heatmapSize
+        self.ratio = float(D.imgSize) / float(D.heatmapSize)
+        self.pixels = D.rangeSize * D.azimuthSize
+        L, dev, G = rt.lib(), self.device, self.G
+        with torch.cuda.device(dev):
+            self._pinned = torch.empty((2, lanes) + ADC_SHAPE, dtype=torch.int16).pin_memory()
+            self._adc = torch.empty((2, lanes) + ADC_SHAPE, dtype=torch.int16, device=dev)
+            self._staging = torch.empty((2, lanes, 16, self.pixels), dtype=torch.float32, device=dev)
+            self._ring = torch.zeros((2, lanes, G, 16, self.pixels), dtype=torch.float32, device=dev)
+            self._state = torch.zeros(max(int(L.hupr_stream_state_bytes()), 16), dtype=torch.uint8, device=dev)
+            self._ws_bytes = int(L.hupr_fft_chain_ws_bytes(2 * lanes))
+            self._ws = torch.empty(max(self._ws_bytes, 16), dtype=torch.uint8, device=dev)
+            act = torch.bfloat16 if self._bf16 else torch.float32
+            self._maps = tuple(torch.empty((lanes, G, D.rangeSize, D.azimuthSize, 32), dtype=act, device=dev) for _ in range(2))
+            self._idx = torch.empty((lanes, self.K), dtype=torch.int32, device=dev)
+            self._mx = torch.empty((lanes, self.K), dtype=torch.float32, device=dev)
+            self._kp = torch.empty((lanes, self.K, 2), dtype=torch.float32, device=dev)
+            self._done = torch.cuda.Event()
+        self._graphs = {}              # "host" / "device" input -> (CUDAGraph, (heatmap, gcn_heatmap))
+        self._eager_emits = 0
+        self._busy = False
+
+    # -- counters (host mirrors of the device state) ---------------------------------------------------------------------------
+    @property
+    def frames_pushed(self):
+        return self.schedule.frames_pushed
+
+    @property
+    def frames_emitted(self):
+        return self.schedule.frames_emitted
+
+    # -- launches -------------------------------------------------------------------------------------------------------------
+    def _front(self, flush):
+        """FFT chain to means on the 2 x lanes new sensor-frames (not for a flush), the window MNet, the state advance."""
+        from ..preprocessing import process_iwr1843 as pre
+        L, s = rt.lib(), rt.stream()
+        if not flush:
+            flags = pre._flags(None, False, None)
+            if flags == 0:
+                rt.check(L.hupr_fft_chain_loader_means_f32(rt.ptr(self._adc), 2 * self.lanes, rt.ptr(self._staging), rt.ptr(self._ws),
+                                                           self._ws_bytes, s))
+            else:
+                rt.check(L.hupr_fft_chain_opts(rt.ptr(self._adc), 2 * self.lanes, rt.ptr(self._staging), flags, 2, rt.ptr(self._ws),
+                                               self._ws_bytes, s))
+        ra, re = self.model.RAchirpNet.temporalConvWx1x1, self.model.REchirpNet.temporalConvWx1x1
+        fn = L.hupr_mnet_stream_bf16act if self._bf16 else L.hupr_mnet_stream_f32
+        rt.check(fn(None if flush else rt.ptr(self._staging), rt.ptr(self._ring), rt.ptr(self._state), self.lookahead, int(flush),
+                    rt.ptr(ra.weight), rt.ptr(ra.bias), rt.ptr(re.weight), rt.ptr(re.bias), rt.ptr(self._maps[0]),
+                    rt.ptr(self._maps[1]), self.lanes, self.G, self.pixels, s))
+        rt.check(L.hupr_stream_advance(rt.ptr(self._state), self.lookahead, int(flush), s))
+
+    def _back(self):
+        """Encoders, decoder, heads on the window maps; arg-max of the GCN head; keypoints in image pixels."""
+        heat, gcn = self.model.forward_chirp_maps(*self._maps)
+        L, s = rt.lib(), rt.stream()
+        rows = self.lanes * self.K
+        rt.check(L.hupr_argmax_rows_f32(rt.ptr(F_._c(gcn)), rows, self.H * self.W, rt.ptr(self._idx), rt.ptr(self._mx), s))
+        rt.check(L.hupr_stream_keypoints_f32(rt.ptr(self._idx), rt.ptr(self._mx), rt.ptr(self._kp), rows, self.W, self.ratio, s))
+        return heat, gcn
+
+    def _capture(self, kind):
+        torch.cuda.synchronize(self.device)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            if kind == "host":
+                self._adc.copy_(self._pinned, non_blocking=True)
+            self._front(False)
+            out = self._back()
+        self._graphs[kind] = (g, out)
+        return self._graphs[kind]
+
+    def _wait(self):
+        if self._busy:
+            self._done.synchronize()
+            self._busy = False
+
+    def _frame(self, center, out):
+        return PoseFrame(center, self._kp, self._mx, self._idx, out[0], out[1])
+
+    # -- public ---------------------------------------------------------------------------------------------------------------
+    def push(self, adc_hori, adc_vert):
+        check_frames(adc_hori, adc_vert, self.lanes)
+        if self.schedule.ended:
+            raise StreamEndedError("flush() ended this sequence; reset() starts a new one")
+        host = not adc_hori.is_cuda
+        if self.model.training:
+            self.model.eval()
+        with torch.cuda.device(self.device), torch.no_grad(), F_.math_mode(self.mode):
+            if host:
+                self._wait()                                   # the previous upload has left the pinned staging
+                self._pinned[0].copy_(adc_hori)
+                self._pinned[1].copy_(adc_vert)
+            else:
+                self._adc[0].copy_(adc_hori, non_blocking=True)
+                self._adc[1].copy_(adc_vert, non_blocking=True)
+            emit = self.schedule.frames_pushed >= self.lookahead
+            if self.graph and emit and self._eager_emits >= WARMUP_PUSHES:
+                kind = "host" if host else "device"
+                g, out = self._graphs.get(kind) or self._capture(kind)
+                self.model._refresh_packed(self.device)        # weights changed since the last push: one table launch, in place
+                g.replay()
+            else:
+                if host:
+                    self._adc.copy_(self._pinned, non_blocking=True)
+                self._front(False)
+                out = None
+                if emit:
+                    out = self._back()
+                    self._eager_emits += 1
+            if host:
+                self._done.record()
+                self._busy = True
+        due = self.schedule.push()
+        return None if due is None else self._frame(due[0], out)
+
+    def flush(self):
+        frames = []
+        if self.model.training:
+            self.model.eval()
+        with torch.cuda.device(self.device), torch.no_grad(), F_.math_mode(self.mode):
+            for center, _ in self.schedule.flush():
+                self._front(True)
+                frames.append(self._frame(center, self._back()).clone())
+        return frames
+
+    def reset(self):
+        with torch.cuda.device(self.device):
+            rt.check(rt.lib().hupr_stream_reset(rt.ptr(self._state), rt.stream()))
+        self.schedule.reset()
+
+
+# ---- command ---------------------------------------------------------------------------------------------------------------------
+def parse(argv=None):
+    p = argparse.ArgumentParser(prog="python -m hupr_amd.tools.stream", description="stream a raw capture frame by frame")
+    p.add_argument("--config", type=str, default="mscsa_prgcn.yaml", help="config file (under ./config if that exists)")
+    p.add_argument("--dir", type=str, default="test", help="logs/<dir>/model_best.pth holds the weights")
+    p.add_argument("--raw", type=str, required=True, help="directory holding hori/adc_data.bin and vert/adc_data.bin")
+    p.add_argument("--lookahead", type=int, default=None, help="frames of look-ahead (default G/2 - 1; 0 = zero latency)")
+    p.add_argument("--math", choices=("f32", "bf16"), default=None, help="precision mode (default: the process default)")
+    p.add_argument("--no-graph", action="store_true", help="eager launches instead of one hipGraph replay per frame")
+    p.add_argument("--out", type=str, default="poses.json")
+    return p.parse_args(argv)
+
+
+def load_model_best(model, log_dir, device):
+    """``model_best.pth`` of ``log_dir`` into ``model``, the way Runner.loadModelWeight reads it for evaluation."""
+    from ..preprocessing import process_iwr1843 as pre
+    path = os.path.join(log_dir, "model_best.pth")
+    if not os.path.exists(path):
+        raise FileNotFoundError("%s not found" % path)
+    ck = torch.load(path, map_location=device)
+    model.load_state_dict(ck["model_state_dict"])
+    side = os.path.join(log_dir, "preprocess.json")
+    if os.path.exists(side):
+        with open(side) as fp:
+            trained = json.load(fp).get("fft_zero_doppler")
+        if trained and trained != pre.ZERO_DOPPLER:
+            print("==========>WARNING: these weights were trained with HUPR_FFT_ZERO_DOPPLER=%s, this process runs %s" % (trained, pre.ZERO_DOPPLER))
+    print("==========>Load the model weight from %s, saved at epoch %d" % (log_dir, ck["epoch"]))
+
+
+def main(argv=None):
+    from ..config_tree import load_config
+    from ..models import HuPRNet
+    from ..preprocessing.process_iwr1843 import dca1000_frames
+    args = parse(argv)
+    if not torch.cuda.is_available():
+        raise rt.HuprError("the live stream needs a GPU (no CPU fallback)")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    cfg = load_config(args.config, "./config" if os.path.isdir("./config") else None)
+    model = HuPRNet(cfg).to(dev).eval()
+    load_model_best(model, os.path.join("./logs", args.dir), dev)
+    if args.math is not None:
+        model.math_mode = args.math
+    frames = []
+    for sensor in ("hori", "vert"):
+        raw = torch.from_numpy(np.fromfile(os.path.join(args.raw, sensor, "adc_data.bin"), dtype=np.int16)).to(dev)
+        frames.append(dca1000_frames(raw))                      # (frames, 4, 192, 256, 2) int16, de-interleaved on the GPU
+    n = min(frames[0].shape[0], frames[1].shape[0])
+    session = PoseStream(model, cfg, lanes=1, lookahead=args.lookahead, graph=not args.no_graph, device=dev)
+    records = []
+
+    def record(pf):
+        kp = np.concatenate([pf.keypoints.cpu().numpy()[0], pf.scores.cpu().numpy()[0][:, None]], axis=1)
+        records.append({"frame": int(pf.frame), "keypoints": [[float(x), float(y), float(s)] for x, y, s in kp]})
+
+    for i in range(n):
+        pf = session.push(frames[0][i:i + 1], frames[1][i:i + 1])
+        if pf is not None:
+            record(pf)
+    for pf in session.flush():
+        record(pf)
+    with open(args.out, "w") as fp:
+        json.dump(records, fp)
+    print("%d frames -> %s" % (len(records), args.out))
+    return records
+
+
+if __name__ == "__main__":
+    main()

@@ -291,6 +291,33 @@ int hupr_mnet_bwd_f32(const float* x_or_null, const float* means_or_null, const 
                       const float* dy, float* dw, float* dbias, long n_bg, int pixels, void* ws, size_t ws_bytes,
                       hupr_stream_t stream);
 
+/* (a3, live stream) the MNet front end over a sliding window — replaces forward_chirp (models/networks.py:23-33) on the G-frame
+ *      window the loader gathers around a frame (datasets/dataset.py:120-139) when the frames arrive one at a time.
+ * The session state (hupr_stream_state_bytes() bytes on the device; hupr_stream_reset zeroes it) counts the sensor-frames pushed
+ * and the poses emitted.  With n = frames pushed so far, a push (flush == 0) files the new frame n and serves the centre frame
+ * c = n - lookahead with newest = n; a flush serves c = poses emitted with newest = n - 1.  Window position j reads frame
+ * clamp(c - G/2 + j, 0, newest): the new frame from `staging`, any other from ring slot (frame mod G).
+ * staging : float [2 sensors][lanes][16][pixels]  the new frame's elevation-mean planes (hupr_fft_chain_loader_means_f32 on the
+ *           2 * lanes new sensor-frames, hori first); null for a flush.  Copied into ring slot n mod G by the same launch.
+ * ring    : float [2][lanes][G][16][pixels]       the session's mean planes of the last G frames
+ * out_*   : [lanes][G][pixels][32] channels-last, fp32 or (bf16act) bf16 — what Encoder3D consumes; bit-identical to
+ *           hupr_mnet_fwd_means_* on the gathered planes.  0 <= lookahead <= G/2 - 1, G even; lanes == 0 is a no-op.
+ * hupr_stream_advance follows on the same stream: a push counts the frame (and the pose once n >= lookahead), a flush the pose.
+ * No argument of either launch depends on the frame number, so one captured graph serves every frame. */
+size_t hupr_stream_state_bytes(void);
+int hupr_stream_reset(void* state, hupr_stream_t stream);
+int hupr_stream_advance(void* state, int lookahead, int flush, hupr_stream_t stream);
+int hupr_mnet_stream_f32(const float* staging_or_null, float* ring, const void* state, int lookahead, int flush,
+                         const float* w_hori, const float* bias_hori, const float* w_vert, const float* bias_vert,
+                         float* out_hori, float* out_vert, int lanes, int G, int pixels, hupr_stream_t stream);
+int hupr_mnet_stream_bf16act(const float* staging_or_null, float* ring, const void* state, int lookahead, int flush,
+                             const float* w_hori, const float* bias_hori, const float* w_vert, const float* bias_vert,
+                             void* out_hori, void* out_vert, int lanes, int G, int pixels, hupr_stream_t stream);
+/* arg-max rows (hupr_argmax_rows_f32) -> keypoints[rows][2] = (idx % W, idx / W) * ratio in image pixels, (0, 0) where the
+ * maximum is <= 0 — the decode of misc/metrics.py:10-38 scaled as tools/run.py:47-53 hands it to saveKeypoints */
+int hupr_stream_keypoints_f32(const int* idx, const float* maxval, float* keypoints, long rows, int W, float ratio,
+                              hupr_stream_t stream);
+
 /* tri-/bilinear align_corners=True resampling (models/layers.py:84,89,199,204; gcn_networks.py:49,63) */
 int hupr_interp_linear_fwd_f32(const float* x, float* y, int Bn, int Di, int Hi, int Wi, int Do, int Ho, int Wo,
                                int C, int in_ld, int out_ld, hupr_stream_t stream);
