@@ -12,6 +12,7 @@ bookkeeping; every kernel is reached through ``runtime.lib()`` and fails loudly 
 """
 import ctypes
 import os
+import threading
 
 import numpy as np
 import torch
@@ -21,16 +22,12 @@ from . import weight_cache as wcache
 
 _ws_cache = {}
 CONV_PROBE = None      # bench.py installs a callable(x, co, k) -> (start_event, end_event) | None
-# Precision state (round 5: per THREAD, ADVICE r3 item 5 / VERDICT r4 weak 2).  ``_st.math`` = matrix-pipe arithmetic of the GEMM-shaped
-# ops: "f32" (parity path) or "bf16"; ``_st.act_f32_here`` / ``_st.region_switched`` = inside a region switched to "f32act" / to the fp32
-# pipe.  Rounds 1-4 kept the three as module globals mutated from whichever thread ran a forward or — through the autograd engine's
-# device thread — a backward: two models driven from two threads of one process (or one per device) silently shared one pipe
-# selection.  Now every thread owns its copy: ``set_math`` sets the calling thread's mode (and the default a thread that never chose
-# one starts from), ``math_mode`` scopes it, ``HuPRNet.math_mode`` pins it per model, and every autograd node carries the state of
-# its forward into its backward on whatever thread the engine runs it (``_math_scoped``).  ``F_.MATH`` etc. stay readable
-# (module ``__getattr__``) and name the calling thread's values.
-import threading
-
+# Precision state, per THREAD (two models driven from two threads of one process must not share one pipe selection).  ``_st.math`` =
+# matrix-pipe arithmetic of the GEMM-shaped ops: "f32" (parity path) or "bf16"; ``_st.act_f32_here`` / ``_st.region_switched`` = inside a
+# region switched to "f32act" / to the fp32 pipe.  ``set_math`` sets the calling thread's mode (and the default a thread that never chose
+# one starts from), ``math_mode`` scopes it, ``HuPRNet.math_mode`` pins it per model, and every autograd node carries the state of its
+# forward into its backward on whatever thread the engine runs it (``_math_scoped``).  ``F_.MATH`` etc. stay readable (module
+# ``__getattr__``) and name the calling thread's values.
 _DEFAULT_MATH = ["f32"]
 
 
@@ -39,6 +36,12 @@ class _State(threading.local):
         self.math = _DEFAULT_MATH[0]
         self.act_f32_here = False
         self.region_switched = False
+
+    def get(self):
+        return self.math, self.act_f32_here, self.region_switched
+
+    def set(self, triple):
+        self.math, self.act_f32_here, self.region_switched = triple
 
 
 _st = _State()
@@ -74,12 +77,12 @@ class math_mode:
         self.mode = mode
 
     def __enter__(self):
-        self.prev = (_st.math, _st.act_f32_here, _st.region_switched)
-        _st.math, _st.act_f32_here, _st.region_switched = self.mode, False, False
+        self.prev = _st.get()
+        _st.set((self.mode, False, False))
         return self
 
     def __exit__(self, *exc):
-        _st.math, _st.act_f32_here, _st.region_switched = self.prev
+        _st.set(self.prev)
         return False
 
 
@@ -109,7 +112,7 @@ class region:
         self.name = name
 
     def __enter__(self):
-        self.prev = (_st.math, _st.act_f32_here, _st.region_switched)
+        self.prev = _st.get()
         mode = PRECISION.get(self.name)
         if _st.math == "bf16" and mode == "f32":
             _st.math = "f32"
@@ -118,7 +121,7 @@ class region:
         return self
 
     def __exit__(self, *exc):
-        _st.math, _st.act_f32_here, _st.region_switched = self.prev
+        _st.set(self.prev)
         return False
 
 
@@ -127,17 +130,17 @@ def _math_scoped(cls):
     fwd, bwd = cls.forward, cls.backward
 
     def forward(ctx, *a):
-        ctx._hupr_math = (_st.math, _st.act_f32_here, _st.region_switched)
+        ctx._hupr_math = _st.get()
         return fwd(ctx, *a)
 
     def backward(ctx, *g):
         # (the engine runs this on ITS thread: that thread's state is set from the node and restored afterwards)
-        prev = (_st.math, _st.act_f32_here, _st.region_switched)
-        _st.math, _st.act_f32_here, _st.region_switched = ctx._hupr_math
+        prev = _st.get()
+        _st.set(ctx._hupr_math)
         try:
             return bwd(ctx, *g)
         finally:
-            _st.math, _st.act_f32_here, _st.region_switched = prev
+            _st.set(prev)
     cls.forward, cls.backward = staticmethod(forward), staticmethod(backward)
     return cls
 
@@ -168,6 +171,25 @@ def workspace(nbytes, device):
 
 def _c(t):
     return t if t.is_contiguous() else t.contiguous()
+
+
+def _ws_args(ws):
+    """(pointer, bytes) of an optional workspace."""
+    return (rt.ptr(ws), ws.numel()) if ws is not None else (None, 0)
+
+
+def _probe_begin(probe, *key):
+    """Open a measured bracket on the current stream.  ``probe``: CONV_PROBE / ATTN_PROBE as the caller reads it at call time
+    (bench.py installs and removes them between phases), a callable(*key) -> (start_event, end_event) | None."""
+    ev = probe(*key) if probe is not None else None
+    if ev is not None:
+        ev[0].record()
+    return ev
+
+
+def _probe_end(ev):
+    if ev is not None:
+        ev[1].record()
 
 
 # ---- two compute streams ------------------------------------------------------------------------------------------
@@ -271,9 +293,8 @@ def _packed(weight, mode, kind):
 
 # The eight 1x1 projection weights of an MSCSA level as the two (4C, C) matrices its two GEMMs read — [phi_cross | theta_cross |
 # phi_self | theta_self] per map — kept as ENTRIES OF THE PACK TABLE: the one table-driven launch after an optimiser step refreshes
-# them with everything else, where rounds 1-4 concatenated them with two ATen launches per level and step.  Two copies per map: the
-# plain one (backward GEMMs, GEMM-attention fallback) and the one whose query (theta) rows carry log2(e) for the QS attention
-# kernels (csrc/attention_bf16.hip, kDeferBits).
+# them with everything else.  Two copies per map: the plain one (backward GEMMs, GEMM-attention fallback) and the one whose query
+# (theta) rows carry log2(e) for the QS attention kernels (csrc/attention_bf16.hip, kDeferBits).
 _PROJ_KINDS = (wcache.COPY, wcache.COPY_LOG2E, wcache.COPY, wcache.COPY_LOG2E)
 QS_ATTN = True             # test aid: False = the plain-Q kernels (fma per score)
 
@@ -312,9 +333,8 @@ def _halo_ok(x, k, pad, co=4):
 
 # BatchNorm statistics fused into the producing convolution (hupr_conv3x3_halo_bf16act_stats, 64-channel 3-D layers = the
 # largest tensors of the step): the column sums wait here, keyed by the output's address, for the BatchNorm that consumes that
-# tensor next (_bn_params pops them).  Round 3: the kernel keeps running per-lane-pair sums in LDS (plain read-add-write of a
-# private slot, deferred epilogue intact) and reduces across lanes once per launch: +6 us on a 222 us launch instead of +14 us
-# and the immediate epilogue, -0.16 ms / +0.7 % frames/s per step measured in interleaved same-box runs -> ON by default
+# tensor next (_bn_params pops them).  The kernel keeps running per-lane-pair sums in LDS and reduces across lanes once per launch:
+# +6 us on a 222 us launch, -0.16 ms / +0.7 % frames/s per step measured in interleaved same-box runs -> ON by default
 # (CONV_STATS = False switches it off: the parity tests compare the two).
 CONV_STATS = True
 ATTN_LEVEL_BATCH = True    # test aid: False = one launch per attention at every level
@@ -329,50 +349,40 @@ def _conv_raw(x, weight, mode, bias, res, co, k, pad, out_extent, out=None, stat
     B, Di, Hi, Wi, Ci = _vox(x)
     Do, Ho, Wo = out_extent
     y = torch.empty((B, Do, Ho, Wo, co), dtype=x.dtype, device=x.device) if out is None else out
-    ev = CONV_PROBE(x, co, k) if CONV_PROBE is not None else None
     abf = x.dtype == torch.bfloat16
+    L = rt.lib()
     if _halo_ok(x, k, pad, co):
         assert res is None or res.dtype == x.dtype
         wp = _packed(weight, mode, 1)
-        if ev is not None:
-            ev[0].record()
+        ev = _probe_begin(CONV_PROBE, x, co, k)
         if (stats and CONV_STATS and abf and bias is None and res is None and out is None
-                and rt.lib().hupr_conv3x3_halo_stats_supported(B, Di, Hi, Wi, Ci, co, k[0])):
-            rows = rt.lib().hupr_conv3x3_halo_stats_rows()
+                and L.hupr_conv3x3_halo_stats_supported(B, Di, Hi, Wi, Ci, co, k[0])):
+            rows = L.hupr_conv3x3_halo_stats_rows()
             st = torch.empty((rows, 2, co), dtype=torch.float64, device=x.device)
-            rt.check(rt.lib().hupr_conv3x3_halo_bf16act_stats(rt.ptr(x), rt.ptr(wp), rt.ptr(y), B, Di, Hi, Wi, Ci, Ci, co, co,
-                                                               k[0], rt.ptr(st), rt.stream()))
+            rt.check(L.hupr_conv3x3_halo_bf16act_stats(rt.ptr(x), rt.ptr(wp), rt.ptr(y), B, Di, Hi, Wi, Ci, Ci, co, co, k[0], rt.ptr(st),
+                                                       rt.stream()))
             _conv_stats[y.data_ptr()] = (st, rows, B * Do * Ho * Wo, co)
-            if ev is not None:
-                ev[1].record()
+            _probe_end(ev)
             return y
-        L = rt.lib()
         # inference on small grids (config C2: B = 1): the reduction is sliced over workgroups, partial sums through a workspace
         nws = L.hupr_conv3x3_halo_splitk_ws_bytes(B, Di, Hi, Wi, Ci, co, k[0]) if (abf and infer) else 0
         if nws:
             ws = workspace(nws, x.device)
-            rt.check(L.hupr_conv3x3_halo_bf16act_ws(rt.ptr(x), rt.ptr(wp), rt.ptr(bias) if bias is not None else None,
-                                                    rt.ptr(res) if res is not None else None, rt.ptr(y), B, Di, Hi, Wi, Ci, Ci, co, co, co,
-                                                    k[0], rt.ptr(ws), ws.numel(), rt.stream()))
+            rt.check(L.hupr_conv3x3_halo_bf16act_ws(rt.ptr(x), rt.ptr(wp), rt.ptr(bias), rt.ptr(res), rt.ptr(y), B, Di, Hi, Wi, Ci, Ci,
+                                                    co, co, co, k[0], rt.ptr(ws), ws.numel(), rt.stream()))
         else:
             fn = L.hupr_conv3x3_halo_bf16act if abf else L.hupr_conv3x3_halo_bf16
-            rt.check(fn(rt.ptr(x), rt.ptr(wp), rt.ptr(bias) if bias is not None else None,
-                        rt.ptr(res) if res is not None else None, rt.ptr(y), B, Di, Hi, Wi, Ci, Ci, co, co, co, k[0], rt.stream()))
-        if ev is not None:
-            ev[1].record()
+            rt.check(fn(rt.ptr(x), rt.ptr(wp), rt.ptr(bias), rt.ptr(res), rt.ptr(y), B, Di, Hi, Wi, Ci, Ci, co, co, co, k[0], rt.stream()))
+        _probe_end(ev)
         return y
     if abf:
         raise rt.HuprError("bf16-stored activations are only supported by the halo-tiled 3x3 convolutions "
                            "(shape %r, kernel %r); cast to fp32 first" % (tuple(x.shape), k))
     wp = _packed(weight, mode, 0)
-    if ev is not None:
-        ev[0].record()
-    rt.check(_fn("conv_fwd")(
-        rt.ptr(x), rt.ptr(wp), rt.ptr(bias) if bias is not None else None,
-        rt.ptr(res) if res is not None else None, rt.ptr(y), B, Di, Hi, Wi, Ci, Ci, Do, Ho, Wo, co, co,
-        co, k[0], k[1], k[2], pad[0], pad[1], pad[2], 0, rt.stream()))
-    if ev is not None:
-        ev[1].record()
+    ev = _probe_begin(CONV_PROBE, x, co, k)
+    rt.check(_fn("conv_fwd")(rt.ptr(x), rt.ptr(wp), rt.ptr(bias), rt.ptr(res), rt.ptr(y), B, Di, Hi, Wi, Ci, Ci, Do, Ho, Wo, co, co,
+                             co, k[0], k[1], k[2], pad[0], pad[1], pad[2], 0, rt.stream()))
+    _probe_end(ev)
     return y
 
 
@@ -419,31 +429,53 @@ def conv_infer(x, weight, pad):
     return ConvPartial(part, n, (B, D, H, W, co))
 
 
+def _tail_side(t):
+    """(pointer, slice count) of one input of ``infer_tail``: a ConvPartial's slices, a stored tensor (0 slices), or nothing."""
+    if t is None:
+        return None, 0
+    return (rt.ptr(t.slices), t.n) if isinstance(t, ConvPartial) else (rt.ptr(_c(t)), 0)
+
+
+def _bn_eval_args(bn):
+    """(gamma, beta, running mean, running variance, eps) as an eval-mode kernel takes them; the null set for an absent second side."""
+    if bn is None:
+        return None, None, None, None, 0.0
+    return rt.ptr(bn.weight), rt.ptr(bn.bias), rt.ptr(bn.running_mean), rt.ptr(bn.running_var), float(bn.eps)
+
+
 def infer_tail(a, b=None, bn_a=None, bn_b=None, relu=False, prelu=None):
     """One launch for the elementwise tail of an inference block; ``a`` / ``b``: bf16 tensors or ConvPartials.
     BatchNorm form (bn_a given): relu?(bn_a(a) [+ bn_b(b)]) on running statistics; PReLU form: prelu(a [+ b])."""
-    def side(t):
-        if t is None:
-            return None, 0
-        return (rt.ptr(t.slices), t.n) if isinstance(t, ConvPartial) else (rt.ptr(_c(t)), 0)
-
     shape = a.shape
     C = shape[-1]
     M = int(np.prod(shape[:-1]))
     dev = (a.slices if isinstance(a, ConvPartial) else a).device
     y = torch.empty(tuple(shape), dtype=torch.bfloat16, device=dev)
-    (x1, n1), (x2, n2) = side(a), side(b)
-    bn = lambda m: (rt.ptr(m.weight), rt.ptr(m.bias), rt.ptr(m.running_mean), rt.ptr(m.running_var), float(m.eps)) \
-        if m is not None else (None, None, None, None, 0.0)
-    rt.check(rt.lib().hupr_infer_tail_bf16act(0 if bn_a is not None else 1, x1, n1, *bn(bn_a), x2, n2, *bn(bn_b),
-                                              rt.ptr(prelu) if prelu is not None else None, 1 if relu else 0, rt.ptr(y), M, C,
-                                              rt.stream()))
+    rt.check(rt.lib().hupr_infer_tail_bf16act(0 if bn_a is not None else 1, *_tail_side(a), *_bn_eval_args(bn_a), *_tail_side(b),
+                                              *_bn_eval_args(bn_b), rt.ptr(prelu), 1 if relu else 0, rt.ptr(y), M, C, rt.stream()))
     return y
 
 
 def _ksize(w):
     k = tuple(w.shape[2:])
     return (1,) + k if len(k) == 2 else k
+
+
+def _dgrad_pad(k, pad):
+    """Padding of the input-gradient convolution (the forward's taps reversed) of a stride-1 convolution."""
+    return k[0] - 1 - pad[0], k[1] - 1 - pad[1], k[2] - 1 - pad[2]
+
+
+def _halo_wgrad(x, dy, weight):
+    """Weight gradient of a halo-tiled 3x3(x3) "same" convolution -> (dw in the parameter layout, written into the gradient sink?)."""
+    B, D, H, W, Ci = _vox(x)
+    Co, k0 = weight.shape[0], _ksize(weight)[0]
+    L = rt.lib()
+    dw, direct = _pgrad(weight)
+    ws = workspace(L.hupr_conv3x3_wgrad_halo_ws_bytes(Ci, Co, k0), x.device)
+    fn = L.hupr_conv3x3_wgrad_halo_bf16act if x.dtype == torch.bfloat16 else L.hupr_conv3x3_wgrad_halo_bf16
+    rt.check(fn(rt.ptr(x), rt.ptr(dy), rt.ptr(dw), B, D, H, W, Ci, Ci, Co, Co, k0, rt.ptr(ws), ws.numel(), rt.stream()))
+    return dw, direct
 
 
 @_math_scoped
@@ -485,28 +517,20 @@ class ConvFn(torch.autograd.Function):
                 dyp[..., :Co] = dy
                 wsrc = torch.zeros((co_pad,) + tuple(weight.shape[1:]), dtype=torch.float32, device=dy.device)
                 wsrc[:Co] = weight
-            dpad = (k[0] - 1 - pad[0], k[1] - 1 - pad[1], k[2] - 1 - pad[2])
-            dx = _conv_raw(dyp, wsrc, 1, None, None, Ci, k, dpad, (Di, Hi, Wi))      # packs [Ci][taps reversed][Co]
-        if ctx.needs_input_grad[1]:
-            dw, dw_direct = _pgrad(weight)
+            dx = _conv_raw(dyp, wsrc, 1, None, None, Ci, k, _dgrad_pad(k, pad), (Di, Hi, Wi))      # packs [Ci][taps reversed][Co]
         if ctx.needs_input_grad[1] and _halo_ok(x, k, pad) and Ci % 32 == 0 and Co % 8 == 0:
-            ws = workspace(L.hupr_conv3x3_wgrad_halo_ws_bytes(Ci, Co, k[0]), x.device)
-            fn = L.hupr_conv3x3_wgrad_halo_bf16act if x.dtype == torch.bfloat16 else L.hupr_conv3x3_wgrad_halo_bf16
-            rt.check(fn(rt.ptr(x), rt.ptr(dy), rt.ptr(dw), B, Di, Hi, Wi, Ci, Ci, Co, Co, k[0],
-                        rt.ptr(ws), ws.numel(), rt.stream()))
+            dw, dw_direct = _halo_wgrad(x, dy, weight)
         elif ctx.needs_input_grad[1] and x.dtype == torch.bfloat16:
             raise rt.HuprError("no bf16-activation weight-gradient kernel for shape %r" % (tuple(x.shape),))
         elif ctx.needs_input_grad[1]:
-            nbytes = L.hupr_conv_wgrad_ws_bytes(B, Do, Ho, Wo, Ci, Co, k[0], k[1], k[2])
-            ws = workspace(nbytes, x.device)
-            rt.check(_fn("conv_wgrad")(rt.ptr(x), rt.ptr(dy), rt.ptr(dw), B, Di, Hi, Wi, Ci, Ci, Do, Ho, Wo,
-                                           Co, Co, k[0], k[1], k[2], pad[0], pad[1], pad[2], rt.ptr(ws),
-                                           ws.numel(), rt.stream()))
+            dw, dw_direct = _pgrad(weight)
+            ws = workspace(L.hupr_conv_wgrad_ws_bytes(B, Do, Ho, Wo, Ci, Co, k[0], k[1], k[2]), x.device)
+            rt.check(_fn("conv_wgrad")(rt.ptr(x), rt.ptr(dy), rt.ptr(dw), B, Di, Hi, Wi, Ci, Ci, Do, Ho, Wo, Co, Co, k[0], k[1], k[2],
+                                       pad[0], pad[1], pad[2], rt.ptr(ws), ws.numel(), rt.stream()))
         if ctx.has_bias and ctx.needs_input_grad[2]:
             db, db_direct = _pgrad(ctx.bias_ref)
             ws = workspace(L.hupr_bn_ws_bytes(Co), dy.device)
-            rt.check(_act("colsum", dy)(rt.ptr(dy), B * Do * Ho * Wo, Co, rt.ptr(db), rt.ptr(ws), ws.numel(),
-                                        rt.stream()))
+            rt.check(_act("colsum", dy)(rt.ptr(dy), B * Do * Ho * Wo, Co, rt.ptr(db), rt.ptr(ws), ws.numel(), rt.stream()))
         dres = dy if ctx.has_res else None
         return dx, _pret(weight, dw, dw_direct), _pret(ctx.bias_ref, db, db_direct), dres, None, None, None
 
@@ -540,10 +564,9 @@ class DualConvFn(torch.autograd.Function):
         L = rt.lib()
         dx = None
         if ctx.needs_input_grad[0]:
-            dpad = (k[0] - 1 - pad[0], k[1] - 1 - pad[1], k[2] - 1 - pad[2])
+            dpad = _dgrad_pad(k, pad)
             dx = _conv_raw(dy[0], w_a, 1, None, None, Ci, k, dpad, (D, H, W))
             dx = _conv_raw(dy[1], w_b, 1, None, dx, Ci, k, dpad, (D, H, W), out=dx)
-        grads = []
         if (ctx.needs_input_grad[1] and ctx.needs_input_grad[2] and x.dtype == torch.bfloat16
                 and L.hupr_conv3x3_wgrad_halo_dual_supported(B, D, H, W, Ci, Co, k[0])):
             # both weight gradients read the same x: one launch over 2 Co output channels, one reduction (same sums as two calls)
@@ -552,16 +575,8 @@ class DualConvFn(torch.autograd.Function):
             rt.check(L.hupr_conv3x3_wgrad_halo_bf16act_dual(rt.ptr(x), rt.ptr(dy[0]), rt.ptr(dy[1]), rt.ptr(dwa), rt.ptr(dwb), B, D, H, W,
                                                             Ci, Ci, Co, Co, k[0], rt.ptr(ws), ws.numel(), rt.stream()))
             return dx, _pret(w_a, dwa, da), _pret(w_b, dwb, db_), None, None, None
-        for i, w in enumerate((w_a, w_b)):
-            if not ctx.needs_input_grad[1 + i]:
-                grads.append(None)
-                continue
-            dw, direct = _pgrad(w)
-            ws = workspace(L.hupr_conv3x3_wgrad_halo_ws_bytes(Ci, Co, k[0]), x.device)
-            fn = L.hupr_conv3x3_wgrad_halo_bf16act if x.dtype == torch.bfloat16 else L.hupr_conv3x3_wgrad_halo_bf16
-            rt.check(fn(rt.ptr(x), rt.ptr(dy[i]), rt.ptr(dw), B, D, H, W, Ci, Ci, Co, Co, k[0], rt.ptr(ws), ws.numel(),
-                        rt.stream()))
-            grads.append(_pret(w, dw, direct))
+        grads = [_pret(w, *_halo_wgrad(x, g, w)) if need else None
+                 for w, g, need in zip((w_a, w_b), dy, ctx.needs_input_grad[1:3])]
         return dx, grads[0], grads[1], None, None, None
 
 
@@ -617,8 +632,7 @@ def _tmerge_wgrad(x, dy, weight):
     dw, direct = _pgrad(weight)
     if TMERGE_STREAM and x.dtype == torch.bfloat16 and L.hupr_tmerge_wgrad_stream_supported(G, H * W, Ci, Co):
         ws = workspace(L.hupr_tmerge_wgrad_stream_ws_bytes(B, G, H * W, Ci, Co), x.device)
-        rt.check(L.hupr_tmerge_wgrad_stream_bf16(rt.ptr(x), rt.ptr(dy), rt.ptr(dw), B, G, H * W, Ci, Co, rt.ptr(ws), ws.numel(),
-                                                 rt.stream()))
+        rt.check(L.hupr_tmerge_wgrad_stream_bf16(rt.ptr(x), rt.ptr(dy), rt.ptr(dw), B, G, H * W, Ci, Co, rt.ptr(ws), ws.numel(), rt.stream()))
         return dw, direct
     ws = workspace(L.hupr_conv_wgrad_ws_bytes(B, 1, H, W, Ci, Co, G, 1, 1), x.device)
     rt.check(L.hupr_conv_wgrad_bf16_mixed(rt.ptr(x), int(x.dtype == torch.bfloat16), rt.ptr(dy), rt.ptr(dw), B, G, H, W, Ci, Ci, 1,
@@ -648,16 +662,11 @@ class TemporalMergeFn(torch.autograd.Function):
     def backward(ctx, dy):
         x, weight = ctx.saved_tensors
         dy = _c(dy)
-        B, G, H, W, Ci = _vox(x)
-        Co = weight.shape[0]
-        L = rt.lib()
-        dx = dw = None
-        direct = False
+        dx = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
             _tmerge_dgrad(dy, weight, dx)
-        if ctx.needs_input_grad[1]:
-            dw, direct = _tmerge_wgrad(x, dy, weight)
+        dw, direct = _tmerge_wgrad(x, dy, weight) if ctx.needs_input_grad[1] else (None, False)
         return dx, _pret(weight, dw, direct)
 
 
@@ -689,17 +698,13 @@ class MergeDownFn(torch.autograd.Function):
     def backward(ctx, d_merged, d_down):
         x, weight = ctx.saved_tensors
         B, G, H, W, Ci = _vox(x)
-        Co = weight.shape[0]
         Do, Ho, Wo = ctx.size
         L = rt.lib()
         d_merged, d_down = _c(d_merged), _c(d_down)
         dx = torch.empty_like(x)
         _tmerge_dgrad(d_merged, weight, dx)
         rt.check(L.hupr_interp_linear_bwd_acc_bf16act(rt.ptr(d_down), rt.ptr(dx), B, G, H, W, Do, Ho, Wo, Ci, Ci, Ci, rt.stream()))
-        dw = None
-        direct = False
-        if ctx.needs_input_grad[1]:
-            dw, direct = _tmerge_wgrad(x, d_merged, weight)
+        dw, direct = _tmerge_wgrad(x, d_merged, weight) if ctx.needs_input_grad[1] else (None, False)
         return dx, _pret(weight, dw, direct), None
 
 
@@ -720,42 +725,38 @@ def temporal_merge(x, weight):
 # ----------------------------------------------------------------------------------------------
 # BatchNorm (+ReLU), and the BasicBlock3D tail  relu(bn_a(x1) + bn_b(x2))
 # ----------------------------------------------------------------------------------------------
+def _bn_bump(bn):
+    """A training-mode pass updated ``bn``'s running statistics: its num_batches_tracked is due."""
+    if bn.running_mean is not None and bn.num_batches_tracked is not None:
+        if BN_COUNTER_SINK is not None:
+            BN_COUNTER_SINK.append(bn)          # the engine bumps all counters of a step with one launch
+        else:
+            bn.num_batches_tracked.add_(1)
+
+
 def _bn_params(x, bn, training, need_bwd=True):
     """-> (scale, shift, save_mean, save_invstd) for one nn.BatchNorm3d-like parameter holder."""
     L = rt.lib()
     C = x.shape[-1]
     M = x.numel() // C
-    dev = x.device
-    scale = torch.empty(C, dtype=torch.float32, device=dev)
-    shift = torch.empty_like(scale)
-    mean = torch.empty_like(scale)
-    invstd = torch.empty_like(scale)
+    scale, shift, mean, invstd = [torch.empty(C, dtype=torch.float32, device=x.device) for _ in range(4)]
     fused = _conv_stats.pop(x.data_ptr(), None)
     if fused is not None and not (training and fused[2] == M and fused[3] == C):
         fused = None
-    if training:
-        track = bn.running_mean is not None
+    if training:            # (the running statistics are null pointers where the module does not track them)
         if fused is not None:           # the producing convolution left the column sums: finalize only
             rt.check(L.hupr_bn_train_finalize_f32(
-                rt.ptr(fused[0]), fused[1], M, C, rt.ptr(bn.weight), rt.ptr(bn.bias),
-                rt.ptr(bn.running_mean) if track else None, rt.ptr(bn.running_var) if track else None,
+                rt.ptr(fused[0]), fused[1], M, C, rt.ptr(bn.weight), rt.ptr(bn.bias), rt.ptr(bn.running_mean), rt.ptr(bn.running_var),
                 float(bn.momentum), float(bn.eps), rt.ptr(mean), rt.ptr(invstd), rt.ptr(scale), rt.ptr(shift), rt.stream()))
         else:
-            ws = workspace(L.hupr_bn_ws_bytes(C), dev)
+            ws = workspace(L.hupr_bn_ws_bytes(C), x.device)
             rt.check(_act("bn_train_stats", x)(
-                rt.ptr(x), M, C, rt.ptr(bn.weight), rt.ptr(bn.bias),
-                rt.ptr(bn.running_mean) if track else None, rt.ptr(bn.running_var) if track else None,
-                float(bn.momentum), float(bn.eps), rt.ptr(mean), rt.ptr(invstd), rt.ptr(scale), rt.ptr(shift),
-                rt.ptr(ws), ws.numel(), rt.stream()))
-        if track and bn.num_batches_tracked is not None:
-            if BN_COUNTER_SINK is not None:
-                BN_COUNTER_SINK.append(bn)          # the engine bumps all counters of a step with one launch
-            else:
-                bn.num_batches_tracked.add_(1)
+                rt.ptr(x), M, C, rt.ptr(bn.weight), rt.ptr(bn.bias), rt.ptr(bn.running_mean), rt.ptr(bn.running_var), float(bn.momentum),
+                float(bn.eps), rt.ptr(mean), rt.ptr(invstd), rt.ptr(scale), rt.ptr(shift), rt.ptr(ws), ws.numel(), rt.stream()))
+        _bn_bump(bn)
     else:
-        rt.check(L.hupr_bn_eval_params_f32(rt.ptr(bn.weight), rt.ptr(bn.bias), rt.ptr(bn.running_mean),
-                                           rt.ptr(bn.running_var), float(bn.eps), C, rt.ptr(scale),
-                                           rt.ptr(shift), rt.stream()))
+        rt.check(L.hupr_bn_eval_params_f32(rt.ptr(bn.weight), rt.ptr(bn.bias), rt.ptr(bn.running_mean), rt.ptr(bn.running_var),
+                                           float(bn.eps), C, rt.ptr(scale), rt.ptr(shift), rt.stream()))
         if need_bwd:                         # only a backward pass through eval-mode statistics reads these two
             mean.copy_(bn.running_mean)
             invstd = torch.rsqrt(bn.running_var + bn.eps)
@@ -777,15 +778,9 @@ def _bn_params_pair(x1, bn1, x2, bn2):
     out = [[torch.empty(C, dtype=torch.float32, device=dev) for _ in range(4)] for _ in range(2)]      # scale, shift, mean, invstd
     args = []
     for f, bn, (scale, shift, mean, invstd) in ((f1, bn1, out[0]), (f2, bn2, out[1])):
-        track = bn.running_mean is not None
-        args += [rt.ptr(f[0]), f[1], rt.ptr(bn.weight), rt.ptr(bn.bias), rt.ptr(bn.running_mean) if track else None,
-                 rt.ptr(bn.running_var) if track else None, float(bn.momentum), float(bn.eps), rt.ptr(mean), rt.ptr(invstd),
-                 rt.ptr(scale), rt.ptr(shift)]
-        if track and bn.num_batches_tracked is not None:
-            if BN_COUNTER_SINK is not None:
-                BN_COUNTER_SINK.append(bn)
-            else:
-                bn.num_batches_tracked.add_(1)
+        args += [rt.ptr(f[0]), f[1], rt.ptr(bn.weight), rt.ptr(bn.bias), rt.ptr(bn.running_mean), rt.ptr(bn.running_var),
+                 float(bn.momentum), float(bn.eps), rt.ptr(mean), rt.ptr(invstd), rt.ptr(scale), rt.ptr(shift)]
+        _bn_bump(bn)
     rt.check(rt.lib().hupr_bn_train_finalize2_f32(*args, M, C, rt.stream()))
     return tuple(out[0]), tuple(out[1])
 
@@ -813,6 +808,26 @@ def _bn_bwd(dy, x, mean, invstd, gamma, training, beta=None, fwd=None):
     return dx, _pret(gamma, dg, dg_direct), _pret(beta, db, db_direct)
 
 
+def _bn_eval_act(x1, bn1, relu, x2=None, bn2=None):
+    """Inference: y = [relu](bn1(x1) [+ bn2(x2)]) on running statistics, coefficients and apply in one launch."""
+    assert x2 is None or x1.dtype == x2.dtype
+    C = x1.shape[-1]
+    y = torch.empty_like(x1)
+    rt.check(_act("bn_eval_act", x1)(rt.ptr(x1), *_bn_eval_args(bn1), rt.ptr(x2), *_bn_eval_args(bn2), rt.ptr(y), x1.numel() // C, C,
+                                     1 if relu else 0, rt.stream()))
+    return y
+
+
+def _scale_shift_act(x1, s1, t1, relu, x2=None, s2=None, t2=None):
+    """y = [relu](s1 x1 + t1 [+ s2 x2 + t2]) with per-channel coefficients."""
+    assert x2 is None or x1.dtype == x2.dtype
+    C = x1.shape[-1]
+    y = torch.empty_like(x1)
+    rt.check(_act("scale_shift_act", x1)(rt.ptr(x1), rt.ptr(s1), rt.ptr(t1), rt.ptr(x2), rt.ptr(s2), rt.ptr(t2), rt.ptr(y),
+                                         x1.numel() // C, C, 1 if relu else 0, rt.stream()))
+    return y
+
+
 @_math_scoped
 class BNActFn(torch.autograd.Function):
     """y = [relu](batch_norm(x)).  ``bn`` is the parameter holder (running stats updated in place)."""
@@ -822,17 +837,10 @@ class BNActFn(torch.autograd.Function):
         # no_bwd: the caller runs under torch.no_grad() (grad mode is always off in here, and needs_input_grad reflects the
         # tensors' flags whatever the mode) — eval-mode statistics then skip what only a backward pass reads
         x = _c(x)
-        C = x.shape[-1]
-        if no_bwd and not training:          # inference: coefficients and apply in one launch
-            y = torch.empty_like(x)
-            rt.check(_act("bn_eval_act", x)(rt.ptr(x), rt.ptr(bn.weight), rt.ptr(bn.bias), rt.ptr(bn.running_mean),
-                                            rt.ptr(bn.running_var), float(bn.eps), None, None, None, None, None, 0.0, rt.ptr(y),
-                                            x.numel() // C, C, 1 if relu else 0, rt.stream()))
-            return y
+        if no_bwd and not training:
+            return _bn_eval_act(x, bn, relu)
         scale, shift, mean, invstd = _bn_params(x, bn, training, not no_bwd)
-        y = torch.empty_like(x)
-        rt.check(_act("scale_shift_act", x)(rt.ptr(x), rt.ptr(scale), rt.ptr(shift), None, None, None,
-                                            rt.ptr(y), x.numel() // C, C, 1 if relu else 0, rt.stream()))
+        y = _scale_shift_act(x, scale, shift, relu)
         ctx.save_for_backward(x, mean, invstd, gamma, scale if relu else None, shift if relu else None)
         ctx.beta_ref = beta
         ctx.training = training
@@ -853,26 +861,15 @@ class BNAddBNReLUFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x1, g1, b1, bn1, x2, g2, b2, bn2, training, no_bwd=False):
         x1, x2 = _c(x1), _c(x2)
-        if no_bwd and not training:          # inference: both coefficient sets and the apply in one launch
-            assert x1.dtype == x2.dtype
-            C = x1.shape[-1]
-            y = torch.empty_like(x1)
-            rt.check(_act("bn_eval_act", x1)(rt.ptr(x1), rt.ptr(bn1.weight), rt.ptr(bn1.bias), rt.ptr(bn1.running_mean),
-                                             rt.ptr(bn1.running_var), float(bn1.eps), rt.ptr(x2), rt.ptr(bn2.weight),
-                                             rt.ptr(bn2.bias), rt.ptr(bn2.running_mean), rt.ptr(bn2.running_var), float(bn2.eps),
-                                             rt.ptr(y), x1.numel() // C, C, 1, rt.stream()))
-            return y
+        if no_bwd and not training:
+            return _bn_eval_act(x1, bn1, True, x2, bn2)
         pair = _bn_params_pair(x1, bn1, x2, bn2) if training else None
         if pair is not None:
             (s1, t1, m1, i1), (s2, t2, m2, i2) = pair
         else:
             s1, t1, m1, i1 = _bn_params(x1, bn1, training, not no_bwd)
             s2, t2, m2, i2 = _bn_params(x2, bn2, training, not no_bwd)
-        C = x1.shape[-1]
-        y = torch.empty_like(x1)
-        assert x1.dtype == x2.dtype
-        rt.check(_act("scale_shift_act", x1)(rt.ptr(x1), rt.ptr(s1), rt.ptr(t1), rt.ptr(x2), rt.ptr(s2),
-                                             rt.ptr(t2), rt.ptr(y), x1.numel() // C, C, 1, rt.stream()))
+        y = _scale_shift_act(x1, s1, t1, True, x2, s2, t2)
         ctx.save_for_backward(x1, x2, m1, i1, g1, m2, i2, g2, s1, t1, s2, t2)
         ctx.beta_refs = (b1, b2)
         ctx.training = training
@@ -889,10 +886,7 @@ class BNAddBNReLUFn(torch.autograd.Function):
         assert dy.dtype == x1.dtype == x2.dtype
         dx1, dx2 = torch.empty_like(x1), torch.empty_like(x2)
         b1, b2 = ctx.beta_refs
-        dg1, dg1_d = _pgrad(g1)
-        db1, db1_d = _pgrad(b1)
-        dg2, dg2_d = _pgrad(g2)
-        db2, db2_d = _pgrad(b2)
+        (dg1, dg1_d), (db1, db1_d), (dg2, dg2_d), (db2, db2_d) = _pgrad(g1), _pgrad(b1), _pgrad(g2), _pgrad(b2)
         ws = workspace(L.hupr_bn_ws_bytes(C), x1.device)
         # ReLU mask recomputed from x1, x2 and the forward coefficients
         rt.check(_act("bn_bwd2_remask", x1)(rt.ptr(dy), rt.ptr(x1), rt.ptr(s1), rt.ptr(t1), rt.ptr(m1), rt.ptr(i1), rt.ptr(g1),
@@ -959,7 +953,7 @@ class MNetFn(torch.autograd.Function):
         need = weight.requires_grad or bias.requires_grad
         means = torch.empty((B * G, R * A, 16), dtype=torch.float32, device=x.device) if need else None
         rt.check(_act("mnet_fwd_means" if from_means else "mnet_fwd", out)(
-            rt.ptr(x), rt.ptr(_c(weight)), rt.ptr(bias), rt.ptr(out), rt.ptr(means) if need else None, B * G, R * A, rt.stream()))
+            rt.ptr(x), rt.ptr(_c(weight)), rt.ptr(bias), rt.ptr(out), rt.ptr(means), B * G, R * A, rt.stream()))
         ctx.save_for_backward(means, weight, bias)
         ctx.geom = (B, G, R, A)
         return out
@@ -1026,7 +1020,7 @@ class JoinFn(torch.autograd.Function):
     """The decoder's channel concatenation (reference models/layers.py:166-178) without a copy: the parts were WRITTEN as adjacent
     channel slices of ``wide`` by their producers (InterpFn / MSCSALevelFn with an output placement), so the forward just hands
     ``wide`` on, and the backward hands each producer its slice of the gradient (views; the producers' backward kernels read them in
-    place).  Rounds 1-4 paid a concatenation kernel per decoder stage and two ``contiguous`` copies of gradient slices per step."""
+    place)."""
 
     @staticmethod
     def forward(ctx, wide, *parts):
@@ -1064,10 +1058,8 @@ def _cast(x, dtype):
     if x.dtype == dtype:
         return x
     y = torch.empty(x.shape, dtype=dtype, device=x.device)
-    if dtype == torch.bfloat16:
-        rt.check(rt.lib().hupr_cast_f32_to_bf16(rt.ptr(x), rt.ptr(y), x.numel(), rt.stream()))
-    else:
-        rt.check(rt.lib().hupr_cast_bf16_to_f32(rt.ptr(x), rt.ptr(y), x.numel(), rt.stream()))
+    fn = rt.lib().hupr_cast_f32_to_bf16 if dtype == torch.bfloat16 else rt.lib().hupr_cast_bf16_to_f32
+    rt.check(fn(rt.ptr(x), rt.ptr(y), x.numel(), rt.stream()))
     return y
 
 
@@ -1102,9 +1094,8 @@ def gemm(ta, tb, A, B, M, N, K, lda, ldb, batch, a_bs, b_bs, out=None, res=None,
     if out is None:
         out = torch.empty((batch, M, N), dtype=torch.float32, device=A.device)
     fn = _fn("gemm") if math is None else getattr(rt.lib(), "hupr_gemm_%s" % math)
-    rt.check(fn(ta, tb, rt.ptr(A), rt.ptr(B), rt.ptr(out), M, N, K, lda, ldb, N, batch, a_bs, b_bs,
-                                   M * N, rt.ptr(res) if res is not None else None, N, M * N if res is not None else 0,
-                                   1 if accumulate else 0, rt.stream()))
+    rt.check(fn(ta, tb, rt.ptr(A), rt.ptr(B), rt.ptr(out), M, N, K, lda, ldb, N, batch, a_bs, b_bs, M * N, rt.ptr(res), N,
+                M * N if res is not None else 0, 1 if accumulate else 0, rt.stream()))
     return out
 
 
@@ -1112,6 +1103,32 @@ def _attn_ws(B, N, C, device):
     """Workspace of the split-key forward (small batches: the plain grid would leave most CUs idle), or None."""
     nbytes = rt.lib().hupr_attn_fwd_split_ws_bytes(B, N, C)
     return workspace(nbytes, device) if nbytes else None
+
+
+# The GEMM / row-softmax attention core, shared by AttentionFn (``dense``: K, Q, dK, dQ are (B, N, C) tensors; ``fn`` follows the math
+# mode) and MSCSALevelFn (column blocks of the (B, N, 4C) projections and of their gradient; always the bf16 pipe).  kp / qp / dkp / dqp / g
+# are raw pointers, the rest dense fp32 tensors.  (``nl``: the ignored leading dimension beside a NULL residual, as each caller spells it.)
+def _attn_gemm_fwd(fn, dense, kp, qp, v, vres, P, out, B, N, C):
+    """P[q][j] = Q[q] . K[j], softmax over the keys j (a row softmax), out = P V (+ vres)."""
+    ld, nl = (C, 1) if dense else (4 * C, 0)
+    rt.check(fn(0, 1, qp, kp, rt.ptr(P), N, N, C, ld, ld, N, B, N * ld, N * ld, N * N, None, nl * N, 0, 0, rt.stream()))
+    rt.check(rt.lib().hupr_softmax_rows_f32(rt.ptr(P), B * N, N, rt.stream()))
+    rt.check(fn(0, 0, rt.ptr(P), rt.ptr(v), rt.ptr(out), N, C, N, N, C, C, B, N * N, N * C, N * C, rt.ptr(vres), C,
+                N * C if vres is not None else 0, 0, rt.stream()))
+
+
+def _attn_gemm_bwd(fn, dense, kp, qp, v, P, g, residual, accumulate, dv, dS, dkp, dqp, B, N, C):
+    """Backward of ``_attn_gemm_fwd`` from the output gradient at ``g``; dS (B, N, N) is scratch."""
+    ld, nl = (C, 1) if dense else (4 * C, 0)
+    # dV[j] = sum_q P[q][j] dout[q]  (+ dout: residual form; ``accumulate``: added onto the dV already there)
+    rt.check(fn(1, 0, rt.ptr(P), g, rt.ptr(dv), N, C, N, N, C, C, B, N * N, N * C, N * C, g if residual else None, C,
+                N * C if residual else 0, 1 if accumulate else 0, rt.stream()))
+    # dP[q][j] = dout[q] . V[j]; dS = softmax backward in place
+    rt.check(fn(0, 1, g, rt.ptr(v), rt.ptr(dS), N, N, C, C, C, N, B, N * C, N * C, N * N, None, nl * N, 0, 0, rt.stream()))
+    rt.check(rt.lib().hupr_softmax_rows_bwd_f32(rt.ptr(P), rt.ptr(dS), B * N, N, rt.stream()))
+    # dQ[q] = sum_j dS[q][j] K[j];  dK[j] = sum_q dS[q][j] Q[q]
+    rt.check(fn(0, 0, rt.ptr(dS), kp, dqp, N, C, N, N, ld, ld, B, N * N, N * ld, N * ld, None, nl * C, 0, 0, rt.stream()))
+    rt.check(fn(1, 0, rt.ptr(dS), qp, dkp, N, C, N, N, ld, ld, B, N * N, N * ld, N * ld, None, nl * C, 0, 0, rt.stream()))
 
 
 @_math_scoped
@@ -1125,6 +1142,7 @@ class AttentionFn(torch.autograd.Function):
         B, N, C = v.shape
         L = rt.lib()
         ctx.flash = _st.math == "bf16" and USE_FLASH and bool(L.hupr_attn_flash_supported(N, C))
+        ctx.residual = residual
         if ctx.flash:
             out = torch.empty_like(v)
             lse = torch.empty((B, N), dtype=torch.float32, device=v.device)
@@ -1133,59 +1151,47 @@ class AttentionFn(torch.autograd.Function):
             kb, qb, vb = _cast(k, torch.bfloat16), _cast(q, torch.bfloat16), _cast(v, torch.bfloat16)
             ws = _attn_ws(B, N, C, v.device)
             rt.check(L.hupr_attn_fwd_bf16in_ld_ws(rt.ptr(kb), C, rt.ptr(qb), C, rt.ptr(vb), rt.ptr(v) if residual else None,
-                                                  rt.ptr(out), rt.ptr(lse), None, 0, B, N, C, rt.ptr(ws) if ws is not None else None,
-                                                  ws.numel() if ws is not None else 0, rt.stream()))
+                                                  rt.ptr(out), rt.ptr(lse), None, 0, B, N, C, *_ws_args(ws), rt.stream()))
             ctx.save_for_backward(kb, qb, vb, v, out, lse)
-            ctx.residual = residual
             return out
-        # St[kq][j] = q . k  -> softmax over j is a row softmax
-        P = gemm(0, 1, q, k, N, N, C, C, C, B, N * C, N * C)
-        rt.check(L.hupr_softmax_rows_f32(rt.ptr(P), B * N, N, rt.stream()))
-        out = gemm(0, 0, P, v, N, C, N, N, C, B, N * N, N * C, res=v if residual else None)
+        P = torch.empty((B, N, N), dtype=torch.float32, device=v.device)
+        out = torch.empty((B, N, C), dtype=torch.float32, device=v.device)
+        _attn_gemm_fwd(_fn("gemm"), True, rt.ptr(k), rt.ptr(q), v, v if residual else None, P, out, B, N, C)
         ctx.save_for_backward(k, q, v, P)
-        ctx.residual = residual
         return out
 
     @staticmethod
     def backward(ctx, dout):
+        dout = _c(dout)
         if ctx.flash:
             kb, qb, vb, v, out, lse = ctx.saved_tensors
-            dout = _c(dout)
             B, N, C = v.shape
             dk, dq, dv = torch.empty_like(v), torch.empty_like(v), torch.empty_like(v)
             dq_scr = torch.empty((B, N), dtype=torch.float32, device=v.device)
             gb = _cast(dout, torch.bfloat16)
-            rt.check(rt.lib().hupr_attn_bwd_bf16in(rt.ptr(kb), rt.ptr(qb), rt.ptr(vb), rt.ptr(gb), rt.ptr(v), rt.ptr(out),
-                                                  rt.ptr(dout), rt.ptr(lse), rt.ptr(dk), rt.ptr(dq), rt.ptr(dv),
-                                                  rt.ptr(dq_scr), B, N, C, 1 if ctx.residual else 0, rt.stream()))
+            rt.check(rt.lib().hupr_attn_bwd_bf16in(rt.ptr(kb), rt.ptr(qb), rt.ptr(vb), rt.ptr(gb), rt.ptr(v), rt.ptr(out), rt.ptr(dout),
+                                                  rt.ptr(lse), rt.ptr(dk), rt.ptr(dq), rt.ptr(dv), rt.ptr(dq_scr), B, N, C,
+                                                  1 if ctx.residual else 0, rt.stream()))
             return dk, dq, dv, None
         k, q, v, P = ctx.saved_tensors
-        dout = _c(dout)
         B, N, C = v.shape
-        L = rt.lib()
-        # dV[j][c] = sum_kq P[kq][j] dout[kq][c]  (+ dout for the residual path)
-        dv = gemm(1, 0, P, dout, N, C, N, N, C, B, N * N, N * C, res=dout if ctx.residual else None)
-        # dP[kq][j] = sum_c dout[kq][c] v[j][c]
-        dS = gemm(0, 1, dout, v, N, N, C, C, C, B, N * C, N * C)
-        rt.check(L.hupr_softmax_rows_bwd_f32(rt.ptr(P), rt.ptr(dS), B * N, N, rt.stream()))
-        dq = gemm(0, 0, dS, k, N, C, N, N, C, B, N * N, N * C)      # dQ[kq][c] = sum_j dS[kq][j] k[j][c]
-        dk = gemm(1, 0, dS, q, N, C, N, N, C, B, N * N, N * C)      # dK[j][c] = sum_kq dS[kq][j] q[kq][c]
+        dv, dS, dq, dk = [torch.empty(s, dtype=torch.float32, device=v.device) for s in ((B, N, C), (B, N, N), (B, N, C), (B, N, C))]
+        _attn_gemm_bwd(_fn("gemm"), True, rt.ptr(k), rt.ptr(q), v, P, rt.ptr(dout), ctx.residual, False, dv, dS, rt.ptr(dk), rt.ptr(dq),
+                       B, N, C)
         return dk, dq, dv, None
 
 
 _level_cat_out = {}      # {"out": view}: where the NEXT fused level writes its concatenated bf16 output (models/layers.py sets it)
 CAT_FUSION = True          # fused levels return their maps concatenated as bf16
 PROJ_STREAM = True         # test aid: False = the level's projections through the generic implicit-GEMM engine
+CAT_INPLACE = True         # test aid: False = concatenation copies per decoder stage
+ATTN_BATCH = True          # test aid: False = one launch pair per attention in single-sample inference
 
 
 def mscsa_level_fused_ok(ra):
     """One MSCSA level can run as MSCSALevelFn (bf16 math; any (N, C) — shapes without a fused attention kernel keep the
     GEMM / row-softmax attention core inside the node)."""
-    B, _, H, W, C = ra.shape
-    return _st.math == "bf16" and ra.dtype == torch.float32 and C % 8 == 0
-
-
-CAT_INPLACE = True         # test aid: False = concatenation copies per decoder stage
+    return _st.math == "bf16" and ra.dtype == torch.float32 and ra.shape[-1] % 8 == 0
 
 
 def level_cat_placement_ok(ra):
@@ -1194,7 +1200,135 @@ def level_cat_placement_ok(ra):
     return CAT_INPLACE and mscsa_level_fused_ok(ra) and USE_FLASH and CAT_FUSION and bool(rt.lib().hupr_attn_flash_supported(H * W, C))
 
 
-ATTN_BATCH = True          # test aid: False = one launch pair per attention in single-sample inference
+def _level_blocks(Y, C):
+    """[(K pointer, Q pointer)] of the four attentions: column blocks (width C) of the two (B, N, 4C) tensors ``Y`` — the projections, or
+    their gradient (dK / dQ).  The one place that does this arithmetic."""
+    step = C * Y[0].element_size()
+    return [(Y[ks].data_ptr() + kslot * step, Y[qs].data_ptr() + qslot * step) for ks, kslot, qs, qslot, _, _ in MSCSALevelFn.SPEC]
+
+
+def _level_project(x, wc, y, flash):
+    """The four projections of map ``x`` (B,1,H,W,C) fp32 as one product with wc (4C, C) -> y (B, N, 4C), bf16 for the fused
+    attention kernels (``flash``), else fp32.  (A 1x1 kernel's packed layout IS the parameter layout (Co, Ci).)"""
+    B, _, H, W, C = x.shape
+    L = rt.lib()
+    if flash and PROJ_STREAM and L.hupr_mscsa_proj_supported(B * H * W, C):
+        # one HBM-bound streaming product (csrc/projection.hip)
+        rt.check(L.hupr_mscsa_proj_fwd_bf16(rt.ptr(x), rt.ptr(wc), rt.ptr(y), B * H * W, C, rt.stream()))
+        return
+    rt.check(L.hupr_conv_fwd_bf16_mixed(rt.ptr(x), 0, rt.ptr(wc), None, rt.ptr(y), 1 if flash else 0, B, 1, H, W, C, C,
+                                        1, H, W, 4 * C, 4 * C, 1, 1, 1, 0, 0, 0, rt.stream()))
+
+
+def _level_fwd_flash(tab, ld16, qscaled, infer, B, N, C, dev):
+    """The four attentions on the fused kernels.  ``tab`` rows: (K ptr, Q ptr, V bf16, V residual fp32 | None, out, log-sum-exp,
+    bf16 cat slice ptr | None)."""
+    L = rt.lib()
+    # single-sample inference (config C2): the four attentions of the level as ONE split launch + ONE merge launch instead of eight
+    split_ws = L.hupr_attn_fwd_split_ws_bytes(B, N, C)       # (> 0: the key-split form applies to this batch)
+    split_bytes = split_ws if (infer and ATTN_BATCH) else 0
+    # training batches, levels 2 and 3 (C = 128 / 256: one attention's grid is 256 / 64 workgroups): the four as ONE launch of the
+    # one-pass kernel (not where the single-sample split form applies: its shares round differently)
+    if split_bytes or (ATTN_LEVEL_BATCH and not split_ws and C != 64):
+        items = (rt.AttnItem * 4)()
+        for it, (kp, qp, v16, vres, out, lse, out16) in zip(items, tab):
+            it.K, it.Q, it.V, it.Vres = kp, qp, rt.ptr(v16), rt.ptr(vres)
+            it.out, it.lse, it.out16 = rt.ptr(out), rt.ptr(lse), out16
+        ws = workspace(4 * split_bytes, dev) if split_bytes else None
+        fwd = L.hupr_attn_fwd_bf16in_ld_ws_batch_qs if qscaled else L.hupr_attn_fwd_bf16in_ld_ws_batch
+        rt.check(fwd(items, 4, 4 * C, 4 * C, ld16, B, N, C, *_ws_args(ws), rt.stream()))
+        return
+    fwd = L.hupr_attn_fwd_bf16in_ld_ws_qs if qscaled else L.hupr_attn_fwd_bf16in_ld_ws
+    for kp, qp, v16, vres, out, lse, out16 in tab:
+        ws = _attn_ws(B, N, C, dev)
+        ev = _probe_begin(ATTN_PROBE, "fwd", B, N, C)
+        rt.check(fwd(kp, 4 * C, qp, 4 * C, rt.ptr(v16), rt.ptr(vres), rt.ptr(out), rt.ptr(lse), out16, ld16, B, N, C, *_ws_args(ws),
+                     rt.stream()))
+        _probe_end(ev)
+
+
+def _level_bwd_flash(tab, dcat, ld, douts, qscaled, scr, B, N, C):
+    """Backward of ``_level_fwd_flash``.  ``tab`` rows: (K ptr, Q ptr, V bf16, V fp32, out, log-sum-exp, dK ptr, dQ ptr, dV, residual);
+    the output gradients are the four column blocks of ``dcat`` (bf16, row stride ``ld``) or, without it, the fp32 ``douts``."""
+    L = rt.lib()
+    if dcat is not None and ATTN_LEVEL_BATCH:
+        # row sums and dQ of the four attentions in one launch each; dK / dV: levels 2 and 3 in two launches of two (the residual
+        # attentions of the two maps, then the two that add onto their dV) — 4 launches instead of 12, grids four / two times as
+        # large; level 1 one launch per attention (12 -> 6 launches)
+        scr4 = torch.empty((4, B, N), dtype=torch.float32, device=dcat.device)
+        items = (rt.AttnBwdItem * 4)()
+        for i, (it, (kp, qp, v16, v32, out, lse, dkp, dqp, dv, residual)) in enumerate(zip(items, tab)):
+            it.K, it.Q, it.V, it.dO = kp, qp, rt.ptr(v16), dcat.data_ptr() + i * C * 2
+            it.V32, it.out, it.lse = rt.ptr(v32), rt.ptr(out), rt.ptr(lse)
+            it.dK, it.dQ, it.dV, it.Dq = dkp, dqp, rt.ptr(dv), scr4.data_ptr() + i * B * N * 4
+            it.residual, it.accumulate = (1, 0) if residual else (0, 1)
+        bwd = L.hupr_attn_bwd_bf16in_ld_batch_qs if qscaled else L.hupr_attn_bwd_bf16in_ld_batch
+        ev = _probe_begin(ATTN_PROBE, "bwd_level", B, N, C)
+        rt.check(bwd(items, 4, 4 * C, 4 * C, ld, 4 * C, 4 * C, B, N, C, rt.stream()))
+        _probe_end(ev)
+        return
+    bwd = L.hupr_attn_bwd_bf16in_ld_qs if qscaled else L.hupr_attn_bwd_bf16in_ld
+    for i, ((kp, qp, v16, v32, out, lse, dkp, dqp, dv, residual), dout) in enumerate(zip(tab, douts)):
+        if dcat is not None:
+            gp, ldg, g32 = dcat.data_ptr() + i * C * 2, ld, None
+        else:
+            dout = _c(dout)
+            gb = _cast(dout, torch.bfloat16)
+            gp, ldg, g32 = rt.ptr(gb), C, rt.ptr(dout)
+        ev = _probe_begin(ATTN_PROBE, "bwd", B, N, C)
+        rt.check(bwd(kp, 4 * C, qp, 4 * C, rt.ptr(v16), gp, ldg, rt.ptr(v32), rt.ptr(out), g32, rt.ptr(lse), dkp, 4 * C, dqp, 4 * C,
+                     rt.ptr(dv), rt.ptr(scr), B, N, C, 1 if residual else 0, 0 if residual else 1, rt.stream()))
+        _probe_end(ev)
+
+
+def _level_map_grads(need, maps, dY, Wc, dV):
+    """Gradients of the two maps: dY . Wc (K = 4C) with the map's accumulated dV as the residual term."""
+    B, _, H, W, C = maps[0].shape
+    L = rt.lib()
+    grads = [None, None]
+    for i in range(2):
+        if not need[i]:
+            continue
+        dx = grads[i] = torch.empty_like(maps[i])
+        if PROJ_STREAM and L.hupr_mscsa_proj_dgrad_supported(B * H * W, C):
+            rt.check(L.hupr_mscsa_proj_dgrad_f32(rt.ptr(dY[i]), rt.ptr(Wc[i]), rt.ptr(dV[i]), rt.ptr(dx), B * H * W, C, rt.stream()))
+        else:
+            rt.check(L.hupr_gemm_bf16(0, 0, rt.ptr(dY[i]), rt.ptr(Wc[i]), rt.ptr(dx), B * H * W, C, 4 * C, 4 * C, C, C, 1, 0, 0, 0,
+                                      rt.ptr(dV[i]), C, 0, 0, rt.stream()))
+    return grads
+
+
+def _level_weight_grads(need, weights, maps, dY):
+    """The eight projection weight gradients as backward() return values: per map one split-K product maps[i]^T dY[i] -> (4C, C), landed
+    in the four parameters' gradients.  ``need``: needs_input_grad of the eight weights."""
+    B, _, H, W, C = maps[0].shape
+    L = rt.lib()
+    wgrads = [None] * 8
+    dsts, srcs, landed = [], [], []
+    for i in range(2):
+        if not any(need[4 * i:4 * i + 4]):
+            continue
+        ws4 = weights[4 * i:4 * i + 4]
+        got = [_pgrad(w) if need[4 * i + j] else (None, False) for j, w in enumerate(ws4)]
+        # the four gradient slots adjacent in their flat bucket, in this order (HuPRNet.gradient_groups -> GradientBuckets): the
+        # GEMM writes them in place — no (4C, C) temporary, no copy launch
+        inplace = all(g is not None and d for g, d in got) and all(
+            got[j][0].is_contiguous() and got[j][0].data_ptr() == got[0][0].data_ptr() + j * C * C * 4 for j in range(4))
+        dWc = None if inplace else torch.empty((4 * C, C), dtype=torch.float32, device=maps[i].device)
+        ws = workspace(L.hupr_conv_wgrad_ws_bytes(B, 1, H, W, C, 4 * C, 1, 1, 1), maps[i].device)
+        rt.check(L.hupr_conv_wgrad_bf16(rt.ptr(maps[i]), rt.ptr(dY[i]), got[0][0].data_ptr() if inplace else rt.ptr(dWc), B, 1, H, W, C, C,
+                                        1, H, W, 4 * C, 4 * C, 1, 1, 1, 0, 0, 0, rt.ptr(ws), ws.numel(), rt.stream()))
+        for j, (w, (g, direct)) in enumerate(zip(ws4, got)):
+            if need[4 * i + j]:
+                if not inplace:
+                    dsts.append(g)
+                    srcs.append(dWc[j * C:(j + 1) * C].view_as(w))
+                landed.append((4 * i + j, w, g, direct))
+    if dsts:
+        torch._foreach_copy_(dsts, srcs)        # the eight row blocks of the two fused gradients in one launch
+    for slot, w, g, direct in landed:
+        wgrads[slot] = _pret(w, g, direct)
+    return wgrads
 
 
 @_math_scoped
@@ -1217,7 +1351,10 @@ class MSCSALevelFn(torch.autograd.Function):
     cat_bf16 (fused attention kernels only): return ONE bf16 tensor (B,1,H,W,4C) = cat(out1..out4) — the kernels write
     the bf16 copy the decoder concatenates next straight from their accumulators, and the backward reads the four
     column blocks of the incoming (possibly strided: a slice of the concatenation's gradient) bf16 gradient in place: no
-    cast or copy kernels on either side.  Otherwise: the four fp32 outputs."""
+    cast or copy kernels on either side.  Otherwise: the four fp32 outputs.
+
+    forward / backward build ONE operand table (a row per attention, SPEC order) and hand it to one attention core: the fused
+    kernels (``_level_fwd_flash`` / ``_level_bwd_flash`` choose batched, split-key or per-attention launches) or ``_attn_gemm_*``."""
 
     #            K source/slot, Q source/slot, V map (0: ra, 1: re), residual
     SPEC = ((0, 0, 1, 1, 0, True), (0, 2, 0, 3, 0, False), (1, 0, 0, 1, 1, True), (1, 2, 1, 3, 1, False))
@@ -1232,210 +1369,74 @@ class MSCSALevelFn(torch.autograd.Function):
         dev = ra.device
         flash = USE_FLASH and bool(L.hupr_attn_flash_supported(N, C))
         ydt = torch.bfloat16 if flash else torch.float32
-        esz = 2 if flash else 4
         maps = (ra, re)
         infer = bool(int(cat_bf16) & 2)                  # bit 1: the caller runs under no_grad (grad mode is always off in here)
-        cat_bf16 = bool(int(cat_bf16) & 1)
+        cat_bf16 = bool(int(cat_bf16) & 1) and flash
         # QS: the query projections leave the GEMM as log2(e) Q (rounded to bf16 once, like every projection), the attention kernels
         # take the exponent of 2 straight from the matrix pipe (csrc/attention_bf16.hip, kDeferBits)
-        qscaled = flash and QS_ATTN                  # (not `qs`: the SPEC loops below bind that name to the query source map)
+        qscaled = flash and QS_ATTN
         pa, pe = _proj_cat(weights[:4], C), _proj_cat(weights[4:], C)
         Wc = (pa[0], pe[0])                              # plain: the backward GEMMs
         Wf = (pa[1], pe[1]) if qscaled else Wc                # what the forward projections multiply by
         Y = (torch.empty((B, N, 4 * C), dtype=ydt, device=dev), torch.empty((B, N, 4 * C), dtype=ydt, device=dev))
-        for x, wc, y in zip(maps, Wf, Y):          # a 1x1 kernel's packed layout IS the parameter layout (Co, Ci)
-            if flash and PROJ_STREAM and L.hupr_mscsa_proj_supported(B * N, C):
-                # the four projections of the map as one HBM-bound streaming product (csrc/projection.hip)
-                rt.check(L.hupr_mscsa_proj_fwd_bf16(rt.ptr(x), rt.ptr(wc), rt.ptr(y), B * N, C, rt.stream()))
-                continue
-            rt.check(L.hupr_conv_fwd_bf16_mixed(rt.ptr(x), 0, rt.ptr(wc), None, rt.ptr(y), 1 if flash else 0, B, 1, H, W, C, C,
-                                                1, H, W, 4 * C, 4 * C, 1, 1, 1, 0, 0, 0, rt.stream()))
+        for x, wc, y in zip(maps, Wf, Y):
+            _level_project(x, wc, y, flash)
         outs = [torch.empty((B, 1, H, W, C), dtype=torch.float32, device=dev) for _ in range(4)]
-        cat_bf16 = bool(cat_bf16) and flash
         cat, ld16 = None, 4 * C
         if cat_bf16:
             cat = _level_cat_out.pop("out", None)      # output placement: a channel slice of the decoder stage's input buffer
-            if cat is not None:
-                assert tuple(cat.shape) == (B, 1, H, W, 4 * C) and cat.dtype == torch.bfloat16 and _ld_view_ok(cat, 4 * C)
-                ld16 = cat.stride(3)
-            else:
+            if cat is None:
                 cat = torch.empty((B, 1, H, W, 4 * C), dtype=torch.bfloat16, device=dev)
+            assert tuple(cat.shape) == (B, 1, H, W, 4 * C) and cat.dtype == torch.bfloat16 and _ld_view_ok(cat, 4 * C)
+            ld16 = cat.stride(3)
         _level_cat_out.clear()
+        vb = (_cast(ra, torch.bfloat16), _cast(re, torch.bfloat16)) if flash else maps
+        # per attention: the log-sum-exp per query (fused kernels) or P[query][key]
+        aux = [torch.empty((B, N) if flash else (B, N, N), dtype=torch.float32, device=dev) for _ in range(4)]
+        tab = [(kp, qp, vb[vs], maps[vs] if residual else None, outs[i], aux[i], cat.data_ptr() + i * C * 2 if cat_bf16 else None)
+               for i, ((kp, qp), (_, _, _, _, vs, residual)) in enumerate(zip(_level_blocks(Y, C), MSCSALevelFn.SPEC))]
         if flash:
-            vb = (_cast(ra, torch.bfloat16), _cast(re, torch.bfloat16))
-            aux = [torch.empty((B, N), dtype=torch.float32, device=dev) for _ in range(4)]          # log-sum-exp per query
+            _level_fwd_flash(tab, ld16, qscaled, infer, B, N, C, dev)
         else:
-            vb = maps
-            aux = [torch.empty((B, N, N), dtype=torch.float32, device=dev) for _ in range(4)]       # P[query][key]
-        # single-sample inference (config C2): the four attentions of the level as ONE split launch + ONE merge launch instead of eight
-        split_ws = L.hupr_attn_fwd_split_ws_bytes(B, N, C) if flash else 0       # (> 0: the key-split form applies to this batch)
-        split_bytes = split_ws if (infer and ATTN_BATCH) else 0
-        # training batches, levels 2 and 3 (C = 128 / 256: one attention's grid is 256 / 64 workgroups): the four as ONE launch of the
-        # one-pass kernel (not where the single-sample split form applies: its shares round differently)
-        level_batch = flash and ATTN_LEVEL_BATCH and not split_ws and C != 64
-        if split_bytes or level_batch:
-            items = (rt.AttnItem * 4)()
-            for i, ((ks, kslot, qs, qslot, vs, residual), out, a) in enumerate(zip(MSCSALevelFn.SPEC, outs, aux)):
-                items[i].K, items[i].Q = Y[ks].data_ptr() + kslot * C * esz, Y[qs].data_ptr() + qslot * C * esz
-                items[i].V, items[i].Vres = rt.ptr(vb[vs]), (rt.ptr(maps[vs]) if residual else None)
-                items[i].out, items[i].lse = rt.ptr(out), rt.ptr(a)
-                items[i].out16 = (cat.data_ptr() + i * C * 2) if cat_bf16 else None
-            ws = workspace(4 * split_bytes, dev) if split_bytes else None
-            fwd_batch = L.hupr_attn_fwd_bf16in_ld_ws_batch_qs if qscaled else L.hupr_attn_fwd_bf16in_ld_ws_batch
-            rt.check(fwd_batch(items, 4, 4 * C, 4 * C, ld16, B, N, C, rt.ptr(ws) if ws is not None else None,
-                               ws.numel() if ws is not None else 0, rt.stream()))
-        for i, ((ks, kslot, qs, qslot, vs, residual), out, a) in enumerate(zip(MSCSALevelFn.SPEC, outs, aux)):
-            if split_bytes or level_batch:
-                break
-            kp, qp = Y[ks].data_ptr() + kslot * C * esz, Y[qs].data_ptr() + qslot * C * esz
-            if flash:
-                ws = _attn_ws(B, N, C, dev)
-                fwd = L.hupr_attn_fwd_bf16in_ld_ws_qs if qscaled else L.hupr_attn_fwd_bf16in_ld_ws
-                ev = ATTN_PROBE("fwd", B, N, C) if ATTN_PROBE is not None else None
-                if ev is not None:
-                    ev[0].record()
-                rt.check(fwd(kp, 4 * C, qp, 4 * C, rt.ptr(vb[vs]), rt.ptr(maps[vs]) if residual else None,
-                             rt.ptr(out), rt.ptr(a), cat.data_ptr() + i * C * 2 if cat_bf16 else None,
-                             ld16, B, N, C, rt.ptr(ws) if ws is not None else None,
-                             ws.numel() if ws is not None else 0, rt.stream()))
-                if ev is not None:
-                    ev[1].record()
-            else:
-                # P[q][j] = Q[q] . K[j], softmax over the keys j (row softmax), out = P V (+ V)
-                rt.check(L.hupr_gemm_bf16(0, 1, qp, kp, rt.ptr(a), N, N, C, 4 * C, 4 * C, N, B, N * 4 * C, N * 4 * C, N * N,
-                                          None, 0, 0, 0, rt.stream()))
-                rt.check(L.hupr_softmax_rows_f32(rt.ptr(a), B * N, N, rt.stream()))
-                v = maps[vs]
-                rt.check(L.hupr_gemm_bf16(0, 0, rt.ptr(a), rt.ptr(v), rt.ptr(out), N, C, N, N, C, C, B, N * N, N * C, N * C,
-                                          rt.ptr(v) if residual else None, C, N * C if residual else 0, 0, rt.stream()))
+            for kp, qp, v, vres, out, P, _ in tab:
+                _attn_gemm_fwd(L.hupr_gemm_bf16, False, kp, qp, v, vres, P, out, B, N, C)
         ctx.save_for_backward(ra, re, Wc[0], Wc[1], Y[0], Y[1], vb[0], vb[1], *outs, *aux)
         ctx.weights = weights
         ctx.flash, ctx.cat_bf16, ctx.qscaled = flash, cat_bf16, qscaled
-        if cat_bf16:
-            return (cat,)
-        return tuple(outs)
+        return (cat,) if cat_bf16 else tuple(outs)
 
     @staticmethod
     def backward(ctx, *douts):
         t = ctx.saved_tensors
         maps, Wc, Y, vb, outs, aux = t[0:2], t[2:4], t[4:6], t[6:8], t[8:12], t[12:16]
-        weights = ctx.weights
-        flash = ctx.flash
-        esz = 2 if flash else 4
         B, _, H, W, C = maps[0].shape
         N = H * W
-        L = rt.lib()
         dev = maps[0].device
         f32 = torch.float32
         dY = (torch.empty((B, N, 4 * C), dtype=f32, device=dev), torch.empty((B, N, 4 * C), dtype=f32, device=dev))
         dV = (torch.empty((B, N, C), dtype=f32, device=dev), torch.empty((B, N, C), dtype=f32, device=dev))
-        scr = torch.empty((B, N), dtype=f32, device=dev) if flash else torch.empty((B, N, N), dtype=f32, device=dev)
+        scr = torch.empty((B, N) if ctx.flash else (B, N, N), dtype=f32, device=dev)       # row sums / dS of one attention at a time
+        dcat, ld = None, 0
         if ctx.cat_bf16:
             # one bf16 gradient (B,1,H,W,4C), typically a column slice of the decoder input's gradient: read in place
-            dcat = douts[0]
+            dcat, douts = douts[0], (None,) * 4
             ld = dcat.stride(3)
             if not (dcat.dtype == torch.bfloat16 and dcat.stride(4) == 1 and dcat.stride(2) == W * ld and ld % 8 == 0
                     and (B == 1 or dcat.stride(0) == N * ld) and dcat.data_ptr() % 16 == 0):
-                dcat = _cast(dcat, torch.bfloat16)
-                ld = 4 * C
-            douts = [None] * 4
+                dcat, ld = _cast(dcat, torch.bfloat16), 4 * C
         # SPEC order: the residual attention of a map writes its dV, the other one adds to it
-        level_batch = flash and ctx.cat_bf16 and ATTN_LEVEL_BATCH
-        if level_batch:
-            # row sums and dQ of the four attentions in one launch each; dK / dV: levels 2 and 3 in two launches of two (the residual
-            # attentions of the two maps, then the two that add onto their dV) — 4 launches instead of 12, grids four / two times as
-            # large; level 1 one launch per attention (12 -> 6 launches)
-            scr4 = torch.empty((4, B, N), dtype=f32, device=dev)
-            items = (rt.AttnBwdItem * 4)()
-            for i, ((ks, kslot, qs, qslot, vs, residual), out, a) in enumerate(zip(MSCSALevelFn.SPEC, outs, aux)):
-                it = items[i]
-                it.K, it.Q = Y[ks].data_ptr() + kslot * C * esz, Y[qs].data_ptr() + qslot * C * esz
-                it.V, it.dO = rt.ptr(vb[vs]), dcat.data_ptr() + i * C * 2
-                it.V32, it.out, it.lse = rt.ptr(maps[vs]), rt.ptr(out), rt.ptr(a)
-                it.dK, it.dQ = dY[ks].data_ptr() + kslot * C * 4, dY[qs].data_ptr() + qslot * C * 4
-                it.dV, it.Dq = rt.ptr(dV[vs]), scr4.data_ptr() + i * B * N * 4
-                it.residual, it.accumulate = (1, 0) if residual else (0, 1)
-            bwd_batch = L.hupr_attn_bwd_bf16in_ld_batch_qs if ctx.qscaled else L.hupr_attn_bwd_bf16in_ld_batch
-            ev = ATTN_PROBE("bwd_level", B, N, C) if ATTN_PROBE is not None else None
-            if ev is not None:
-                ev[0].record()
-            rt.check(bwd_batch(items, 4, 4 * C, 4 * C, ld, 4 * C, 4 * C, B, N, C, rt.stream()))
-            if ev is not None:
-                ev[1].record()
-        for i, ((ks, kslot, qs, qslot, vs, residual), out, a, dout) in enumerate(zip(MSCSALevelFn.SPEC, outs, aux, douts)):
-            if level_batch:
-                break
-            kp, qp = Y[ks].data_ptr() + kslot * C * esz, Y[qs].data_ptr() + qslot * C * esz
-            dkp, dqp = dY[ks].data_ptr() + kslot * C * 4, dY[qs].data_ptr() + qslot * C * 4
-            if flash:
-                if ctx.cat_bf16:
-                    gp, ldg, g32 = dcat.data_ptr() + i * C * 2, ld, None
-                else:
-                    dout = _c(dout)
-                    gb = _cast(dout, torch.bfloat16)
-                    gp, ldg, g32 = rt.ptr(gb), C, rt.ptr(dout)
-                bwd = L.hupr_attn_bwd_bf16in_ld_qs if ctx.qscaled else L.hupr_attn_bwd_bf16in_ld
-                ev = ATTN_PROBE("bwd", B, N, C) if ATTN_PROBE is not None else None
-                if ev is not None:
-                    ev[0].record()
-                rt.check(bwd(kp, 4 * C, qp, 4 * C, rt.ptr(vb[vs]), gp, ldg, rt.ptr(maps[vs]),
-                             rt.ptr(out), g32, rt.ptr(a), dkp, 4 * C, dqp, 4 * C, rt.ptr(dV[vs]),
-                             rt.ptr(scr), B, N, C, 1 if residual else 0, 0 if residual else 1,
-                             rt.stream()))
-                if ev is not None:
-                    ev[1].record()
-                continue
-            dout = _c(dout)
-            v, P, g = maps[vs], a, rt.ptr(dout)
-            # dV[j] = sum_q P[q][j] dout[q]  (+ dout: residual form; else added onto the dV already there)
-            rt.check(L.hupr_gemm_bf16(1, 0, rt.ptr(P), g, rt.ptr(dV[vs]), N, C, N, N, C, C, B, N * N, N * C, N * C,
-                                      g if residual else None, C, N * C if residual else 0, 0 if residual else 1, rt.stream()))
-            # dP[q][j] = dout[q] . V[j]; dS = softmax backward in place
-            rt.check(L.hupr_gemm_bf16(0, 1, g, rt.ptr(v), rt.ptr(scr), N, N, C, C, C, N, B, N * C, N * C, N * N, None, 0, 0, 0,
-                                      rt.stream()))
-            rt.check(L.hupr_softmax_rows_bwd_f32(rt.ptr(P), rt.ptr(scr), B * N, N, rt.stream()))
-            # dQ[q] = sum_j dS[q][j] K[j];  dK[j] = sum_q dS[q][j] Q[q]   (into their column blocks)
-            rt.check(L.hupr_gemm_bf16(0, 0, rt.ptr(scr), kp, dqp, N, C, N, N, 4 * C, 4 * C, B, N * N, N * 4 * C, N * 4 * C,
-                                      None, 0, 0, 0, rt.stream()))
-            rt.check(L.hupr_gemm_bf16(1, 0, rt.ptr(scr), qp, dkp, N, C, N, N, 4 * C, 4 * C, B, N * N, N * 4 * C, N * 4 * C,
-                                      None, 0, 0, 0, rt.stream()))
-        grads = [None, None]
-        for i in range(2):
-            if ctx.needs_input_grad[i]:
-                dx = torch.empty_like(maps[i])
-                if PROJ_STREAM and L.hupr_mscsa_proj_dgrad_supported(B * N, C):
-                    rt.check(L.hupr_mscsa_proj_dgrad_f32(rt.ptr(dY[i]), rt.ptr(Wc[i]), rt.ptr(dV[i]), rt.ptr(dx), B * N, C, rt.stream()))
-                else:
-                    rt.check(L.hupr_gemm_bf16(0, 0, rt.ptr(dY[i]), rt.ptr(Wc[i]), rt.ptr(dx), B * N, C, 4 * C, 4 * C, C, C, 1, 0, 0,
-                                              0, rt.ptr(dV[i]), C, 0, 0, rt.stream()))
-                grads[i] = dx
-        wgrads = [None] * 8
-        dsts, srcs, landed = [], [], []
-        for i in range(2):
-            if not any(ctx.needs_input_grad[3 + 4 * i + j] for j in range(4)):
-                continue
-            ws4 = weights[4 * i:4 * i + 4]
-            got = [_pgrad(w) if ctx.needs_input_grad[3 + 4 * i + j] else (None, False) for j, w in enumerate(ws4)]
-            # the four gradient slots adjacent in their flat bucket, in this order (HuPRNet.gradient_groups -> GradientBuckets): the
-            # GEMM writes them in place — no (4C, C) temporary, no copy launch
-            inplace = all(g is not None and d for g, d in got) and all(
-                got[j][0].is_contiguous() and got[j][0].data_ptr() == got[0][0].data_ptr() + j * C * C * 4 for j in range(4))
-            dWc = None if inplace else torch.empty((4 * C, C), dtype=f32, device=dev)
-            ws = workspace(L.hupr_conv_wgrad_ws_bytes(B, 1, H, W, C, 4 * C, 1, 1, 1), dev)
-            rt.check(L.hupr_conv_wgrad_bf16(rt.ptr(maps[i]), rt.ptr(dY[i]), got[0][0].data_ptr() if inplace else rt.ptr(dWc), B, 1, H, W, C, C,
-                                            1, H, W, 4 * C, 4 * C, 1, 1, 1, 0, 0, 0, rt.ptr(ws), ws.numel(), rt.stream()))
-            for j in range(4):
-                w = ws4[j]
-                if ctx.needs_input_grad[3 + 4 * i + j]:
-                    g, direct = got[j]
-                    if not inplace:
-                        dsts.append(g)
-                        srcs.append(dWc[j * C:(j + 1) * C].view_as(w))
-                    landed.append((4 * i + j, w, g, direct))
-        if dsts:
-            torch._foreach_copy_(dsts, srcs)        # the eight row blocks of the two fused gradients in one launch
-        for slot, w, g, direct in landed:
-            wgrads[slot] = _pret(w, g, direct)
+        tab = [(kp, qp, vb[vs], maps[vs], outs[i], aux[i], dkp, dqp, dV[vs], residual)
+               for i, ((kp, qp), (dkp, dqp), (_, _, _, _, vs, residual))
+               in enumerate(zip(_level_blocks(Y, C), _level_blocks(dY, C), MSCSALevelFn.SPEC))]
+        if ctx.flash:
+            _level_bwd_flash(tab, dcat, ld, douts, ctx.qscaled, scr, B, N, C)
+        else:
+            for (kp, qp, _, v, _, P, dkp, dqp, dv, residual), dout in zip(tab, douts):
+                dout = _c(dout)
+                _attn_gemm_bwd(rt.lib().hupr_gemm_bf16, False, kp, qp, v, P, rt.ptr(dout), residual, not residual, dv, scr, dkp, dqp,
+                               B, N, C)
+        grads = _level_map_grads(ctx.needs_input_grad, maps, dY, Wc, dV)
+        wgrads = _level_weight_grads(ctx.needs_input_grad[3:], ctx.weights, maps, dY)
         return (grads[0], grads[1], None) + tuple(wgrads)
 
 
@@ -1495,8 +1496,7 @@ class GCNLayerFn(torch.autograd.Function):
         L = rt.lib()
         dt = torch.empty_like(x)
         gm = torch.empty_like(x)
-        # weight / bias gradients go straight into the flat-bucket views when a gradient sink is installed (round 5: the six
-        # AccumulateGrad add kernels of the PRGCN per step are gone)
+        # weight / bias gradients go straight into the flat-bucket views when a gradient sink is installed
         bias = ctx.bias_ref
         dbias, db_direct = _pgrad(bias) if tuple(bias.shape) == (F, K) and bias.is_contiguous() else (torch.empty((F, K), dtype=torch.float32, device=x.device), False)
         rt.check(L.hupr_gcn_adj_bwd_f32(rt.ptr(_c(dy)), rt.ptr(y), rt.ptr(adj), rt.ptr(dt), rt.ptr(gm), rt.ptr(dbias), B, F, K,
@@ -1527,8 +1527,7 @@ _HEAD_KINDS = (wcache.COPY,)
 
 def _head_w16_cached(weight):
     """The 14 head filters zero-padded to 16 as a PACK-TABLE entry (a plain copy into rows 0..K-1 of a persistent buffer whose other
-    rows stay zero), refreshed by the one table launch after an optimiser step — rounds 1-4 padded with ATen in every training
-    forward (a fill, a copy, and a slice + accumulate in the backward)."""
+    rows stay zero), refreshed by the one table launch after an optimiser step."""
     w16 = wcache.lookup((weight,), _HEAD_KINDS, _alloc_head) if tuple(weight.shape[1:]) == (32, 1, 1) else None
     if w16 is None:
         return torch.nn.functional.pad(weight.detach(), (0, 0, 0, 0, 0, 0, 0, 16 - weight.shape[0]))
@@ -1570,8 +1569,8 @@ class Head1x1Fn(torch.autograd.Function):
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         dw, direct = _pgrad(weight) if ctx.needs_input_grad[1] else (None, False)
         ws = workspace(L.hupr_head1x1_ws_bytes(), x.device)
-        rt.check(L.hupr_head1x1_bwd_rows_f32(rt.ptr(x), rt.ptr(w16), rt.ptr(dy), rt.ptr(dx) if dx is not None else None,
-                                             rt.ptr(dw) if dw is not None else None, weight.shape[0], M, rt.ptr(ws), ws.numel(), rt.stream()))
+        rt.check(L.hupr_head1x1_bwd_rows_f32(rt.ptr(x), rt.ptr(w16), rt.ptr(dy), rt.ptr(dx), rt.ptr(dw), weight.shape[0], M, rt.ptr(ws),
+                                             ws.numel(), rt.stream()))
         return dx, _pret(weight, dw, direct) if dw is not None else None, None
 
 
@@ -1657,7 +1656,7 @@ class PairBCEFn(torch.autograd.Function):
         dp1, dp2 = torch.empty_like(p1), torch.empty_like(p2)
         g = _c(g.reshape(1).to(torch.float32))
         g2 = _c(g2.reshape(1).to(torch.float32)) if g2 is not None else None
-        rt.check(rt.lib().hupr_bce_pair_bwd_f32(rt.ptr(p1), rt.ptr(p2), rt.ptr(t), rt.ptr(g), rt.ptr(g2) if g2 is not None else None,
+        rt.check(rt.lib().hupr_bce_pair_bwd_f32(rt.ptr(p1), rt.ptr(p2), rt.ptr(t), rt.ptr(g), rt.ptr(g2),
                                                 ctx.ab[0], ctx.ab[1], rt.ptr(dp1), rt.ptr(dp2), p1.numel(), rt.stream()))
         return dp1, dp2, None, None, None
 
