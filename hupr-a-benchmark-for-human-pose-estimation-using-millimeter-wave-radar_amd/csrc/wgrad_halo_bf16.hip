@@ -980,31 +980,30 @@ static int g_wgrad_groups256 = 1;   // (hupr_debug_wgrad_ci32(16 + mode): 128 pa
 static int g_wgrad_ci32 = 1;        // A/B aid (hupr_debug_wgrad_ci32): 0 = Ci <= 32 through the two-quadrant kernel as before, 2 = K quarters always
 extern "C" void hupr_debug_wgrad_ci32(int on) { g_wgrad_ci32 = on & 15; g_wgrad_groups256 = !(on & 16); }
 
-// dy2 / dw2 (both or neither): a second gradient tensor of the same shape and stride over the same x — Co is then the channel count of
-// EACH; one launch of the 16 x 16 x 32 kernel over 2 Co output channels and one reduction that splits its rows between dw and dw2.
-// Same partial tensors and the same sums per element as two calls (the workgroup count per (depth tap, tile pair) is the single
-// call's).  LDS-DMA kernels (bf16 storage) only: HUPR_ERR_ARG otherwise (the caller makes two calls).
-static int wgrad_halo(const void* x, const void* dy, float* dw, int Bn, int D, int H, int W, int Ci, int in_ld, int Co,
-                      int dy_ld, int kd, void* ws, size_t ws_bytes, bool abf, hupr_stream_t stream, const char* who,
-                      const void* dy2 = nullptr, float* dw2 = nullptr) {
-    HUPR_REQUIRE(x && dy && dw && ws, "%s: null pointer", who);
-    HUPR_REQUIRE((dy2 == nullptr) == (dw2 == nullptr), "%s: dy2 and dw2 go together", who);
-    const bool dual = dy2 != nullptr;
+// Route codes of a hupr_conv3x3_wgrad_halo_bf16(act)(_dual) call (hupr_debug_wgrad_route, include/hupr_debug.h): which kernel
+// instantiation it launches, on which grid.
+//   route & 15 : 1 hupr_k_wgrad_halo_m16<true>     2 hupr_k_wgrad_halo_m16<false>      3 hupr_k_wgrad_halo_m16<true, true> (K quarters)
+//                4 hupr_k_wgrad_halo_glds<false, false>  5 <false, true>  6 <true, false>  7 <true, true>     (<IS3D, CI32>)
+//                8 hupr_k_wgrad_halo_bf16<false, false>  9 <false, true> 10 <true, false> 11 <true, true>     (<ABF, IS3D>, register-staged)
+//   route & 16 : the XCD-aware 1-D grid (xcd_map); else (groups, kd, tile pairs)
+//   route & 32 : two gradients in one launch (dual)
+constexpr int kWgradM16 = 1, kWgradGlds = 4, kWgradReg = 8, kWgradXcd = 16, kWgradDual = 32;
+
+// The launch a call makes, decided once for wgrad_halo and hupr_debug_wgrad_route: checks the arguments (HUPR_ERR_ARG /
+// HUPR_ERR_WORKSPACE, before any launch) and returns the route code with the tile, group and grid fields of `a` filled (a.groups: the
+// partial-tensor count; a.Co / a.n_co_tiles / a.co_split of a dual launch cover both gradients).  `a` brings the shape and the strides.
+static int wgrad_plan(WgradHaloArgs& a, bool abf, bool dual, size_t ws_bytes, const char* who) {
+    const int Bn = a.Bn, D = a.D, H = a.H, W = a.W, Ci = a.Ci, in_ld = a.in_ld, Co = a.Co, dy_ld = a.dy_ld, kd = a.kd;
     HUPR_REQUIRE(!dual || (abf && Co % 64 == 0), "%s: the two-gradient form needs bf16 storage and Co %% 64 == 0", who);
     const int al = abf ? 8 : 4;
-    HUPR_REQUIRE(Bn > 0 && Co > 0 && Ci % 8 == 0 && Co % 8 == 0 && in_ld % al == 0 && dy_ld % al == 0,
+    HUPR_REQUIRE(Bn > 0 && Co > 0 && Ci > 0 && Ci % 8 == 0 && Co % 8 == 0 && in_ld % al == 0 && dy_ld % al == 0,
                  "%s: unsupported channels Ci=%d Co=%d", who, Ci, Co);
-    HUPR_REQUIRE(H % 8 == 0 && ((kd == 3 && D % 2 == 0 && W % 8 == 0) || (kd == 1 && D == 1 && W % 16 == 0)),
+    HUPR_REQUIRE(H > 0 && W > 0 && H % 8 == 0 && ((kd == 3 && D > 0 && D % 2 == 0 && W % 8 == 0) || (kd == 1 && D == 1 && W % 16 == 0)),
                  "%s: unsupported geometry", who);
     HUPR_REQUIRE((long)Bn * D * H * W * (in_ld > dy_ld ? in_ld : dy_ld) < (1L << 31), "%s: tensor too large for 32-bit offsets", who);
-    WgradHaloArgs a;
     a.xcd_map = 0;
-    a.x = x; a.dy = dy; a.part = reinterpret_cast<float*>(ws);
-    a.Bn = Bn; a.D = D; a.H = H; a.W = W; a.Ci = Ci; a.in_ld = in_ld; a.Co = Co; a.dy_ld = dy_ld;
-    a.kd = kd;
     if (kd == 3) { a.TD = 2; a.log2TW = 3; } else { a.TD = 1; a.log2TW = 4; }
     a.nd = D / a.TD; a.nh = H / 8; a.nw = W >> a.log2TW;
-    a.dy2 = dy2;
     a.co_split = dual ? Co : 0;
     a.n_ci_tiles = (Ci + 63) / 64;
     a.n_co_tiles = (Co + 63) / 64;
@@ -1017,9 +1016,8 @@ static int wgrad_halo(const void* x, const void* dy, float* dw, int Bn, int D, i
     int groups = max(1, min(kd == 1 && g_wgrad_groups256 ? 256 : 128, 768 / pairs));
     groups = min(groups, a.n_spatial);
     while (groups > 1 && (size_t)groups * one > ws_bytes) groups >>= 1;
-    if ((size_t)groups * one > ws_bytes) return fail(HUPR_ERR_WORKSPACE, "hupr_conv3x3_wgrad_halo_bf16: workspace too small");
-    hipStream_t s = as_stream(stream);
-    const long n = (long)Co * kd * 9 * Ci;
+    if ((size_t)groups * one > ws_bytes)
+        return fail(HUPR_ERR_WORKSPACE, dual ? "%s: workspace too small for two gradients" : "%s: workspace too small", who);
     const long max_bytes = (long)Bn * D * H * W * (in_ld > dy_ld ? in_ld : dy_ld) * 2;
     if (abf && max_bytes < 0x7ffffff0L) {
         // LDS-DMA kernel: one 512-thread workgroup per CU (two K halves, merged in LDS), one partial tensor per workgroup
@@ -1029,47 +1027,76 @@ static int wgrad_halo(const void* x, const void* dy, float* dw, int Bn, int D, i
         a.xcd_map = g8 > 0 && 10 * g8 >= 9 * gw && g8 <= a.n_spatial;
         if (a.xcd_map) gw = min(g8, 128);
         gw = min(gw, a.n_spatial);
-        while (gw > 1 && (size_t)gw * one > ws_bytes) { gw >>= 1; a.xcd_map = 0; }
-        if (dual && (size_t)gw * one > ws_bytes) return fail(HUPR_ERR_WORKSPACE, "%s: workspace too small for two gradients", who);
-        if ((size_t)gw * one <= ws_bytes) {
-            a.groups = gw;
-            if (dual) { a.Co = 2 * Co; a.n_co_tiles *= 2; }
-            const dim3 grid = a.xcd_map ? dim3(gw * pairs * nt) : dim3(gw, kd, a.n_ci_tiles * a.n_co_tiles);
-            // K quarters pay once a workgroup multiplies enough tiles to amortise the extra LDS merge (measured: 222 -> 160 us on
-            // the 32 -> 64 layer-1 shape at 102 tiles per workgroup; +2-3 us on shapes with one or two tiles per workgroup)
-            const bool ci32 = Ci <= 32 && (g_wgrad_ci32 >= 2 || (g_wgrad_ci32 == 1 && a.n_spatial >= 16 * gw));
-            if (g_wgrad_m16 && !ci32) {                                  // the 16 x 16 x 32 form (round 5)
-                if (kd == 3) HUPR_LAUNCH((hupr_k_wgrad_halo_m16<true>), grid, dim3(512), 0, s, a);
-                else HUPR_LAUNCH((hupr_k_wgrad_halo_m16<false>), grid, dim3(512), 0, s, a);
-            } else if (g_wgrad_m16 && kd == 3 && g_wgrad_ci32 != 3) {    // ... and its K-quarter form for Ci <= 32 (round 6; hupr_debug_wgrad_ci32(3): the 32 x 32 x 16 one)
-                HUPR_LAUNCH((hupr_k_wgrad_halo_m16<true, true>), grid, dim3(512), 0, s, a);
-            } else if (kd == 3) {
-                if (ci32) HUPR_LAUNCH((hupr_k_wgrad_halo_glds<true, true>), grid, dim3(512), 0, s, a);
-                else HUPR_LAUNCH((hupr_k_wgrad_halo_glds<true, false>), grid, dim3(512), 0, s, a);
-            } else {
-                if (ci32) HUPR_LAUNCH((hupr_k_wgrad_halo_glds<false, true>), grid, dim3(512), 0, s, a);
-                else HUPR_LAUNCH((hupr_k_wgrad_halo_glds<false, false>), grid, dim3(512), 0, s, a);
-            }
-            HUPR_LAUNCH_OK("hupr_k_wgrad_halo_glds");
-            launch_splitk_reduce(reinterpret_cast<const float*>(ws), dw, nt * n, gw, nt * n, kd * 9, Ci, s, dw2, n);
-            HUPR_LAUNCH_OK("hupr_k_splitk_reduce");
-            return HUPR_OK;
-        }
+        while (gw > 1 && (size_t)gw * one > ws_bytes) { gw >>= 1; a.xcd_map = 0; }      // (one partial tensor fits: checked above)
+        a.groups = gw;
+        if (dual) { a.Co = 2 * Co; a.n_co_tiles *= 2; }
+        // K quarters pay once a workgroup multiplies enough tiles to amortise the extra LDS merge (measured: 222 -> 160 us on
+        // the 32 -> 64 layer-1 shape at 102 tiles per workgroup; +2-3 us on shapes with one or two tiles per workgroup)
+        const bool ci32 = Ci <= 32 && (g_wgrad_ci32 >= 2 || (g_wgrad_ci32 == 1 && a.n_spatial >= 16 * gw));
+        int kernel;
+        if (g_wgrad_m16 && !ci32) kernel = kWgradM16 + (kd == 3 ? 0 : 1);                // the 16 x 16 x 32 form (round 5)
+        else if (g_wgrad_m16 && kd == 3 && g_wgrad_ci32 != 3) kernel = kWgradM16 + 2;    // ... and its K-quarter form for Ci <= 32 (round 6; hupr_debug_wgrad_ci32(3): the 32 x 32 x 16 one)
+        else kernel = kWgradGlds + 2 * (kd == 3) + (ci32 ? 1 : 0);
+        return kernel + (a.xcd_map ? kWgradXcd : 0) + (dual ? kWgradDual : 0);
     }
     if (dual) return fail(HUPR_ERR_ARG, "%s: the two-gradient form applies to the LDS-DMA kernel's envelope only", who);
     a.groups = groups;
-    const dim3 grid(groups, kd, a.n_ci_tiles * a.n_co_tiles);
-    if (kd == 3) {
-        if (abf) HUPR_LAUNCH((hupr_k_wgrad_halo_bf16<true, true>), grid, dim3(256), 0, s, a);
-        else HUPR_LAUNCH((hupr_k_wgrad_halo_bf16<false, true>), grid, dim3(256), 0, s, a);
-    } else {
-        if (abf) HUPR_LAUNCH((hupr_k_wgrad_halo_bf16<true, false>), grid, dim3(256), 0, s, a);
-        else HUPR_LAUNCH((hupr_k_wgrad_halo_bf16<false, false>), grid, dim3(256), 0, s, a);
+    return kWgradReg + 2 * (abf ? 1 : 0) + (kd == 3);
+}
+
+// dy2 / dw2 (both or neither): a second gradient tensor of the same shape and stride over the same x — Co is then the channel count of
+// EACH; one launch of the 16 x 16 x 32 kernel over 2 Co output channels and one reduction that splits its rows between dw and dw2.
+// Same partial tensors and the same sums per element as two calls (the workgroup count per (depth tap, tile pair) is the single
+// call's).  LDS-DMA kernels (bf16 storage) only: HUPR_ERR_ARG otherwise (the caller makes two calls).
+static int wgrad_halo(const void* x, const void* dy, float* dw, int Bn, int D, int H, int W, int Ci, int in_ld, int Co,
+                      int dy_ld, int kd, void* ws, size_t ws_bytes, bool abf, hupr_stream_t stream, const char* who,
+                      const void* dy2 = nullptr, float* dw2 = nullptr) {
+    HUPR_REQUIRE(x && dy && dw && ws, "%s: null pointer", who);
+    HUPR_REQUIRE((dy2 == nullptr) == (dw2 == nullptr), "%s: dy2 and dw2 go together", who);
+    const bool dual = dy2 != nullptr;
+    WgradHaloArgs a;
+    a.x = x; a.dy = dy; a.part = reinterpret_cast<float*>(ws);
+    a.Bn = Bn; a.D = D; a.H = H; a.W = W; a.Ci = Ci; a.in_ld = in_ld; a.Co = Co; a.dy_ld = dy_ld;
+    a.kd = kd;
+    a.dy2 = dy2;
+    const int route = wgrad_plan(a, abf, dual, ws_bytes, who);
+    if (route < 0) return route;
+    hipStream_t s = as_stream(stream);
+    const long n = (long)Co * kd * 9 * Ci;
+    const int nt = dual ? 2 : 1;
+    const int tile_pairs = a.n_ci_tiles * a.n_co_tiles;                 // of the whole launch (both gradients of a dual one)
+    const dim3 grid = (route & kWgradXcd) ? dim3(a.groups * tile_pairs * kd) : dim3(a.groups, kd, tile_pairs);
+    const int threads = (route & 15) >= kWgradReg ? 256 : 512;
+    switch (route & 15) {
+        case 1: HUPR_LAUNCH((hupr_k_wgrad_halo_m16<true>), grid, dim3(threads), 0, s, a); break;
+        case 2: HUPR_LAUNCH((hupr_k_wgrad_halo_m16<false>), grid, dim3(threads), 0, s, a); break;
+        case 3: HUPR_LAUNCH((hupr_k_wgrad_halo_m16<true, true>), grid, dim3(threads), 0, s, a); break;
+        case 4: HUPR_LAUNCH((hupr_k_wgrad_halo_glds<false, false>), grid, dim3(threads), 0, s, a); break;
+        case 5: HUPR_LAUNCH((hupr_k_wgrad_halo_glds<false, true>), grid, dim3(threads), 0, s, a); break;
+        case 6: HUPR_LAUNCH((hupr_k_wgrad_halo_glds<true, false>), grid, dim3(threads), 0, s, a); break;
+        case 7: HUPR_LAUNCH((hupr_k_wgrad_halo_glds<true, true>), grid, dim3(threads), 0, s, a); break;
+        case 8: HUPR_LAUNCH((hupr_k_wgrad_halo_bf16<false, false>), grid, dim3(threads), 0, s, a); break;
+        case 9: HUPR_LAUNCH((hupr_k_wgrad_halo_bf16<false, true>), grid, dim3(threads), 0, s, a); break;
+        case 10: HUPR_LAUNCH((hupr_k_wgrad_halo_bf16<true, false>), grid, dim3(threads), 0, s, a); break;
+        default: HUPR_LAUNCH((hupr_k_wgrad_halo_bf16<true, true>), grid, dim3(threads), 0, s, a); break;
     }
-    HUPR_LAUNCH_OK("hupr_k_wgrad_halo_bf16");
-    launch_splitk_reduce(reinterpret_cast<const float*>(ws), dw, n, groups, n, kd * 9, Ci, s);
+    HUPR_LAUNCH_OK((route & 15) >= kWgradReg ? "hupr_k_wgrad_halo_bf16" : "hupr_k_wgrad_halo_glds");
+    launch_splitk_reduce(reinterpret_cast<const float*>(ws), dw, nt * n, a.groups, nt * n, kd * 9, Ci, s, dw2, n);
     HUPR_LAUNCH_OK("hupr_k_splitk_reduce");
     return HUPR_OK;
+}
+
+// Test aid (include/hupr_debug.h): the route code of the launch hupr_conv3x3_wgrad_halo_bf16 (abf = 0) / _bf16act (abf = 1) / _bf16act_dual
+// (dual) would make with a workspace of ws_bytes, under the current hupr_debug_wgrad_m16 / _ci32 settings, and its partial-tensor count in
+// *groups_out (may be null; 0 where refused) — or the HUPR_ERR_* value of a refused call.  Nothing is launched.
+extern "C" int hupr_debug_wgrad_route(int Bn, int D, int H, int W, int Ci, int in_ld, int Co, int dy_ld, int kd, int abf, int dual,
+                                      size_t ws_bytes, int* groups_out) {
+    WgradHaloArgs a{};
+    a.Bn = Bn; a.D = D; a.H = H; a.W = W; a.Ci = Ci; a.in_ld = in_ld; a.Co = Co; a.dy_ld = dy_ld;
+    a.kd = kd;
+    const int route = wgrad_plan(a, abf != 0, dual != 0, ws_bytes, "hupr_debug_wgrad_route");
+    if (groups_out) *groups_out = route < 0 ? 0 : a.groups;
+    return route;
 }
 
 extern "C" int hupr_conv3x3_wgrad_halo_bf16(const float* x, const float* dy, float* dw, int Bn, int D, int H, int W, int Ci,

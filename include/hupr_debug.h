@@ -4,6 +4,7 @@
  */
 #ifndef HUPR_DEBUG_H
 #define HUPR_DEBUG_H
+#include <stddef.h>
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -27,6 +28,13 @@ int hupr_debug_halo_route(int Bn, int D, int H, int W, int Ci, int in_ld, int Co
      * channels), 3 the 1 x 16 x 16 tile, 4 / 5 the 4 x 8 x 8 tile with fused statistics of one / two output tiles per workgroup, 6 the 2 x 8 x 16
      * tile with fused statistics, 7 the 4 x 8 x 8 tile, 8 the 2 x 8 x 16 tile; else the 128-voxel kernel: 256 + 16 * slices + 8 * (BN == 64)
      * + 4 * (KC == 64) + 2 * (kd == 3) + abf (slices > 1: the K-sliced form) */
+int hupr_debug_wgrad_route(int Bn, int D, int H, int W, int Ci, int in_ld, int Co, int dy_ld, int kd, int abf, int dual, size_t ws_bytes,
+                           int* groups_out);
+    /* test aid: which kernel instantiation hupr_conv3x3_wgrad_halo_bf16 (abf = 0) / _bf16act (abf = 1) / _bf16act_dual (dual = 1) would launch
+     * with a workspace of ws_bytes, under hupr_debug_wgrad_m16 / _ci32 as set; *groups_out (may be null): its partial-tensor count.  Nothing is
+     * launched.  HUPR_ERR_ARG / HUPR_ERR_WORKSPACE where the call is refused.  route & 15: 1 hupr_k_wgrad_halo_m16<true> (3-D taps), 2
+     * m16<false>, 3 m16<true, true> (K quarters); 4-7 hupr_k_wgrad_halo_glds<IS3D, CI32> = 4 + 2 * IS3D + CI32 (the 32 x 32 x 16 kernel);
+     * 8-11 the register-staged hupr_k_wgrad_halo_bf16<ABF, IS3D> = 8 + 2 * ABF + IS3D.  + 16: the XCD-aware 1-D grid; + 32: two gradients */
 #ifdef __cplusplus
 }
 #endif
