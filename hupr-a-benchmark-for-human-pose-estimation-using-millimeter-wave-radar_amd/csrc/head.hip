@@ -287,9 +287,9 @@ __global__ __launch_bounds__(64) void hupr_k_argmax_rows(const float* __restrict
 }
 
 // ---- Adam with coupled L2 weight decay (torch.optim.Adam semantics), one flat launch --------------
-__global__ __launch_bounds__(256) void hupr_k_adam(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                   float* __restrict__ v, long n, float lr, float b1, float b2, float eps,
-                                                   float wd, float bc1, float bc2_sqrt, float gscale) {
+__device__ __forceinline__ void adam_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                          float* __restrict__ v, long n, float lr, float b1, float b2, float eps, float wd,
+                                          float bc1, float bc2_sqrt, float gscale) {
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
         const float pv = p[i];
         const float gr = fmaf(wd, pv, g[i] * gscale);
@@ -302,24 +302,40 @@ __global__ __launch_bounds__(256) void hupr_k_adam(float* __restrict__ p, const 
     }
 }
 
+__global__ __launch_bounds__(256) void hupr_k_adam(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                   float* __restrict__ v, long n, float lr, float b1, float b2, float eps,
+                                                   float wd, float bc1, float bc2_sqrt, float gscale) {
+    adam_body(p, g, m, v, n, lr, b1, b2, eps, wd, bc1, bc2_sqrt, gscale);
+}
+
+// the bias corrections of step `step` as hupr_adam_step_f32 forms them on the host
+__device__ __forceinline__ void adam_bias_corrections(float b1, float b2, float step_f, float& bc1, float& bc2_sqrt) {
+    const double step = (double)step_f;
+    bc1 = (float)(1.0 - pow((double)b1, step));
+    bc2_sqrt = (float)sqrt(1.0 - pow((double)b2, step));
+}
+
 // same update with the learning rate and the step count read from device memory (state = {lr, step}): the launch
 // arguments of a captured hipGraph are frozen, the bias corrections must not be
 __global__ __launch_bounds__(256) void hupr_k_adam_dev(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                        float* __restrict__ v, long n, const float* __restrict__ state, float b1,
                                                        float b2, float eps, float wd, float gscale) {
-    const float lr = state[0];
-    const double step = (double)state[1];
-    const float bc1 = (float)(1.0 - pow((double)b1, step)), bc2_sqrt = (float)sqrt(1.0 - pow((double)b2, step));
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-        const float pv = p[i];
-        const float gr = fmaf(wd, pv, g[i] * gscale);
-        const float mv = fmaf(b1, m[i], (1.f - b1) * gr);
-        const float vv = fmaf(b2, v[i], (1.f - b2) * gr * gr);
-        m[i] = mv;
-        v[i] = vv;
-        const float denom = sqrtf(vv) / bc2_sqrt + eps;
-        p[i] = pv - (lr / bc1) * (mv / denom);
-    }
+    float bc1, bc2_sqrt;
+    adam_bias_corrections(b1, b2, state[1], bc1, bc2_sqrt);
+    adam_body(p, g, m, v, n, state[0], b1, b2, eps, wd, bc1, bc2_sqrt, gscale);
+}
+
+// hupr_k_adam_dev behind the gradient guard (grad_guard.hip; guard = {coef, norm, skipped, finite}): nothing is written when the
+// step's gradients were not finite, otherwise the gradient scale carries the clipping coefficient (one fp32 product; coef = 1
+// leaves gscale's bits, so the unclipped step is hupr_k_adam_dev's)
+__global__ __launch_bounds__(256) void hupr_k_adam_guard(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                         float* __restrict__ v, long n, const float* __restrict__ state,
+                                                         const float* __restrict__ guard, float b1, float b2, float eps, float wd,
+                                                         float gscale) {
+    if (guard[3] == 0.f) return;
+    float bc1, bc2_sqrt;
+    adam_bias_corrections(b1, b2, state[1], bc1, bc2_sqrt);
+    adam_body(p, g, m, v, n, state[0], b1, b2, eps, wd, bc1, bc2_sqrt, gscale * guard[0]);
 }
 
 // ---- SGD with momentum and coupled L2 weight decay (torch.optim.SGD, dampening 0, no Nesterov), one flat launch -------------
@@ -372,6 +388,14 @@ __global__ __launch_bounds__(256) void hupr_k_sgd_dev(float* __restrict__ p, con
                                                       long n, const float* __restrict__ state, float m, float wd, float gscale,
                                                       int vec) {
     sgd_body(p, g, buf, n, state[0], m, wd, gscale, state[1] == 1.f, vec != 0);
+}
+
+// hupr_k_sgd_dev behind the gradient guard, as hupr_k_adam_guard
+__global__ __launch_bounds__(256) void hupr_k_sgd_guard(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
+                                                        long n, const float* __restrict__ state, const float* __restrict__ guard,
+                                                        float m, float wd, float gscale, int vec) {
+    if (guard[3] == 0.f) return;
+    sgd_body(p, g, buf, n, state[0], m, wd, gscale * guard[0], state[1] == 1.f, vec != 0);
 }
 
 static inline int grid1d(long n, int bs = 256, long cap = 4096) { return (int)min(cap, (n + bs - 1) / bs); }
@@ -651,6 +675,18 @@ extern "C" int hupr_adam_step_dev_f32(float* p, const float* g, float* exp_avg, 
     return HUPR_OK;
 }
 
+// hupr_adam_step_dev_f32 behind the gradient guard: guard = the 4 floats hupr_grad_guard_f32 wrote on this stream before
+extern "C" int hupr_adam_step_guard_f32(float* p, const float* g, float* exp_avg, float* exp_avg_sq, long n,
+                                        const float* dev_state, const float* guard, float beta1, float beta2, float eps,
+                                        float weight_decay, float gscale, hupr_stream_t stream) {
+    HUPR_REQUIRE(p && g && exp_avg && exp_avg_sq && dev_state && guard && n > 0,
+                 "hupr_adam_step_guard_f32: bad argument (null pointer or n <= 0)");
+    HUPR_LAUNCH(hupr_k_adam_guard, dim3(grid1d(n, 256, 8192)), dim3(256), 0, as_stream(stream), p, g, exp_avg, exp_avg_sq, n,
+                dev_state, guard, beta1, beta2, eps, weight_decay, gscale);
+    HUPR_LAUNCH_OK("hupr_k_adam_guard");
+    return HUPR_OK;
+}
+
 // float4 path only when all three streams are 16-byte aligned; grid = min(ceil(n / (256 * 4)), 2048) with a grid-stride loop
 static inline int sgd_vec(const float* p, const float* g, const float* buf) {
     return ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(buf)) & 15) == 0;
@@ -674,5 +710,16 @@ extern "C" int hupr_sgd_step_dev_f32(float* p, const float* g, float* momentum_b
     HUPR_LAUNCH(hupr_k_sgd_dev, dim3(grid1d(n, 256 * 4, 2048)), dim3(256), 0, as_stream(stream), p, g, momentum_buf, n, dev_state,
                 momentum, weight_decay, gscale, sgd_vec(p, g, momentum_buf));
     HUPR_LAUNCH_OK("hupr_k_sgd_dev");
+    return HUPR_OK;
+}
+
+// hupr_sgd_step_dev_f32 behind the gradient guard (hupr_grad_guard_f32 advanced dev_state[1] on this stream before)
+extern "C" int hupr_sgd_step_guard_f32(float* p, const float* g, float* momentum_buf, long n, const float* dev_state,
+                                       const float* guard, float momentum, float weight_decay, float gscale, hupr_stream_t stream) {
+    HUPR_REQUIRE(p && g && momentum_buf && dev_state && guard && n > 0,
+                 "hupr_sgd_step_guard_f32: bad argument (null pointer or n <= 0)");
+    HUPR_LAUNCH(hupr_k_sgd_guard, dim3(grid1d(n, 256 * 4, 2048)), dim3(256), 0, as_stream(stream), p, g, momentum_buf, n, dev_state,
+                guard, momentum, weight_decay, gscale, sgd_vec(p, g, momentum_buf));
+    HUPR_LAUNCH_OK("hupr_k_sgd_guard");
     return HUPR_OK;
 }

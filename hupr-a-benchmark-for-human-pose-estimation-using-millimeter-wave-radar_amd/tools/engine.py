@@ -29,6 +29,10 @@ class TrainEngine:
         self.optimizer = make_optimizer(cfg, self.model.parameters(), lr if lr is not None else cfg.TRAINING.lr)
         self.optimizer.attach_flat_buckets(self.buckets.flat_pairs(), self.buckets.layout())
         self.optimizer.grad_scale = 1.0 / self.world_size
+        # TRAINING.gradClip: clip the global gradient norm / skip a non-finite step, decided on the device between finish() and
+        # the update (so the norm is that of the mean gradient over ranks and micro-batches, identical on every rank)
+        if self.optimizer.grad_clip is not None:
+            self.optimizer.enable_grad_guard(self.optimizer.grad_clip)
         self.G = cfg.DATASET.numGroupFrames
         self.fuse_elevation_mean = os.environ.get("HUPR_NO_FUSED_MEAN", "0") != "1"
         self._fft_ws = None
@@ -126,6 +130,7 @@ class TrainEngine:
         in lock step.  Requirements: fixed shapes (the static input buffers are refilled by copy), joints already on
         the device (a pageable host-to-device copy is illegal inside a capture), ``TRAINING.lossDecay == -1`` (the
         alpha/beta loss weights would be frozen at their capture-time values), ``sync_lr()`` after LR changes.
+        The gradient guard (``TRAINING.gradClip``) is device-side and replays with the step.
         The ``warmup`` eager steps are real optimisation steps."""
         tr = self.buckets.transport
         if self.buckets.active and not getattr(tr, "capturable", False):
@@ -153,6 +158,13 @@ class TrainEngine:
 
     def sync_lr(self):
         self.optimizer.sync_lr()
+
+    def guard_stats(self):
+        """With ``TRAINING.gradClip`` set: {"norm": the last step's global gradient norm (after ``grad_scale``), "coef": its
+        clipping coefficient (0 for a skipped step), "skipped": steps skipped so far}; None otherwise.  Synchronises the
+        device: per epoch, not per step.  A skipped step leaves parameters, optimiser state and step count as they were; the
+        BatchNorm running statistics of its forward pass have moved all the same (as under torch's GradScaler)."""
+        return self.optimizer.guard_stats()
 
     def _replay(self, adc_hori, adc_vert, joints):
         for dst, src in zip(self._g_in, (adc_hori, adc_vert, joints)):

@@ -5,6 +5,10 @@ weight_decay=1e-4)`` or ``optim.Adam(lr, betas=(0.9, 0.999), weight_decay=1e-4)`
 Each fused optimiser has the update rule and the ``state_dict`` layout of its torch counterpart, so the reference's
 ``optimizer_state_dict`` checkpoints interchange.  One kernel launch per parameter tensor, or one per flat bucket when the
 parameters were flattened by ``tools.distributed``.
+
+``TRAINING.gradClip`` (absent from the reference's YAML; ``-1`` = off) puts the gradient guard in front of the flat-bucket step:
+global-norm clipping (``torch.nn.utils.clip_grad_norm_``'s rule) and the skip of a step whose gradients are not finite, both
+decided on the device (``enable_grad_guard``).
 """
 import torch
 
@@ -21,6 +25,8 @@ class _FlatBucketOptimizer(torch.optim.Optimizer):
         super().__init__(params, defaults)
         self.grad_scale = 1.0            # e.g. 1/world_size when gradients were sum-all-reduced
         self._flat = None                # optional [(param_flat, grad_flat)] installed by tools.distributed
+        self._guard = None               # {coef, norm, skipped, finite} on the device: set by enable_grad_guard()
+        self.grad_clip = None            # TRAINING.gradClip as make_optimizer read it (None = off)
 
     def attach_flat_buckets(self, buckets, layout=None):
         """buckets: list of (flat_param, flat_grad) fp32 GPU tensors covering all parameters in order.
@@ -35,10 +41,53 @@ class _FlatBucketOptimizer(torch.optim.Optimizer):
     def use_device_state(self):
         """Keep the learning rate and the step count in device memory (needed when step() is captured in a hipGraph:
         launch arguments are frozen at capture, the step count and LR schedule must keep moving)."""
+        if self._dev_state is not None:      # already there (enable_grad_guard): the device copy is the truth
+            self.sync_lr()
+            return
         dev = self._flat[0][0].device
         self._dev_state = torch.tensor([self.param_groups[0]["lr"], float(self._flat_state[0]["step"])], dtype=torch.float32,
                                        device=dev)
         self._dev_lr = self.param_groups[0]["lr"]
+
+    # -- gradient guard: global-norm clipping and the skip of a non-finite step, on the device -----------------------
+    def enable_grad_guard(self, max_norm):
+        """From now on ``step()`` takes the L2 norm of all flat gradients times ``grad_scale`` (one ``hupr_grad_sumsq_f32`` per
+        bucket + one ``hupr_grad_guard_f32``), scales the gradients by ``min(1, max_norm / (norm + 1e-6))`` inside the update
+        and leaves parameters, state and step count untouched when the norm is not finite.  ``max_norm = inf``: guard only.
+        Everything is device-side ({lr, step} move to device memory, the guard kernel owns the step increment), so a step
+        captured in a hipGraph is guarded too."""
+        if self._flat is None:
+            raise RuntimeError("enable_grad_guard needs flat gradient buckets (attach_flat_buckets first): the global norm is "
+                               "taken over the buckets")
+        max_norm = float(max_norm)
+        if not max_norm > 0.0:
+            raise ValueError("enable_grad_guard: max_norm must be positive (inf = guard only), got %r" % (max_norm,))
+        self.use_device_state()
+        dev = self._flat[0][0].device
+        if self._guard is None:
+            self._guard_k = rt.lib().hupr_grad_sumsq_partials()
+            self._guard_partials = torch.zeros(len(self._flat) * self._guard_k, dtype=torch.float64, device=dev)
+            self._guard = torch.zeros(4, dtype=torch.float32, device=dev)
+        self._guard_max_norm = max_norm
+
+    def _guard_launches(self, L, s):
+        """The launches of a guarded step in front of the per-bucket updates; afterwards ``_guard`` holds this step's decision and
+        ``_dev_state[1]`` this step's count (unchanged when the step is skipped)."""
+        if not torch.cuda.is_current_stream_capturing():
+            self.sync_lr()                   # a changed param_groups lr (Runner.adjustLR); a captured step reads it on replay
+        k = self._guard_k
+        for i, (_, g) in enumerate(self._flat):
+            rt.check(L.hupr_grad_sumsq_f32(rt.ptr(g), g.numel(), rt.ptr(self._guard_partials) + 8 * k * i, s))
+        rt.check(L.hupr_grad_guard_f32(rt.ptr(self._guard_partials), self._guard_partials.numel(), self.grad_scale,
+                                       self._guard_max_norm, rt.ptr(self._dev_state), rt.ptr(self._guard), s))
+
+    def guard_stats(self):
+        """The last step's {"norm", "coef"} and the number of steps skipped so far (not checkpointed); None without the guard.
+        Reads device memory, so it synchronises: per epoch, not per step."""
+        if self._guard is None:
+            return None
+        coef, norm, skipped, _ = self._guard.tolist()
+        return {"norm": norm, "coef": coef, "skipped": int(skipped)}
 
     # -- checkpoint interchange with torch.optim (reference tools/base.py:76-81,113) -----------------------------
     def _host_step(self, i):
@@ -136,6 +185,13 @@ class FusedAdam(_FlatBucketOptimizer):
         if self._flat is not None:
             g0 = self.param_groups[0]
             b1, b2 = g0["betas"]
+            if self._guard is not None:
+                self._guard_launches(L, s)       # advances the device-side step count unless the step is skipped
+                for (p, g), st in zip(self._flat, self._flat_state):
+                    rt.check(L.hupr_adam_step_guard_f32(rt.ptr(p), rt.ptr(g), rt.ptr(st["exp_avg"]), rt.ptr(st["exp_avg_sq"]),
+                                                        p.numel(), rt.ptr(self._dev_state), rt.ptr(self._guard), b1, b2,
+                                                        g0["eps"], g0["weight_decay"], self.grad_scale, s))
+                return loss
             if self._dev_state is not None:
                 self._dev_state[1] += 1          # device-side step count (captured as a graph node)
                 for (p, g), st in zip(self._flat, self._flat_state):
@@ -223,6 +279,13 @@ class FusedSGD(_FlatBucketOptimizer):
         F_.invalidate_packed()             # parameters change below without bumping torch's version counters
         if self._flat is not None:
             g0 = self.param_groups[0]
+            if self._guard is not None:
+                self._guard_launches(L, s)       # advances the device-side step count unless the step is skipped
+                for (p, g), st in zip(self._flat, self._flat_state):
+                    rt.check(L.hupr_sgd_step_guard_f32(rt.ptr(p), rt.ptr(g), rt.ptr(st["momentum_buffer"]), p.numel(),
+                                                       rt.ptr(self._dev_state), rt.ptr(self._guard), g0["momentum"],
+                                                       g0["weight_decay"], self.grad_scale, s))
+                return loss
             if self._dev_state is not None:
                 self._dev_state[1] += 1          # device-side step count (captured as a graph node): step 1 is the first
                 for (p, g), st in zip(self._flat, self._flat_state):
@@ -250,12 +313,29 @@ class FusedSGD(_FlatBucketOptimizer):
         return loss
 
 
+def grad_clip_setting(cfg):
+    """``TRAINING.gradClip`` -> None (absent or -1: off, the YAML's own "-1 = off" idiom) or the max norm as a float (``.inf``:
+    guard only, no clipping).  Anything else (0, another negative number, NaN, not a number) is refused."""
+    v = getattr(cfg.TRAINING, "gradClip", -1)
+    if isinstance(v, (int, float)) and not isinstance(v, bool):
+        if v == -1:
+            return None
+        if v > 0:                            # False for NaN
+            return float(v)
+    raise ValueError("TRAINING.gradClip must be -1 (off), a positive max norm, or .inf (guard only, no clipping); got %r" % (v,))
+
+
 def make_optimizer(cfg, params, lr):
     """The optimiser ``TRAINING.optimizer`` selects, built as the reference builds it (tools/base.py:44-47).  The reference
-    leaves ``self.optimizer`` unset for any other name and fails later; this raises here."""
+    leaves ``self.optimizer`` unset for any other name and fails later; this raises here.  ``TRAINING.gradClip`` is read into
+    ``optimizer.grad_clip``; the caller enables the guard once the flat buckets are attached (``TrainEngine``)."""
     name = cfg.TRAINING.optimizer
+    clip = grad_clip_setting(cfg)
     if name == "adam":
-        return FusedAdam(params, lr=lr, betas=(0.9, 0.999), weight_decay=1e-4)
-    if name == "sgd":
-        return FusedSGD(params, lr=lr, momentum=0.9, weight_decay=1e-4)
-    raise ValueError("TRAINING.optimizer must be 'sgd' or 'adam' (tools/base.py:44-47), got %r" % (name,))
+        opt = FusedAdam(params, lr=lr, betas=(0.9, 0.999), weight_decay=1e-4)
+    elif name == "sgd":
+        opt = FusedSGD(params, lr=lr, momentum=0.9, weight_decay=1e-4)
+    else:
+        raise ValueError("TRAINING.optimizer must be 'sgd' or 'adam' (tools/base.py:44-47), got %r" % (name,))
+    opt.grad_clip = clip
+    return opt

@@ -127,6 +127,7 @@ class Runner(BaseRunner):
     def train(self):
         for epoch in range(self.start_epoch, self.cfg.TRAINING.epochs):
             loss_list = []
+            guard0 = self.engine.guard_stats()
             self.logger.clear(len(self.trainLoader.dataset))
             if hasattr(self.trainLoader.sampler, "set_epoch"):
                 self.trainLoader.sampler.set_epoch(epoch)
@@ -139,6 +140,10 @@ class Runner(BaseRunner):
                 loss_list.append(loss.detach())
                 if getattr(self.args, "max_steps", 0) and idxBatch + 1 >= self.args.max_steps:
                     break
+            if guard0 is not None:           # TRAINING.gradClip: steps of this epoch whose gradients were not finite
+                skipped = self.engine.guard_stats()["skipped"] - guard0["skipped"]
+                if skipped and self.rank == 0:
+                    print("==========>Skipped %d optimizer step(s) with non-finite gradients in epoch %d" % (skipped, epoch))
             accAP = self.eval(visualization=False, epoch=epoch)
             if self.rank == 0:
                 self.saveModelWeight(epoch, accAP)

@@ -483,6 +483,30 @@ int hupr_sgd_step_f32(float* p, const float* g, float* momentum_buf, long n, flo
 int hupr_sgd_step_dev_f32(float* p, const float* g, float* momentum_buf, long n, const float* dev_state,
                           float momentum, float weight_decay, float gscale, hupr_stream_t stream);
 
+/* (a11) Gradient guard: global-norm clipping and the skip of a non-finite step, decided on the device (csrc/grad_guard.hip).
+ * New, no reference counterpart: the reference steps on whatever backward left (tools/run.py:78-79).  Per optimiser step and
+ * stream: hupr_grad_sumsq_f32 once per gradient bucket, hupr_grad_guard_f32 once, then the *_step_guard_f32 entry per bucket.
+ * No atomics: results are bit-identical from run to run.  All of it is stream-ordered and capturable in a hipGraph. */
+/* number of fp64 partials one hupr_grad_sumsq_f32 call writes */
+int hupr_grad_sumsq_partials(void);
+/* partials[0 .. hupr_grad_sumsq_partials()) <- partial sums of g[i]^2 over g[0 .. n), accumulated in fp64 (slots without an
+ * element hold 0.0).  g may start at any 4-byte boundary: float4 loads from its first 16-byte boundary, scalar ends. */
+int hupr_grad_sumsq_f32(const float* g, long n, double* partials, hupr_stream_t stream);
+/* total = sum of partials[0 .. count) (the partials of all buckets, fixed order, fp64);  norm = gscale * sqrt(total);
+ * coef = min(1, max_norm / (norm + 1e-6)) (torch.nn.utils.clip_grad_norm_; max_norm = +inf: exactly 1).
+ * guard[0 .. 4) <- {coef, norm, skipped, finite}.  total finite: finite = 1 and dev_state[1] (the step count of
+ * hupr_adam_step_dev_f32) += 1.  total not finite: coef = 0, finite = 0, skipped (guard[2], zeroed by the caller once) += 1
+ * and dev_state[1] stays. */
+int hupr_grad_guard_f32(const double* partials, int count, float gscale, float max_norm, float* dev_state, float* guard,
+                        hupr_stream_t stream);
+/* hupr_adam_step_dev_f32 / hupr_sgd_step_dev_f32 obeying guard: nothing is written when guard[3] == 0, otherwise the update
+ * runs on g * (gscale * guard[0]) (one fp32 product; with coef = 1 the bits of the _dev entries). */
+int hupr_adam_step_guard_f32(float* p, const float* g, float* exp_avg, float* exp_avg_sq, long n, const float* dev_state,
+                             const float* guard, float beta1, float beta2, float eps, float weight_decay, float gscale,
+                             hupr_stream_t stream);
+int hupr_sgd_step_guard_f32(float* p, const float* g, float* momentum_buf, long n, const float* dev_state, const float* guard,
+                            float momentum, float weight_decay, float gscale, hupr_stream_t stream);
+
 /* ---- bf16-activation variants ("bf16act") -------------------------------------------------------------
  * Same operators with the ACTIVATION tensors (x, y, dy, dx, residual) stored as bf16 in HBM; parameters,
  * statistics, weight gradients and all arithmetic stay fp32 (fp32 accumulate on the matrix pipe).  The
