@@ -270,19 +270,9 @@ __global__ void hupr_k_gaussian_targets(const long long* __restrict__ joints, co
 // ---- arg-max over HW per (b,k) row, first maximum wins (np.argmax) --------------------------------
 __global__ __launch_bounds__(64) void hupr_k_argmax_rows(const float* __restrict__ p, int n, int* __restrict__ idx,
                                                          float* __restrict__ maxval) {
-    const float* row = p + (long)blockIdx.x * n;
-    float best = -INFINITY;
-    int bi = 0x7fffffff;
-    for (int i = threadIdx.x; i < n; i += 64) {
-        const float v = row[i];
-        if (v > best || (v == best && i < bi)) { best = v; bi = i; }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(best, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
-    }
+    float best;
+    int bi;
+    wave_argmax_row(p + (long)blockIdx.x * n, n, threadIdx.x, best, bi);
     if (threadIdx.x == 0) { idx[blockIdx.x] = bi; maxval[blockIdx.x] = best; }
 }
 

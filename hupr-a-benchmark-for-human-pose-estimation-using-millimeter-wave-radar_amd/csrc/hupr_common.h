@@ -64,6 +64,24 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
+// Arg-max of one row of n floats by one 64-lane wave, first maximum wins (np.argmax): every lane returns with the same (best, bi).
+// A row without a value above -inf (all NaN, or n == 0) leaves bi = 0x7fffffff and best = -inf.  Shared by hupr_k_argmax_rows
+// (head.hip) and hupr_k_pose_decode (pose_decode.hip), so the two agree bit for bit.
+__device__ __forceinline__ void wave_argmax_row(const float* row, int n, int lane, float& best, int& bi) {
+    best = -INFINITY;
+    bi = 0x7fffffff;
+    for (int i = lane; i < n; i += 64) {
+        const float v = row[i];
+        if (v > best || (v == best && i < bi)) { best = v; bi = i; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(best, o, 64);
+        const int oi = __shfl_xor(bi, o, 64);
+        if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
+    }
+}
+
 // Activation storage helpers: 4 consecutive channels as fp32 (16 B) or bf16 (8 B), always computed on as fp32.
 typedef __bf16 hupr_bf16x4 __attribute__((ext_vector_type(4)));
 typedef float hupr_f32x4 __attribute__((ext_vector_type(4)));

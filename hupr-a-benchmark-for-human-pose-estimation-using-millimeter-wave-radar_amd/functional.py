@@ -1688,3 +1688,40 @@ def argmax_rows(p):
     mx = torch.empty(rows, dtype=torch.float32, device=p.device)
     rt.check(rt.lib().hupr_argmax_rows_f32(rt.ptr(p), rows, n, rt.ptr(idx), rt.ptr(mx), rt.stream()))
     return idx, mx
+
+
+def pose_filter_state(rows, device):
+    """A zero-filled ("never seen") One-Euro filter state for ``rows`` (sample, joint) rows: (rows, 8) fp32."""
+    n = int(rt.lib().hupr_pose_filter_state_bytes(rows)) // 4
+    return torch.zeros((rows, n // max(rows, 1)), dtype=torch.float32, device=device)
+
+
+def pose_decode(heat, ratio, refine=True, filter_state=None, smoothing=None):
+    """heat (..., H, W) fp32 GPU -> (idx int32 (...), maxval (...), raw keypoints (..., 2), filtered keypoints, velocity) in one launch
+    (csrc/pose_decode.hip; the rule is stated beside hupr_pose_decode_f32 in include/hupr.h).  ``idx`` / ``maxval`` are
+    ``argmax_rows``' bits; the keypoints are (x, y) in heat-map pixels times ``ratio``, refined to sub-pixel position unless
+    ``refine`` is false.  ``filter_state`` (``pose_filter_state``, advanced in place) together with ``smoothing`` (an object with
+    ``rate_hz``, ``min_cutoff``, ``beta``, ``d_cutoff``, ``min_score``: tools.stream.PoseSmoothing) adds the One-Euro filter: the
+    filtered keypoints and the velocity in pixels per second, both None without it.  Device tensors, no sync."""
+    if heat.dim() < 2:
+        raise ValueError("pose_decode needs (..., H, W) heat-maps, got shape %r" % (tuple(heat.shape),))
+    if heat.dtype != torch.float32:
+        raise ValueError("pose_decode needs fp32 heat-maps, got %s" % heat.dtype)
+    if (filter_state is None) != (smoothing is None):
+        raise ValueError("filter_state and smoothing go together")
+    heat = _c(heat)
+    lead, (H, W) = tuple(heat.shape[:-2]), heat.shape[-2:]
+    rows = int(np.prod(lead, dtype=np.int64))
+    idx = torch.empty(lead, dtype=torch.int32, device=heat.device)
+    mx = torch.empty(lead, dtype=torch.float32, device=heat.device)
+    raw = torch.empty(lead + (2,), dtype=torch.float32, device=heat.device)
+    kp = vel = None
+    params = (0.0,) * 5
+    if filter_state is not None:
+        if filter_state.dtype != torch.float32 or filter_state.numel() * 4 != int(rt.lib().hupr_pose_filter_state_bytes(rows)):
+            raise ValueError("filter_state must be the fp32 tensor pose_filter_state(%d, device) returns" % rows)
+        kp, vel = torch.empty_like(raw), torch.empty_like(raw)
+        params = tuple(float(getattr(smoothing, k)) for k in ("rate_hz", "min_cutoff", "beta", "d_cutoff", "min_score"))
+    rt.check(rt.lib().hupr_pose_decode_f32(rt.ptr(heat), rows, H, W, float(ratio), int(bool(refine)), rt.ptr(filter_state), *params,
+                                           rt.ptr(idx), rt.ptr(mx), rt.ptr(raw), rt.ptr(kp), rt.ptr(vel), rt.stream()))
+    return idx, mx, raw, kp, vel

@@ -3,7 +3,7 @@
 import torch
 
 from .. import functional as F_
-from .metrics import get_max_preds
+from .metrics import decode_setting, get_final_preds, get_max_preds
 
 PAIR_BCE = True      # test aid: False = one BCE node per head, combined by torch
 
@@ -18,6 +18,7 @@ class LossComputer():
         self.heatmapSize = self.width = self.height = cfg.DATASET.heatmapSize
         self.imgSize = self.imgWidth = self.imgHeight = cfg.DATASET.imgSize
         self.lossDecay = cfg.TRAINING.lossDecay
+        self.decode = decode_setting(cfg)       # TEST.decode: how the host-decode branch below turns preds2 into pred2d
         self.alpha = 0.0
         self.beta = 1.0
 
@@ -52,6 +53,7 @@ class LossComputer():
             # the reference decodes both arg-max sets every iteration (misc/losses.py:43-44); here the two decodes are
             # kernels on the step's stream and the (B,K) index / maximum tensors stay on the device (no sync, no D2H)
             return loss, loss2, F_.argmax_rows(preds2.detach().reshape(-1, H * W)), F_.argmax_rows(heatmaps.reshape(-1, H * W))
-        pred2d, _ = get_max_preds(preds2.detach().reshape(-1, K, H, W))
+        final = get_final_preds if self.decode == "subpixel" else get_max_preds
+        pred2d, _ = final(preds2.detach().reshape(-1, K, H, W))
         gt2d, _ = get_max_preds(heatmaps)
         return loss, loss2, pred2d, gt2d

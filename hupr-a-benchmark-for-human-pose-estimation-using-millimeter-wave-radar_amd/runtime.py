@@ -51,6 +51,9 @@ SIGNATURES = {
     "hupr_mnet_stream_f32": (c_int, [c_void_p] * 3 + [c_int, c_int] + [c_void_p] * 6 + [c_int] * 3 + [c_void_p]),
     "hupr_mnet_stream_bf16act": (c_int, [c_void_p] * 3 + [c_int, c_int] + [c_void_p] * 6 + [c_int] * 3 + [c_void_p]),
     "hupr_stream_keypoints_f32": (c_int, [c_void_p] * 3 + [c_long, c_int, c_float, c_void_p]),
+    # keypoint decode: arg-max + sub-pixel refinement + One-Euro filter (csrc/pose_decode.hip)
+    "hupr_pose_filter_state_bytes": (c_size_t, [c_long]),
+    "hupr_pose_decode_f32": (c_int, [c_void_p, c_long, c_int, c_int, c_float, c_int, c_void_p] + [c_float] * 5 + [c_void_p] * 6),
     "hupr_fft_chain_opts": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "hupr_loader_normalize_c64": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
     "hupr_dca1000_deinterleave": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),

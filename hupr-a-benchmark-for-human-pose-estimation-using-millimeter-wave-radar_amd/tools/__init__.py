@@ -1,7 +1,7 @@
 from .optim import FusedAdam, FusedSGD  # noqa: F401
 
 _STREAM = ("PoseStream", "PoseFrame", "StreamSchedule", "stream_window_sources", "StreamError", "LookaheadError",
-           "FrameShapeError", "FrameDtypeError", "StreamEndedError")
+           "FrameShapeError", "FrameDtypeError", "StreamEndedError", "PoseSmoothing", "DecodeError", "SmoothingError")
 
 
 def __getattr__(name):          # lazy: Runner pulls in datasets/models

@@ -15,11 +15,17 @@ The frame and pose counters the kernels read live on the device and are advanced
 depends on the frame number: with ``graph=True`` the steady-state push is ONE hipGraph replay (upload from pinned staging, FFT chain,
 window MNet, state advance, encoders / decoder / heads, arg-max, keypoint decode).
 
+Decode: by default the keypoint is the arg-max pixel times imgSize / heatmapSize, as the reference decodes it.  ``decode="subpixel"``
+refines the peak to sub-pixel position and ``smooth=PoseSmoothing(rate_hz)`` runs a One-Euro filter over the keypoints, its state on
+the device; either replaces the two decode launches by one (csrc/pose_decode.hip), inside the captured graph like them.
+
     python -m hupr_amd.tools.stream --config mscsa_prgcn.yaml --dir <logs name> --raw <dir with hori/ and vert/ adc_data.bin>
                                     [--lookahead N] [--math f32|bf16] [--no-graph] [--out poses.json]
+                                    [--decode argmax|subpixel] [--smooth --rate FPS]
 """
 import argparse
 import json
+import math
 import os
 
 import numpy as np
@@ -50,6 +56,49 @@ class FrameDtypeError(StreamError):
 
 class StreamEndedError(StreamError):
     """push() after flush(): the sequence has ended, reset() starts the next one."""
+
+
+class DecodeError(StreamError):
+    """``decode`` is neither "argmax" nor "subpixel"."""
+
+
+class SmoothingError(StreamError):
+    """A ``PoseSmoothing`` parameter out of range, or ``smooth`` is not a ``PoseSmoothing``."""
+
+
+DECODES = ("argmax", "subpixel")
+
+
+class PoseSmoothing:
+    """One-Euro filter settings (Casiez et al.) of a session: ``rate_hz`` the frame rate of the stream, ``min_cutoff`` (Hz) the
+    cut-off at rest, ``beta`` its growth per pixel / second of speed, ``d_cutoff`` (Hz) the cut-off of the velocity estimate.  A
+    joint whose score is <= ``min_score`` (or whose keypoint is not finite) is missing: it holds its last filtered position, reports
+    zero velocity and leaves the filter state alone."""
+    __slots__ = ("rate_hz", "min_cutoff", "beta", "d_cutoff", "min_score")
+
+    def __init__(self, rate_hz, min_cutoff=1.0, beta=0.01, d_cutoff=1.0, min_score=0.0):
+        vals = dict(rate_hz=rate_hz, min_cutoff=min_cutoff, beta=beta, d_cutoff=d_cutoff, min_score=min_score)
+        for k, v in vals.items():
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(v):
+                raise SmoothingError("PoseSmoothing.%s must be a finite number, got %r" % (k, v))
+        for k in ("rate_hz", "min_cutoff", "d_cutoff"):
+            if not vals[k] > 0:
+                raise SmoothingError("PoseSmoothing.%s must be positive, got %r" % (k, vals[k]))
+        if beta < 0:
+            raise SmoothingError("PoseSmoothing.beta must not be negative, got %r" % (beta,))
+        for k, v in vals.items():
+            setattr(self, k, float(v))
+
+    def __repr__(self):
+        return "PoseSmoothing(%s)" % ", ".join("%s=%r" % (k, getattr(self, k)) for k in self.__slots__)
+
+
+def check_decode(decode, smooth):
+    """The session's decode arguments: ``decode`` one of DECODES, ``smooth`` None or a PoseSmoothing."""
+    if decode not in DECODES:
+        raise DecodeError("decode must be 'argmax' or 'subpixel', got %r" % (decode,))
+    if smooth is not None and not isinstance(smooth, PoseSmoothing):
+        raise SmoothingError("smooth must be a PoseSmoothing or None, got %r" % (smooth,))
 
 
 def stream_window_sources(center, newest, G):
@@ -123,17 +172,21 @@ class StreamSchedule:
 
 
 class PoseFrame:
-    """One emitted pose.  ``frame``: its number in the stream; ``keypoints`` (lanes, K, 2) fp32 image pixels (x, y); ``scores``
-    (lanes, K) the GCN head's maxima; ``indices`` (lanes, K) int32 arg-max positions; ``heatmap`` (lanes, K, 1, H, W) and
-    ``gcn_heatmap`` (lanes, 1, K, H, W).  Device tensors owned by the session, valid until its next push / flush / reset."""
-    __slots__ = ("frame", "keypoints", "scores", "indices", "heatmap", "gcn_heatmap")
+    """One emitted pose.  ``frame``: its number in the stream; ``keypoints`` (lanes, K, 2) fp32 image pixels (x, y) — the One-Euro
+    filtered ones when the session smooths; ``scores`` (lanes, K) the GCN head's maxima; ``indices`` (lanes, K) int32 arg-max
+    positions; ``heatmap`` (lanes, K, 1, H, W) and ``gcn_heatmap`` (lanes, 1, K, H, W); ``raw_keypoints`` the decoded keypoints in
+    front of the filter (``keypoints`` itself without one); ``velocity`` (lanes, K, 2) image pixels per second, None without a
+    filter.  Device tensors owned by the session, valid until its next push / flush / reset."""
+    __slots__ = ("frame", "keypoints", "scores", "indices", "heatmap", "gcn_heatmap", "raw_keypoints", "velocity")
 
-    def __init__(self, frame, keypoints, scores, indices, heatmap, gcn_heatmap):
+    def __init__(self, frame, keypoints, scores, indices, heatmap, gcn_heatmap, raw_keypoints=None, velocity=None):
         self.frame, self.keypoints, self.scores, self.indices = frame, keypoints, scores, indices
         self.heatmap, self.gcn_heatmap = heatmap, gcn_heatmap
+        self.raw_keypoints = keypoints if raw_keypoints is None else raw_keypoints
+        self.velocity = velocity
 
     def _map(self, fn):
-        return PoseFrame(self.frame, *[fn(getattr(self, k)) for k in self.__slots__[1:]])
+        return PoseFrame(self.frame, *[None if getattr(self, k) is None else fn(getattr(self, k)) for k in self.__slots__[1:]])
 
     def clone(self):
         return self._map(torch.clone)
@@ -153,13 +206,17 @@ class PoseStream:
     the replay.  A push waits for the previous one to finish before it reuses the pinned staging.  Side effect: like ``engine.infer``,
     ``push`` and ``flush`` put a model that is in training mode into eval mode (``model.eval()``) and leave it there.  ``lanes = 2`` is
     the model at batch 2: bit-identical to the offline route on a batch of 2, not to two ``lanes = 1`` sessions (the existing kernels
-    take other launch routes for a single sample)."""
+    take other launch routes for a single sample).  ``decode="subpixel"`` refines every keypoint to sub-pixel
+    position; ``smooth=PoseSmoothing(rate_hz, ...)`` filters the keypoints over time (the filter state is the session's, ``reset()``
+    clears it) and adds ``PoseFrame.velocity``.  With the defaults the session decodes exactly as before, in the same two launches."""
 
-    def __init__(self, model, cfg, lanes=1, lookahead=None, graph=True, device=None):
+    def __init__(self, model, cfg, lanes=1, lookahead=None, graph=True, device=None, decode="argmax", smooth=None):
         D = cfg.DATASET
         self.G = D.numGroupFrames
         self.schedule = StreamSchedule(self.G, lookahead)
         self.lookahead = self.schedule.lookahead
+        check_decode(decode, smooth)
+        self.decode, self.smooth = decode, smooth
         if not isinstance(lanes, int) or lanes < 1:
             raise StreamError("lanes must be a positive integer, got %r" % (lanes,))
         self.device = torch.device(device) if device is not None else next(model.parameters()).device
@@ -190,6 +247,13 @@ class PoseStream:
             self._idx = torch.empty((lanes, self.K), dtype=torch.int32, device=dev)
             self._mx = torch.empty((lanes, self.K), dtype=torch.float32, device=dev)
             self._kp = torch.empty((lanes, self.K, 2), dtype=torch.float32, device=dev)
+            # the one-launch decode (csrc/pose_decode.hip) serves everything but the default; with a filter _kp holds the filtered
+            # keypoints, _raw the decoded ones, _vel the velocity, _fstate the filter's state
+            self._fused = decode != "argmax" or smooth is not None
+            self._raw = self._vel = self._fstate = None
+            if smooth is not None:
+                self._raw, self._vel = torch.empty_like(self._kp), torch.empty_like(self._kp)
+                self._fstate = F_.pose_filter_state(lanes * self.K, dev)
             self._done = torch.cuda.Event()
         self._graphs = {}              # "host" / "device" input -> (CUDAGraph, (heatmap, gcn_heatmap))
         self._eager_emits = 0
@@ -229,6 +293,14 @@ class PoseStream:
         heat, gcn = self.model.forward_chirp_maps(*self._maps)
         L, s = rt.lib(), rt.stream()
         rows = self.lanes * self.K
+        if self._fused:
+            f = self.smooth
+            params = (0.0,) * 5 if f is None else (f.rate_hz, f.min_cutoff, f.beta, f.d_cutoff, f.min_score)
+            rt.check(L.hupr_pose_decode_f32(rt.ptr(F_._c(gcn)), rows, self.H, self.W, self.ratio, int(self.decode == "subpixel"),
+                                            rt.ptr(self._fstate), *params, rt.ptr(self._idx), rt.ptr(self._mx),
+                                            rt.ptr(self._kp if f is None else self._raw), rt.ptr(None if f is None else self._kp),
+                                            rt.ptr(self._vel), s))
+            return heat, gcn
         rt.check(L.hupr_argmax_rows_f32(rt.ptr(F_._c(gcn)), rows, self.H * self.W, rt.ptr(self._idx), rt.ptr(self._mx), s))
         rt.check(L.hupr_stream_keypoints_f32(rt.ptr(self._idx), rt.ptr(self._mx), rt.ptr(self._kp), rows, self.W, self.ratio, s))
         return heat, gcn
@@ -250,7 +322,7 @@ class PoseStream:
             self._busy = False
 
     def _frame(self, center, out):
-        return PoseFrame(center, self._kp, self._mx, self._idx, out[0], out[1])
+        return PoseFrame(center, self._kp, self._mx, self._idx, out[0], out[1], self._raw, self._vel)
 
     # -- public ---------------------------------------------------------------------------------------------------------------
     def push(self, adc_hori, adc_vert):
@@ -301,6 +373,8 @@ class PoseStream:
     def reset(self):
         with torch.cuda.device(self.device):
             rt.check(rt.lib().hupr_stream_reset(rt.ptr(self._state), rt.stream()))
+            if self._fstate is not None:
+                self._fstate.zero_()                           # "never seen": the next valid sample of a joint starts its filter
         self.schedule.reset()
 
 
@@ -314,7 +388,13 @@ def parse(argv=None):
     p.add_argument("--math", choices=("f32", "bf16"), default=None, help="precision mode (default: the process default)")
     p.add_argument("--no-graph", action="store_true", help="eager launches instead of one hipGraph replay per frame")
     p.add_argument("--out", type=str, default="poses.json")
-    return p.parse_args(argv)
+    p.add_argument("--decode", choices=DECODES, default="argmax", help="argmax: the reference's decode; subpixel: refined peaks")
+    p.add_argument("--smooth", action="store_true", help="One-Euro filter over the keypoints (needs --rate); adds the velocity")
+    p.add_argument("--rate", type=float, default=None, help="frames per second of the capture (required with --smooth)")
+    args = p.parse_args(argv)
+    if args.smooth and args.rate is None:
+        p.error("--smooth needs --rate (frames per second)")
+    return args
 
 
 def load_model_best(model, log_dir, device):
@@ -352,12 +432,15 @@ def main(argv=None):
         raw = torch.from_numpy(np.fromfile(os.path.join(args.raw, sensor, "adc_data.bin"), dtype=np.int16)).to(dev)
         frames.append(dca1000_frames(raw))                      # (frames, 4, 192, 256, 2) int16, de-interleaved on the GPU
     n = min(frames[0].shape[0], frames[1].shape[0])
-    session = PoseStream(model, cfg, lanes=1, lookahead=args.lookahead, graph=not args.no_graph, device=dev)
+    session = PoseStream(model, cfg, lanes=1, lookahead=args.lookahead, graph=not args.no_graph, device=dev, decode=args.decode,
+                         smooth=PoseSmoothing(args.rate) if args.smooth else None)
     records = []
 
     def record(pf):
         kp = np.concatenate([pf.keypoints.cpu().numpy()[0], pf.scores.cpu().numpy()[0][:, None]], axis=1)
         records.append({"frame": int(pf.frame), "keypoints": [[float(x), float(y), float(s)] for x, y, s in kp]})
+        if pf.velocity is not None:
+            records[-1]["velocity"] = [[float(vx), float(vy)] for vx, vy in pf.velocity.cpu().numpy()[0]]
 
     for i in range(n):
         pf = session.push(frames[0][i:i + 1], frames[1][i:i + 1])

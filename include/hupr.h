@@ -317,6 +317,32 @@ int hupr_mnet_stream_bf16act(const float* staging_or_null, float* ring, const vo
  * maximum is <= 0 — the decode of misc/metrics.py:10-38 scaled as tools/run.py:47-53 hands it to saveKeypoints */
 int hupr_stream_keypoints_f32(const int* idx, const float* maxval, float* keypoints, long rows, int W, float ratio,
                               hupr_stream_t stream);
+/* Keypoint decode in one launch (csrc/pose_decode.hip): arg-max, sub-pixel refinement and, with a filter state, One-Euro smoothing.
+ * Extends the decode of misc/metrics.py:10-38; one 64-lane wave per row, no scratch, no LDS.
+ * heat : float [rows][H][W].  idx / maxval [rows]: the bits of hupr_argmax_rows_f32 (first maximum wins).
+ * With the peak at (px, py) = (idx % W, idx / W) and h the row as H x W, the offset (ox, oy) in heat-map pixels is
+ *   (0, 0) when refine == 0, when maxval <= 0, or when the peak lies on the map border (px in {0, W-1} or py in {0, H-1});
+ *   else, with l = logf(fmaxf(h, 1e-10f)) on the 3 x 3 neighbourhood (a NaN neighbour counts as a non-finite log),
+ *     dx = 0.5 (l[x+1] - l[x-1]), dxx = l[x+1] - 2 l[x] + l[x-1] (dy, dyy likewise),
+ *     dxy = 0.25 (l[x+1,y+1] - l[x-1,y+1] - l[x+1,y-1] + l[x-1,y-1]), det = dxx dyy - dxy^2:
+ *     if dxx < 0 and det > 0, the Taylor step (-(dyy dx - dxy dy) / det, -(dxx dy - dxy dx) / det), each component clamped to
+ *     [-0.5, 0.5] (Zhang et al., DARK); otherwise the quarter rule 0.25 sign(h[x+1] - h[x-1]) per axis, sign(0) = 0;
+ *   (0, 0) when one of the nine logs or an unclamped offset is not finite.
+ * raw_keypoints [rows][2] = ((px + ox) * ratio, (py + oy) * ratio), (0, 0) where maxval <= 0.  With refine == 0 these are the floats of
+ * hupr_argmax_rows_f32 followed by hupr_stream_keypoints_f32.
+ * filter_state_or_null : float [rows][8] = (x^, y^, dx^, dy^, valid, 3 x pad), hupr_pose_filter_state_bytes(rows) bytes; all zero =
+ *   never seen.  Null: no filter, keypoints_or_null and velocity_or_null must be null and the five parameters are ignored.
+ *   Otherwise rate_hz, min_cutoff, d_cutoff > 0 and beta >= 0 (One-Euro filter, Casiez et al.), a(fc) = 1 / (1 + rate_hz / (2 pi fc)).
+ *   A joint is missing when maxval <= min_score or its raw keypoint is not finite: keypoints = (x^, y^) if the state is valid, else
+ *   the raw keypoint; velocity = 0; the state is untouched.  The first sample that is not missing sets x^ = x, dx^ = 0, valid = 1.
+ *   After that, per axis: dx = (x - x^) rate_hz; dx^ = a(d_cutoff) dx + (1 - a(d_cutoff)) dx^; fc = min_cutoff + beta |dx^|;
+ *   x^ = a(fc) x + (1 - a(fc)) x^.  keypoints_or_null [rows][2] = (x^, y^), velocity_or_null [rows][2] = (dx^, dy^) in image pixels
+ *   per second.  The parameters are launch arguments, i.e. constants of a captured graph; the state advances with every launch.
+ * rows == 0 is a no-op. */
+size_t hupr_pose_filter_state_bytes(long rows);
+int hupr_pose_decode_f32(const float* heat, long rows, int H, int W, float ratio, int refine, float* filter_state_or_null,
+                         float rate_hz, float min_cutoff, float beta, float d_cutoff, float min_score, int* idx, float* maxval,
+                         float* raw_keypoints, float* keypoints_or_null, float* velocity_or_null, hupr_stream_t stream);
 
 /* tri-/bilinear align_corners=True resampling (models/layers.py:84,89,199,204; gcn_networks.py:49,63) */
 int hupr_interp_linear_fwd_f32(const float* x, float* y, int Bn, int Di, int Hi, int Wi, int Do, int Ho, int Wo,

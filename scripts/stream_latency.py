@@ -10,7 +10,11 @@
 Device events around every frame, a host clock around every block (ending in a synchronise); the routes alternate block by block.
 Medians over all frames, and the spread of (a) as the range of its block medians.
 
+--decode subpixel and / or --smooth (a One-Euro filter at --rate frames per second) put the one-launch decode of
+csrc/pose_decode.hip at the tail of route (a) in place of arg-max + keypoints; run once without and once with them to compare.
+
 usage: python scripts/stream_latency.py [--frames 512] [--blocks 8] [--math bf16|f32] [--out profiles/stream_latency.txt]
+                                        [--decode argmax|subpixel] [--smooth [--rate 10]]
        python scripts/stream_latency.py --trace-frames 64        (eager session only: the run to put under
                                                                   rocprofv3 --kernel-trace --stats for hupr_k_mnet_stream)"""
 import argparse
@@ -26,7 +30,7 @@ import torch
 from hupr_amd import runtime as rt, synth
 from hupr_amd.config_tree import load_config
 from hupr_amd.models import HuPRNet
-from hupr_amd.tools.stream import ADC_SHAPE, PoseStream, stream_window_sources
+from hupr_amd.tools.stream import ADC_SHAPE, PoseSmoothing, PoseStream, stream_window_sources
 
 p = argparse.ArgumentParser()
 p.add_argument("--frames", type=int, default=512)
@@ -34,7 +38,11 @@ p.add_argument("--blocks", type=int, default=8)
 p.add_argument("--math", choices=("f32", "bf16"), default="bf16")
 p.add_argument("--trace-frames", type=int, default=0)
 p.add_argument("--out", type=str, default=None)
+p.add_argument("--decode", choices=("argmax", "subpixel"), default="argmax")
+p.add_argument("--smooth", action="store_true")
+p.add_argument("--rate", type=float, default=10.0)
 args = p.parse_args()
+decode_kw = dict(decode=args.decode, smooth=PoseSmoothing(args.rate) if args.smooth else None)
 if not torch.cuda.is_available():
     raise SystemExit("stream_latency.py measures on the GPU; none is visible")
 
@@ -48,7 +56,7 @@ POOL = 24                                              # distinct synthetic fram
 pool = [[torch.from_numpy(synth.adc_cube_int16(9, frame=f, sensor=s)).pin_memory() for s in range(2)] for f in range(POOL)]
 
 if args.trace_frames:
-    s = PoseStream(model, cfg, graph=False)
+    s = PoseStream(model, cfg, graph=False, **decode_kw)
     for n in range(args.trace_frames):
         s.push(pool[n % POOL][0], pool[n % POOL][1])
     s.flush()
@@ -57,7 +65,7 @@ if args.trace_frames:
     raise SystemExit(0)
 
 L = rt.lib()
-session = PoseStream(model, cfg, graph=True)
+session = PoseStream(model, cfg, graph=True, **decode_kw)
 
 # (b) / (b1): static buffers, the window gathered on the host into pinned memory the way a caller without a session would
 win_pinned = torch.empty((2, G) + ADC_SHAPE, dtype=torch.int16).pin_memory()
@@ -144,8 +152,9 @@ for b in range(args.blocks):
         block_medians[name].append(statistics.median(t))
     n += per_block
 
-lines = ["stream_latency.py --frames %d --blocks %d --math %s   (lanes 1, G %d, lookahead %d; %s)"
-         % (args.frames, args.blocks, args.math, G, session.lookahead, torch.cuda.get_device_name(0)),
+lines = ["stream_latency.py --frames %d --blocks %d --math %s --decode %s%s   (lanes 1, G %d, lookahead %d; %s)"
+         % (args.frames, args.blocks, args.math, args.decode, " --smooth --rate %g" % args.rate if args.smooth else "", G,
+            session.lookahead, torch.cuda.get_device_name(0)),
          "route  frames  device-event median ms  [block medians min .. max]  host clock ms/frame (mean of blocks)"]
 label = {"a": "(a)  PoseStream.push, one graph replay", "b": "(b)  window upload + FFT eager, graph forward + arg-max",
          "b1": "(b1) window upload + FFT + forward + arg-max in one graph"}
