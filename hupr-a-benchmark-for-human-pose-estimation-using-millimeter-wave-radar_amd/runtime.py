@@ -169,6 +169,10 @@ SIGNATURES = {
     "hupr_grad_guard_f32": (c_int, [c_void_p, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p]),
     "hupr_adam_step_guard_f32": (c_int, [c_void_p] * 4 + [c_long, c_void_p, c_void_p] + [c_float] * 5 + [c_void_p]),
     "hupr_sgd_step_guard_f32": (c_int, [c_void_p] * 3 + [c_long, c_void_p, c_void_p] + [c_float] * 3 + [c_void_p]),
+    # averaged weights (csrc/weight_ema.hip)
+    "hupr_ema_tick_f32": (c_int, [c_void_p, c_float, c_void_p, c_void_p]),
+    "hupr_ema_update_f32": (c_int, [c_void_p, c_void_p, c_long, c_void_p, c_void_p]),
+    "hupr_swap_f32": (c_int, [c_void_p, c_void_p, c_long, c_void_p]),
     # bf16-activation variants (same argument lists as their fp32-activation counterparts)
     "hupr_conv3x3_halo_bf16act": (c_int, [c_void_p] * 5 + [c_int] * 10 + [c_void_p]),
     "hupr_conv3x3_halo_splitk_ws_bytes": (c_size_t, [c_int] * 7),

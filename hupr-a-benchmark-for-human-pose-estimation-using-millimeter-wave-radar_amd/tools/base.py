@@ -79,9 +79,18 @@ class BaseRunner():
         for group in self.optimizer.param_groups:
             group["lr"] *= factor
 
+    def _ema(self):
+        """The engine's weight average (TRAINING.emaDecay), or None."""
+        return getattr(getattr(self, "engine", None), "ema", None)
+
     def _checkpoint_dict(self, epoch):
-        return {"epoch": epoch, "model_state_dict": self.model.state_dict(),
-                "optimizer_state_dict": self.optimizer.state_dict(), "accuracy": self.logger.showBestAP()}
+        group = {"epoch": epoch, "model_state_dict": self.model.state_dict(),
+                 "optimizer_state_dict": self.optimizer.state_dict(), "accuracy": self.logger.showBestAP()}
+        ema = self._ema()
+        if ema is not None:                  # TRAINING.emaDecay: two more keys; without it exactly the reference's four
+            group["ema_state_dict"] = ema.state_dict(self.model)
+            group["ema_updates"] = ema.stats()["updates"]
+        return group
 
     def saveModelWeight(self, epoch, acc):
         best = self.logger.isBestAccAP(acc)
@@ -112,7 +121,14 @@ class BaseRunner():
             print("==========>Train the model from scratch")
             return
         ck = torch.load(path, map_location=self.device)
-        self.model.load_state_dict(ck["model_state_dict"])
+        ema = self._ema()
+        if ema is not None and self.args.eval and "ema_state_dict" in ck:
+            self.model.load_state_dict(ck["ema_state_dict"])
+            print("==========>Load the averaged weights (ema_state_dict, %d updates)" % ck.get("ema_updates", 0))
+        else:
+            self.model.load_state_dict(ck["model_state_dict"])
+            if ema is not None:
+                print("==========>Load the trained weights (model_state_dict)")
         side = os.path.join(self.dir, "preprocess.json")
         if os.path.exists(side):
             from ..preprocessing import process_iwr1843 as _pre
@@ -130,4 +146,12 @@ class BaseRunner():
             self.optimizer.load_state_dict(ck["optimizer_state_dict"])      # TRAINING.optimizer's torch layout (optim.SGD / optim.Adam)
             self.start_epoch = ck["epoch"]
             self.logger.updateBestAcc(ck["accuracy"])
+        if ema is not None and not self.args.eval:
+            if not getattr(self.args, "pretrained", False) and "ema_state_dict" in ck and "ema_updates" in ck:
+                ema.load_state_dict(ck["ema_state_dict"], ck["ema_updates"])
+                print("==========>Load the previous weight average (%d updates)" % ck["ema_updates"])
+            else:
+                ema.reset()
+                print("==========>NOTE: TRAINING.emaDecay is set but no weight average is taken from this checkpoint: the average starts "
+                      "from the loaded weights at 0 updates")
         print("==========>Load the model weight from %s, saved at epoch %d" % (self.dir, ck["epoch"]))

@@ -2,6 +2,7 @@
 flat gradient buckets (+ RCCL all-reduce when world_size > 1) + fused Adam or SGD, optionally fed by the
 on-GPU FFT loader (int16 ADC cubes -> normalised network input, config "C3" of BASELINE.json)."""
 
+import contextlib
 import os
 
 import torch
@@ -11,6 +12,7 @@ from ..misc.losses import LossComputer
 from ..models import HuPRNet
 from ..preprocessing.process_iwr1843 import fft_chain_loader, fft_chain_loader_means
 from .distributed import GradientBuckets
+from .ema import WeightEMA, ema_decay_setting
 from .optim import make_optimizer
 
 
@@ -33,6 +35,10 @@ class TrainEngine:
         # the update (so the norm is that of the mean gradient over ranks and micro-batches, identical on every rank)
         if self.optimizer.grad_clip is not None:
             self.optimizer.enable_grad_guard(self.optimizer.grad_clip)
+        # TRAINING.emaDecay: the averaged weights, one flat tensor per bucket, updated on the device behind every optimiser step.
+        # Built after broadcast_parameters: every rank starts from the same weights and computes the same average, no exchange
+        decay = ema_decay_setting(cfg)
+        self.ema = WeightEMA(self.buckets.flat_pairs(), self.buckets.layout(), decay, module=self.model) if decay is not None else None
         self.G = cfg.DATASET.numGroupFrames
         self.fuse_elevation_mean = os.environ.get("HUPR_NO_FUSED_MEAN", "0") != "1"
         self._fft_ws = None
@@ -73,6 +79,7 @@ class TrainEngine:
         arg-max decodes of the reference's per-iteration ``computeLoss`` (misc/losses.py:43-44) as kernels on the
         step's stream; their results stay on the device (``self.last_decode``)."""
         from .. import functional as F_
+        self._refuse_while_swapped("train_step")
         self.model.train()
         self.buckets.prepare(reduce=_last)
         F_.BN_COUNTER_SINK = due = []
@@ -99,6 +106,8 @@ class TrainEngine:
         self.buckets.finish()
         self.optimizer.grad_scale = 1.0 / (self.world_size * _micro)
         self.optimizer.step()
+        if self.ema is not None:                            # a step the guard skipped leaves the average and its count alone
+            self.ema.update(guard=self.optimizer._guard)
         return loss, loss2
 
     def train_step_accumulated(self, micro_batches, from_adc=True, decode=False):
@@ -116,6 +125,7 @@ class TrainEngine:
 
     def train_step_from_adc(self, adc_hori, adc_vert, joints, decode=False):
         if self._graph is not None:
+            self._refuse_while_swapped("train_step")
             return self._replay(adc_hori, adc_vert, joints)
         h, v = self.preprocess(adc_hori, adc_vert)
         return self.train_step(h, v, joints, decode=decode)
@@ -130,8 +140,10 @@ class TrainEngine:
         in lock step.  Requirements: fixed shapes (the static input buffers are refilled by copy), joints already on
         the device (a pageable host-to-device copy is illegal inside a capture), ``TRAINING.lossDecay == -1`` (the
         alpha/beta loss weights would be frozen at their capture-time values), ``sync_lr()`` after LR changes.
-        The gradient guard (``TRAINING.gradClip``) is device-side and replays with the step.
+        The gradient guard (``TRAINING.gradClip``) and the weight average (``TRAINING.emaDecay``) are device-side and replay with
+        the step.
         The ``warmup`` eager steps are real optimisation steps."""
+        self._refuse_while_swapped("capture")
         tr = self.buckets.transport
         if self.buckets.active and not getattr(tr, "capturable", False):
             raise RuntimeError("graph capture needs the native RCCL transport (got %s)" % getattr(tr, "name", tr))
@@ -165,6 +177,40 @@ class TrainEngine:
         device: per epoch, not per step.  A skipped step leaves parameters, optimiser state and step count as they were; the
         BatchNorm running statistics of its forward pass have moved all the same (as under torch's GradScaler)."""
         return self.optimizer.guard_stats()
+
+    # -- averaged weights (TRAINING.emaDecay) -----------------------------------------------------------------------------------
+    def ema_stats(self):
+        """With ``TRAINING.emaDecay`` set: {"updates": updates of the average so far (skipped steps do not count), "weight": the
+        last step's weight 1 - min(decay, (1 + k) / (10 + k)), 0.0 for a skipped step}; None otherwise.  Synchronises the device:
+        per epoch, not per step."""
+        return self.ema.stats() if self.ema is not None else None
+
+    def _refuse_while_swapped(self, what):
+        if self.ema is not None and self.ema.swapped:
+            raise RuntimeError("%s inside averaged_weights(): the parameters hold the average, not the trained weights" % what)
+
+    def _swap_weights(self):
+        from .. import functional as F_
+        self.ema.swap()
+        F_.invalidate_packed()      # the parameters changed behind every host-side cache, as after a graph replay (_replay)
+        if self.keep_inference_graphs_current:
+            F_.refresh_packed(self.device)
+
+    @contextlib.contextmanager
+    def averaged_weights(self):
+        """``with engine.averaged_weights():`` — the model's parameters are the averaged weights inside the block (``infer``,
+        ``Runner.eval``) and the trained ones again behind it: parameters and average are exchanged in place, one launch per
+        bucket each way, every bit kept.  Buffers are not touched: the BatchNorm running statistics are the live ones.  No
+        training step, no capture and no second ``averaged_weights()`` inside the block."""
+        if self.ema is None:
+            raise RuntimeError("averaged_weights() needs TRAINING.emaDecay")
+        if self.ema.swapped:
+            raise RuntimeError("averaged_weights() is already active (no nesting)")
+        self._swap_weights()
+        try:
+            yield self
+        finally:
+            self._swap_weights()
 
     def _replay(self, adc_hori, adc_vert, joints):
         for dst, src in zip(self._g_in, (adc_hori, adc_vert, joints)):

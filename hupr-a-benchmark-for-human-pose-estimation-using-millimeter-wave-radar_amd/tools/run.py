@@ -5,6 +5,7 @@ Differences that are the point of this build: the step runs through ``TrainEngin
 flat gradient buckets, RCCL all-reduce when launched under torchrun), the FFT preprocessing can run
 on the GPU inside the step (synthetic/raw-ADC datasets), and losses are not synchronised every step.
 """
+import contextlib
 import os
 
 import numpy as np
@@ -125,6 +126,10 @@ class Runner(BaseRunner):
         return ap
 
     def train(self):
+        averaged = self.engine.ema is not None
+        if averaged and self.rank == 0:
+            print("==========>TRAINING.emaDecay = %g: each epoch is evaluated, and model_best.pth chosen, with the averaged weights"
+                  % self.engine.ema.decay)
         for epoch in range(self.start_epoch, self.cfg.TRAINING.epochs):
             loss_list = []
             guard0 = self.engine.guard_stats()
@@ -144,7 +149,8 @@ class Runner(BaseRunner):
                 skipped = self.engine.guard_stats()["skipped"] - guard0["skipped"]
                 if skipped and self.rank == 0:
                     print("==========>Skipped %d optimizer step(s) with non-finite gradients in epoch %d" % (skipped, epoch))
-            accAP = self.eval(visualization=False, epoch=epoch)
+            with self.engine.averaged_weights() if averaged else contextlib.nullcontext():
+                accAP = self.eval(visualization=False, epoch=epoch)
             if self.rank == 0:
                 self.saveModelWeight(epoch, accAP)
                 self.saveLosslist(epoch, [float(l) for l in loss_list], "train")

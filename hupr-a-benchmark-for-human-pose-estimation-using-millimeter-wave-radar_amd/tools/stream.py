@@ -67,6 +67,7 @@ class SmoothingError(StreamError):
 
 
 DECODES = ("argmax", "subpixel")
+WEIGHTS = ("live", "averaged")      # which parameters of model_best.pth: as trained, or their moving average (TRAINING.emaDecay)
 
 
 class PoseSmoothing:
@@ -391,20 +392,33 @@ def parse(argv=None):
     p.add_argument("--decode", choices=DECODES, default="argmax", help="argmax: the reference's decode; subpixel: refined peaks")
     p.add_argument("--smooth", action="store_true", help="One-Euro filter over the keypoints (needs --rate); adds the velocity")
     p.add_argument("--rate", type=float, default=None, help="frames per second of the capture (required with --smooth)")
+    p.add_argument("--weights", choices=WEIGHTS, default="live", help="live: model_state_dict as trained; averaged: ema_state_dict "
+                   "(a run with TRAINING.emaDecay)")
     args = p.parse_args(argv)
     if args.smooth and args.rate is None:
         p.error("--smooth needs --rate (frames per second)")
     return args
 
 
-def load_model_best(model, log_dir, device):
-    """``model_best.pth`` of ``log_dir`` into ``model``, the way Runner.loadModelWeight reads it for evaluation."""
+def load_model_best(model, log_dir, device, weights="live"):
+    """``model_best.pth`` of ``log_dir`` into ``model``, the way Runner.loadModelWeight reads it for evaluation.  ``weights``:
+    ``"live"`` = ``model_state_dict``, the parameters as trained; ``"averaged"`` = ``ema_state_dict``, their moving average, which
+    only a run with ``TRAINING.emaDecay`` saved."""
+    if weights not in WEIGHTS:
+        raise ValueError("weights must be one of %s, got %r" % (", ".join(WEIGHTS), weights))
     from ..preprocessing import process_iwr1843 as pre
     path = os.path.join(log_dir, "model_best.pth")
     if not os.path.exists(path):
         raise FileNotFoundError("%s not found" % path)
     ck = torch.load(path, map_location=device)
-    model.load_state_dict(ck["model_state_dict"])
+    if weights == "averaged":
+        if "ema_state_dict" not in ck:
+            raise KeyError("%s holds no averaged weights (ema_state_dict): it was trained without TRAINING.emaDecay; use "
+                           "--weights live" % path)
+        model.load_state_dict(ck["ema_state_dict"])
+        print("==========>Load the averaged weights (ema_state_dict, %d updates)" % ck.get("ema_updates", 0))
+    else:
+        model.load_state_dict(ck["model_state_dict"])
     side = os.path.join(log_dir, "preprocess.json")
     if os.path.exists(side):
         with open(side) as fp:
@@ -424,7 +438,7 @@ def main(argv=None):
     dev = torch.device("cuda", torch.cuda.current_device())
     cfg = load_config(args.config, "./config" if os.path.isdir("./config") else None)
     model = HuPRNet(cfg).to(dev).eval()
-    load_model_best(model, os.path.join("./logs", args.dir), dev)
+    load_model_best(model, os.path.join("./logs", args.dir), dev, weights=args.weights)
     if args.math is not None:
         model.math_mode = args.math
     frames = []

@@ -533,6 +533,23 @@ int hupr_adam_step_guard_f32(float* p, const float* g, float* exp_avg, float* ex
 int hupr_sgd_step_guard_f32(float* p, const float* g, float* momentum_buf, long n, const float* dev_state, const float* guard,
                             float momentum, float weight_decay, float gscale, hupr_stream_t stream);
 
+/* (a12) Exponential moving average of the weights, kept and swapped on the device (csrc/weight_ema.hip; TRAINING.emaDecay).
+ * New, no reference counterpart: the reference evaluates `self.model` as trained, `tools/run.py:35-63`.  Per optimiser step and
+ * stream, behind the optimiser's launches: hupr_ema_tick_f32 once, then hupr_ema_update_f32 once per parameter bucket.
+ * No atomics: results are bit-identical from run to run.  All of it is stream-ordered and capturable in a hipGraph. */
+/* ema_state[0 .. 2) = {updates, weight} in device memory.  guard: null, or the 4 floats of hupr_grad_guard_f32.  guard given and
+ * guard[3] == 0 (the step was skipped): weight = 0, updates stays.  Otherwise, k = updates: d = min(decay, (1 + k) / (10 + k)) in
+ * fp64 (the warm-up ramp: the first updates are not dominated by the initial weights), weight = (float)(1 - d), updates = k + 1.
+ * One thread.  decay must be inside (0, 1). */
+int hupr_ema_tick_f32(float* ema_state, float decay, const float* guard, hupr_stream_t stream);
+/* ema[i] += w * (p[i] - ema[i]) over [0, n), w = ema_state[1]: one fp32 subtraction and one fused multiply-add per element, the
+ * same bits whichever path runs.  w == 0 stores nothing (the bits of ema are kept, whatever p holds).  ema and p may start at any
+ * 4-byte boundary: float4 accesses from the first 16-byte boundary and scalar ends when both share their offset to it, 4-byte
+ * accesses otherwise.  ema and p must not overlap. */
+int hupr_ema_update_f32(float* ema, const float* p, long n, const float* ema_state, hupr_stream_t stream);
+/* a[0 .. n) <-> b[0 .. n), every bit pattern kept.  Alignment handled as in hupr_ema_update_f32; overlapping ranges are refused. */
+int hupr_swap_f32(float* a, float* b, long n, hupr_stream_t stream);
+
 /* ---- bf16-activation variants ("bf16act") -------------------------------------------------------------
  * Same operators with the ACTIVATION tensors (x, y, dy, dx, residual) stored as bf16 in HBM; parameters,
  * statistics, weight gradients and all arithmetic stay fp32 (fp32 accumulate on the matrix pipe).  The
