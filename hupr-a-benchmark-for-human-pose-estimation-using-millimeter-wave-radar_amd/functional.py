@@ -1680,6 +1680,25 @@ def gaussian_targets(joints, hsize=64, isize=256, sigma=2):
     return t
 
 
+def gaussian_targets_subpixel(joints, hsize=64, isize=256, sigma=2):
+    """joints (B,K,2) GPU tensor of any real dtype, image pixels with their fractions -> (B,K,H,W) fp32 targets whose Gaussian is
+    centred on the joint's real position inside the window ``gaussian_targets`` pastes (csrc/targets.hip; the rule is stated beside
+    hupr_gaussian_targets_subpixel_f32 in include/hupr.h).  One launch, no host table; a joint that is not finite gives a zero plane."""
+    if not isinstance(joints, torch.Tensor) or joints.dim() != 3 or joints.shape[-1] != 2:
+        raise ValueError("gaussian_targets_subpixel needs (B, K, 2) joints, got %s" %
+                         (tuple(joints.shape) if isinstance(joints, torch.Tensor) else type(joints).__name__,))
+    if joints.dtype == torch.bool or joints.is_complex():
+        raise ValueError("gaussian_targets_subpixel needs joints of a real dtype, got %s" % joints.dtype)
+    if not joints.is_cuda:
+        raise rt.HuprError("tensor is on %s; the HIP path needs a GPU tensor (no CPU fallback)" % joints.device)
+    joints = _c(joints.to(torch.float32))
+    B, K, _ = joints.shape
+    t = torch.empty((B, K, hsize, hsize), dtype=torch.float32, device=joints.device)
+    rt.check(rt.lib().hupr_gaussian_targets_subpixel_f32(rt.ptr(joints), rt.ptr(t), B * K, hsize, float(sigma), int(3 * sigma),
+                                                        float(isize) / float(hsize), rt.stream()))
+    return t
+
+
 def argmax_rows(p):
     """p (rows, n) GPU -> (idx int32 (rows,), maxval (rows,)) with first-max tie-break."""
     p = _c(p)

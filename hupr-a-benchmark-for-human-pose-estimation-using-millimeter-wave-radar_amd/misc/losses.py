@@ -7,6 +7,18 @@ from .metrics import decode_setting, get_final_preds, get_max_preds
 
 PAIR_BCE = True      # test aid: False = one BCE node per head, combined by torch
 
+TARGETS = ("integer", "subpixel")
+
+
+def targets_setting(cfg):
+    """``TRAINING.targets`` (not a key of the reference's YAML): absent or ``integer`` = the reference's targets, a fixed patch
+    centred on the whole heat-map pixel nearest the integer joint; ``subpixel`` = the Gaussian centred on the float joint's real
+    position inside that window (``functional.gaussian_targets_subpixel``).  Anything else raises here, where the config is read."""
+    name = getattr(getattr(cfg, "TRAINING", None), "targets", "integer")
+    if not isinstance(name, str) or name not in TARGETS:
+        raise ValueError("TRAINING.targets must be 'integer' or 'subpixel', got %r" % (name,))
+    return name
+
 
 class LossComputer():
     def __init__(self, cfg, device):
@@ -19,15 +31,19 @@ class LossComputer():
         self.imgSize = self.imgWidth = self.imgHeight = cfg.DATASET.imgSize
         self.lossDecay = cfg.TRAINING.lossDecay
         self.decode = decode_setting(cfg)       # TEST.decode: how the host-decode branch below turns preds2 into pred2d
+        self.targets_mode = targets_setting(cfg)    # TRAINING.targets: which joints computeLoss takes and how targets() encodes them
         self.alpha = 0.0
         self.beta = 1.0
 
     def targets(self, gt):
         sigma = {64: 2, 128: 3}[self.heatmapSize]
+        if self.targets_mode == "subpixel":
+            return F_.gaussian_targets_subpixel(gt.to(self.device), self.heatmapSize, self.imgSize, sigma)
         return F_.gaussian_targets(gt.to(self.device), self.heatmapSize, self.imgSize, sigma)
 
     def computeLoss(self, preds, gt, decode=True):
-        """preds = (heatmap (B,K,1,H,W), gcn_heatmap (B,1,K,H,W)); gt (B,K,2) integer joints.
+        """preds = (heatmap (B,K,1,H,W), gcn_heatmap (B,1,K,H,W)); gt (B,K,2) integer joints — with
+        ``TRAINING.targets: subpixel`` the float joints (an integer tensor is accepted there and means whole pixels).
         -> (loss, loss2, pred2d ndarray, gt2d ndarray) — same tuple as the reference."""
         heatmaps = self.targets(gt)
         preds1, preds2 = preds

@@ -172,3 +172,27 @@ def evaluate_keypoints(gts, dts, idx_keypoint=-1):
         return float(np.mean(s)) if s.size else -1.0
 
     return [_ap(0), _ap(0, .5), _ap(0, .75), _ap(1), _ap(2), _ar(0), _ar(0, .5), _ar(0, .75), _ar(1), _ar(2)]
+
+
+def mean_position_error(gts, dts):
+    """Mean per-joint position error in image pixels: the Euclidean distance between each detection's joints and its ground truth's.
+    gts, dts: the record forms of ``evaluate_keypoints``, matched by ``image_id`` (one person per image, as in HuPR: the first record
+    of an image on either side); a detection without ground truth, and ground truth without a detection, are not counted.
+    -> (mean over all matched joints, per-joint means ndarray (K,), number of matched images); (nan, nan's, 0) without a match."""
+    g_by = {}
+    for g in gts:
+        kp = np.asarray(g["keypoints"], dtype=np.float64)
+        xy = kp.reshape(-1, 3)[:, :2] if "area" in g else kp.reshape(-1, 2)
+        g_by.setdefault(int(g["image_id"]), xy)
+    dist, seen = [], set()
+    for d in dts:
+        iid = int(d["image_id"])
+        if iid not in g_by or iid in seen:
+            continue
+        seen.add(iid)
+        xy = np.asarray(d["keypoints"], dtype=np.float64).reshape(-1, 3)[:, :2]
+        dist.append(np.sqrt(((xy - g_by[iid]) ** 2).sum(axis=1)))
+    if not dist:
+        return float("nan"), np.full(len(SIGMAS), np.nan), 0
+    dist = np.stack(dist)
+    return float(dist.mean()), dist.mean(axis=0), len(dist)

@@ -159,6 +159,8 @@ SIGNATURES = {
     "hupr_bce_pair_bwd_f32": (c_int, [c_void_p] * 5 + [c_float, c_float, c_void_p, c_void_p, c_long, c_void_p]),
     "hupr_gaussian_targets_f32": (c_int, [c_void_p] * 3 + [c_int, c_int, c_int, c_float, c_void_p]),
     "hupr_argmax_rows_f32": (c_int, [c_void_p, c_long, c_int, c_void_p, c_void_p, c_void_p]),
+    # sub-pixel Gaussian targets (csrc/targets.hip)
+    "hupr_gaussian_targets_subpixel_f32": (c_int, [c_void_p, c_void_p, c_long, c_int, c_float, c_int, c_float, c_void_p]),
     "hupr_adam_step_f32": (c_int, [c_void_p] * 4 + [c_long] + [c_float] * 5 + [c_int, c_float, c_void_p]),
     "hupr_adam_step_dev_f32": (c_int, [c_void_p] * 4 + [c_long, c_void_p] + [c_float] * 5 + [c_void_p]),
     "hupr_sgd_step_f32": (c_int, [c_void_p] * 3 + [c_long] + [c_float] * 3 + [c_int, c_float, c_void_p]),

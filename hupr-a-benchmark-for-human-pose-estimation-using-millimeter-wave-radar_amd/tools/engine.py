@@ -77,7 +77,9 @@ class TrainEngine:
     def train_step(self, hori, vert, joints, decode=False, _last=True, _micro=1):
         """One forward + loss + backward (+ exchange + Adam when ``_last``).  ``decode="device"`` also runs the two
         arg-max decodes of the reference's per-iteration ``computeLoss`` (misc/losses.py:43-44) as kernels on the
-        step's stream; their results stay on the device (``self.last_decode``)."""
+        step's stream; their results stay on the device (``self.last_decode``).  ``joints`` (B,K,2) are what ``TRAINING.targets``
+        asks for: the integer joints by default, the float joints for ``subpixel`` (``tools.run.loss_labels``); they are handed to
+        ``LossComputer.computeLoss`` as they come."""
         from .. import functional as F_
         self._refuse_while_swapped("train_step")
         self.model.train()
@@ -113,7 +115,7 @@ class TrainEngine:
     def train_step_accumulated(self, micro_batches, from_adc=True, decode=False):
         """One optimiser step over several micro-batches (fixed GLOBAL batch, ``bench.py --strong``): gradients of the
         leading micro-batches are summed locally, the exchange happens once, overlapped with the last backward.
-        ``micro_batches``: list of (hori, vert, joints) — ADC cubes when ``from_adc`` — each a per-rank micro-batch whose
+        ``micro_batches``: list of (hori, vert, joints) — ADC cubes when ``from_adc``, joints as ``train_step`` takes them — each a per-rank micro-batch whose
         loss is its own mean, so the step's gradient is the mean over all ``world * len(micro_batches)`` of them.
         BatchNorm statistics are per micro-batch (as they are per rank in data parallel)."""
         m = len(micro_batches)
@@ -140,6 +142,8 @@ class TrainEngine:
         in lock step.  Requirements: fixed shapes (the static input buffers are refilled by copy), joints already on
         the device (a pageable host-to-device copy is illegal inside a capture), ``TRAINING.lossDecay == -1`` (the
         alpha/beta loss weights would be frozen at their capture-time values), ``sync_lr()`` after LR changes.
+        With ``TRAINING.targets: subpixel`` the joints must be a floating tensor: the static buffer keeps their dtype (an integer
+        buffer would truncate every later batch), and a conversion to fp32 is a device kernel inside the captured region.
         The gradient guard (``TRAINING.gradClip``) and the weight average (``TRAINING.emaDecay``) are device-side and replay with
         the step.
         The ``warmup`` eager steps are real optimisation steps."""
@@ -151,6 +155,9 @@ class TrainEngine:
             raise RuntimeError("graph capture would freeze the loss weights alpha/beta (TRAINING.lossDecay != -1)")
         if not (adc_hori.is_cuda and adc_vert.is_cuda and joints.is_cuda):
             raise RuntimeError("graph capture needs ADC cubes and joints resident on the GPU")
+        if self.lossComputer.targets_mode == "subpixel" and not joints.is_floating_point():
+            raise RuntimeError("graph capture with TRAINING.targets: subpixel needs floating joints (got %s): the static buffer "
+                               "keeps their dtype" % joints.dtype)
         self.optimizer.use_device_state()
         self._g_decode = decode
         self._g_in = (adc_hori.clone(), adc_vert.clone(), joints.clone())

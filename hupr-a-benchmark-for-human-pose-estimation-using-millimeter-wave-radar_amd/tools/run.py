@@ -15,7 +15,8 @@ import torch.utils.data as data
 
 from ..datasets import getDataset
 from ..datasets.dataset import HuPRRawADC, SequenceGroupedSampler
-from ..misc.oks_eval import evaluate_keypoints
+from ..misc.losses import TARGETS
+from ..misc.oks_eval import evaluate_keypoints, mean_position_error
 from ..misc.plot import plotHumanPose
 from .base import BaseRunner
 from .engine import TrainEngine
@@ -27,6 +28,20 @@ def _collate(batch):
         v = [b[k] for b in batch]
         out[k] = torch.stack(v) if isinstance(v[0], torch.Tensor) else torch.as_tensor(v)
     return out
+
+
+def loss_labels(batch, mode):
+    """The joints of ``batch`` that the loss takes under ``TRAINING.targets`` = ``mode``: the integer ``jointsGroup`` itself for
+    ``integer``, the float ``jointsFloat`` as fp32 (fractions kept) for ``subpixel``.  A batch without ``jointsFloat`` is an error
+    there, not a reason to train on the truncated joints."""
+    if mode not in TARGETS:
+        raise ValueError("TRAINING.targets must be 'integer' or 'subpixel', got %r" % (mode,))
+    if mode == "integer":
+        return batch["jointsGroup"]
+    if "jointsFloat" not in batch:
+        raise KeyError("TRAINING.targets: subpixel needs the float joints of the batch ('jointsFloat'); this dataset yields only %s"
+                       % sorted(batch))
+    return batch["jointsFloat"].float()
 
 
 class Runner(BaseRunner):
@@ -79,7 +94,10 @@ class Runner(BaseRunner):
     def eval(self, visualization=True, epoch=-1):
         """-> AP (reference tools/run.py:35-63).  Predictions are decoded from the GCN head, scaled to image pixels,
         written to ``<phase>_results.json`` by rank 0 and scored with the OKS evaluator against the ground truth the
-        reference uses: the float joints of ``<phase>_gt.json`` (not the integer-truncated ``jointsGroup`` the loss sees).
+        reference uses: the float joints of ``<phase>_gt.json`` (not the integer-truncated ``jointsGroup`` the loss sees by default;
+        with ``TRAINING.targets: subpixel`` the loss sees the float joints too, ``loss_labels``).  When ``TRAINING.targets`` or
+        ``TEST.decode`` is ``subpixel`` one more line is printed, the mean per-joint position error in image pixels
+        (``mean_position_error``): AP's OKS thresholds are too coarse to show a sub-pixel change.
         ``--keypoints`` prints the per-joint APs (``evaluateEach``) instead of the summary line."""
         self.logger.clear(len(self.testLoader.dataset))
         savePreds, gts = [], []
@@ -88,7 +106,7 @@ class Runner(BaseRunner):
             hori, vert = self._inputs(batch)
             preds = self.engine.infer(hori, vert)
             with torch.no_grad():
-                loss, loss2, pred2d, _ = self.lossComputer.computeLoss(preds, keypoints)
+                loss, loss2, pred2d, _ = self.lossComputer.computeLoss(preds, loss_labels(batch, self.lossComputer.targets_mode))
             self.logger.display(loss, loss2, keypoints.size(0), epoch)
             if visualization:                       # --visDir given: one skeleton overlay per sample (run.py:50-52)
                 plotHumanPose(pred2d * self.imgHeatmapRatio, self.cfg, self.visDir, batch["imageId"], None)
@@ -119,6 +137,8 @@ class Runner(BaseRunner):
             stats = evaluate_keypoints(gts, savePreds)
             print("  ".join("%s: %.3f" % (n, s) for n, s in zip(names, stats)))
             ap = float(stats[0])
+            if "subpixel" in (self.lossComputer.targets_mode, self.lossComputer.decode):
+                print("MPJPE: %.3f px (n = %d)" % mean_position_error(gts, savePreds)[::2])
         if self.world > 1:
             box = [ap]
             dist.broadcast_object_list(box, src=0)
@@ -138,7 +158,7 @@ class Runner(BaseRunner):
                 self.trainLoader.sampler.set_epoch(epoch)
             for idxBatch, batch in enumerate(self.trainLoader):
                 hori, vert = self._inputs(batch)
-                loss, loss2 = self.engine.train_step(hori, vert, batch["jointsGroup"])
+                loss, loss2 = self.engine.train_step(hori, vert, loss_labels(batch, self.lossComputer.targets_mode))
                 self.logger.display(loss, loss2, batch["jointsGroup"].size(0), epoch)
                 if idxBatch % self.cfg.TRAINING.lrDecayIter == 0:
                     self.adjustLR(epoch)

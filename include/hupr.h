@@ -493,6 +493,28 @@ int hupr_bce_pair_bwd_f32(const float* p1, const float* p2, const float* t, cons
 int hupr_gaussian_targets_f32(const long long* joints, const float* patch, float* t, int BK, int H, int rad,
                               float stride, hupr_stream_t stream);
 int hupr_argmax_rows_f32(const float* p, long rows, int n, int* idx, float* maxval, hupr_stream_t stream);
+/* Sub-pixel Gaussian targets in one launch (csrc/targets.hip): the unbiased encoding of Zhang et al., "Distribution-Aware Coordinate
+ * Representation for Human Pose Estimation" (CVPR 2020), inside the window and in-bounds rule of the reference's targets
+ * (misc/utils.py:6-66, hupr_gaussian_targets_f32 above).  hupr_pose_decode_f32 with refine != 0 inverts it.  No host table, no
+ * workspace, no LDS, no scratch; every element of t is written exactly once, zeros included, so t may be uninitialised.
+ * joints_xy : float [BK][2] = (x, y) in image pixels.  t : float [BK][H][H], t[r][y][x].  For row r and each axis, in fp32:
+ *   ac = joint / stride;  mu = (int)(ac + 0.5f) (the truncating cast of hupr_gaussian_targets_f32);  f = ac - (float)mu.
+ * The plane of row r is all zeros
+ *   when mu_x - rad >= H, mu_y - rad >= H, mu_x + rad + 1 < 0 or mu_y + rad + 1 < 0 (the window lies outside the map), or
+ *   when a coordinate is NaN or infinite, or ac + 0.5f is outside [-2^31, 2^31): decided in float arithmetic, the cast is not
+ *   executed then, and a NaN never reaches t.
+ * Otherwise cell (x, y), with dx = x - mu_x, dy = y - mu_y, |dx| <= rad, |dy| <= rad, 0 <= x, y < H, holds
+ *   expf(-((dx - f_x)^2 + (dy - f_y)^2) / (2 sigma^2))
+ * and every other cell holds exactly 0.0f.  A joint on a whole map pixel (f == 0) gives the support of hupr_gaussian_targets_f32
+ * exactly and its values up to the rounding of expf.  (The cast truncates towards zero, so for ac < -0.5 the window's middle is the
+ * pixel above the nearest one and f lies in (-1.5, -0.5]: the window is still that of hupr_gaussian_targets_f32, the Gaussian is on
+ * the joint.)
+ * Returns -1 (HUPR_ERR_ARG) before any launch for a null pointer, BK < 0 or BK * H * H beyond the 64-bit index arithmetic, H outside
+ * [1, 4096], rad < 1, sigma or stride not finite or not positive (or 2 sigma^2 not a positive finite float).  Any other H is accepted:
+ * 16-byte stores where H % 4 == 0 and t is 16-byte aligned, 4-byte stores otherwise; H may be smaller than the window.
+ * BK == 0 is a no-op. */
+int hupr_gaussian_targets_subpixel_f32(const float* joints_xy, float* t, long BK, int H, float sigma, int rad, float stride,
+                                       hupr_stream_t stream);
 
 /* (a10) Adam with coupled L2 weight decay (tools/base.py:47), one flat launch */
 int hupr_adam_step_f32(float* p, const float* g, float* exp_avg, float* exp_avg_sq, long n, float lr, float beta1,
