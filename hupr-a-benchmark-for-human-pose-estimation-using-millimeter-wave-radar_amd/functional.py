@@ -1661,6 +1661,65 @@ class PairBCEFn(torch.autograd.Function):
         return dp1, dp2, None, None, None
 
 
+@_math_scoped
+class MinedBCEFn(torch.autograd.Function):
+    """PairBCEFn with online hard keypoint mining and per-joint weights (csrc/bce_mined.hip; the rule is stated beside
+    hupr_bce_mined_fwd_f32 in include/hupr.h): per head and sample only the ``k`` joints with the largest weighted plane loss carry
+    loss and gradient.  ``MinedBCEFn.apply(p1, p2, t, k, joint_w, alpha, beta, counts)`` -> (loss, loss2) with the launches of
+    PairBCEFn, two forward and one backward.  p1, p2, t: fp32 GPU tensors of one shape (B, K, ...); ``joint_w``: None or K fp32
+    weights on the device; ``counts``: None or a (2, K) int64 device tensor that accumulates how often each joint was selected by
+    each head.  ``MinedBCEFn.last_plane_loss`` is the (2, B, K) unweighted plane losses of the latest forward, detached.  Anything
+    else raises: there is no fallback to the plain loss."""
+
+    last_plane_loss = None
+
+    @staticmethod
+    def forward(ctx, p1, p2, t, k, joint_w, alpha, beta, counts):
+        for name, x in (("p1", p1), ("p2", p2), ("t", t)):
+            if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float32:
+                raise ValueError("MinedBCEFn: %s must be an fp32 GPU tensor, got %s" % (
+                    name, "%s on %s" % (x.dtype, x.device) if isinstance(x, torch.Tensor) else type(x).__name__))
+        if not (p1.shape == p2.shape == t.shape) or p1.dim() < 2:
+            raise ValueError("MinedBCEFn: p1, p2 and t must share one shape (B, K, ...), got %s, %s, %s" % (
+                tuple(p1.shape), tuple(p2.shape), tuple(t.shape)))
+        B, K = p1.shape[0], p1.shape[1]
+        if B < 1 or K < 1 or p1.numel() == 0:
+            raise ValueError("MinedBCEFn: empty input %s" % (tuple(p1.shape),))
+        HW = p1.numel() // (B * K)
+        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= K <= 64:
+            raise ValueError("MinedBCEFn: k must be an int with 1 <= k <= K <= 64, got k = %r, K = %d" % (k, K))
+        if joint_w is not None and not (isinstance(joint_w, torch.Tensor) and joint_w.device == p1.device and joint_w.is_contiguous()
+                                        and joint_w.dtype == torch.float32 and tuple(joint_w.shape) == (K,)):
+            raise ValueError("MinedBCEFn: joint_w must be None or %d contiguous fp32 weights on %s" % (K, p1.device))
+        if counts is not None and not (isinstance(counts, torch.Tensor) and counts.device == p1.device and counts.is_contiguous()
+                                       and counts.dtype == torch.int64 and tuple(counts.shape) == (2, K)):
+            raise ValueError("MinedBCEFn: counts must be None or a contiguous (2, %d) int64 tensor on %s" % (K, p1.device))
+        p1, p2, t = _c(p1), _c(p2), _c(t)
+        out = torch.empty(3, dtype=torch.float32, device=p1.device)
+        plane_loss = torch.empty((2, B, K), dtype=torch.float32, device=p1.device)
+        coef = torch.empty((2, B, K), dtype=torch.float32, device=p1.device)
+        rt.check(rt.lib().hupr_bce_mined_fwd_f32(rt.ptr(p1), rt.ptr(p2), rt.ptr(t), B, K, HW, k, rt.ptr(joint_w), float(alpha), float(beta),
+                                                 rt.ptr(out), rt.ptr(plane_loss), rt.ptr(coef), rt.ptr(counts), rt.stream()))
+        ctx.save_for_backward(p1, p2, t, coef)
+        ctx.ab = (float(alpha), float(beta))
+        ctx.set_materialize_grads(False)
+        MinedBCEFn.last_plane_loss = plane_loss
+        return out[0], out[2]
+
+    @staticmethod
+    def backward(ctx, g, g2):
+        p1, p2, t, coef = ctx.saved_tensors
+        if g is None:
+            g = torch.zeros(1, dtype=torch.float32, device=p1.device)
+        dp1, dp2 = torch.empty_like(p1), torch.empty_like(p2)
+        g = _c(g.reshape(1).to(torch.float32))
+        g2 = _c(g2.reshape(1).to(torch.float32)) if g2 is not None else None
+        B, K = p1.shape[0], p1.shape[1]
+        rt.check(rt.lib().hupr_bce_mined_bwd_f32(rt.ptr(p1), rt.ptr(p2), rt.ptr(t), rt.ptr(coef), rt.ptr(g), rt.ptr(g2), ctx.ab[0], ctx.ab[1],
+                                                 rt.ptr(dp1), rt.ptr(dp2), B, K, p1.numel() // (B * K), rt.stream()))
+        return dp1, dp2, None, None, None, None, None, None
+
+
 _PATCH_CACHE = {}
 
 

@@ -1,5 +1,7 @@
 """LossComputer (reference misc/losses.py:8-48) with device-side targets, BCE and decode."""
 
+import math
+
 import torch
 
 from .. import functional as F_
@@ -20,6 +22,36 @@ def targets_setting(cfg):
     return name
 
 
+def ohkm_setting(cfg):
+    """``TRAINING.ohkm`` (not a key of the reference's YAML) -> None (absent or -1: off, the YAML's own "-1 = off" idiom) or ``k``, an
+    int in [1, DATASET.numKeypoints]: online hard keypoint mining, per head and sample only the ``k`` joints with the largest loss
+    carry loss and gradient (``functional.MinedBCEFn``).  Anything else (0, a bool, a float, a string, out of range) raises here,
+    where the config is read."""
+    v = getattr(getattr(cfg, "TRAINING", None), "ohkm", -1)
+    K = cfg.DATASET.numKeypoints
+    if isinstance(v, int) and not isinstance(v, bool):
+        if v == -1:
+            return None
+        if 1 <= v <= K:
+            return v
+    raise ValueError("TRAINING.ohkm must be -1 (off) or an int in [1, numKeypoints = %d], got %r" % (K, v))
+
+
+def joint_weights_setting(cfg):
+    """``TRAINING.jointWeights`` (not a key of the reference's YAML) -> None (absent or -1: off) or the per-joint loss weights as a
+    list of DATASET.numKeypoints floats in ``DATASET.idxToJoints`` order: finite, >= 0, not all zero.  Anything else raises here,
+    where the config is read."""
+    v = getattr(getattr(cfg, "TRAINING", None), "jointWeights", -1)
+    K = cfg.DATASET.numKeypoints
+    if isinstance(v, (int, float)) and not isinstance(v, bool) and v == -1:
+        return None
+    if isinstance(v, (list, tuple)) and len(v) == K and \
+            all(isinstance(x, (int, float)) and not isinstance(x, bool) and math.isfinite(x) and x >= 0 for x in v) and any(x > 0 for x in v):
+        return [float(x) for x in v]
+    raise ValueError("TRAINING.jointWeights must be -1 (off) or a list of numKeypoints = %d finite weights >= 0, not all zero, "
+                     "got %r" % (K, v))
+
+
 class LossComputer():
     def __init__(self, cfg, device):
         self.device = device
@@ -32,6 +64,15 @@ class LossComputer():
         self.lossDecay = cfg.TRAINING.lossDecay
         self.decode = decode_setting(cfg)       # TEST.decode: how the host-decode branch below turns preds2 into pred2d
         self.targets_mode = targets_setting(cfg)    # TRAINING.targets: which joints computeLoss takes and how targets() encodes them
+        # TRAINING.ohkm / TRAINING.jointWeights: with either set computeLoss takes the mined loss (k = numKeypoints for weights alone)
+        self.ohkm = ohkm_setting(cfg)
+        self.jointWeights = joint_weights_setting(cfg)
+        self.mined = self.ohkm is not None or self.jointWeights is not None
+        self.mined_k = (self.ohkm if self.ohkm is not None else self.numKeypoints) if self.mined else None
+        # the weights and the (2, K) selection counters live on the device from the start: a captured step replays their updates
+        self._joint_w = torch.tensor(self.jointWeights, dtype=torch.float32, device=device) if self.jointWeights is not None else None
+        self.mining_counts = torch.zeros((2, self.numKeypoints), dtype=torch.int64, device=device) if self.mined else None
+        self.plane_loss = None          # the last mined loss's (2, B, K) unweighted plane losses, on the device
         self.alpha = 0.0
         self.beta = 1.0
 
@@ -52,7 +93,14 @@ class LossComputer():
         if self.alpha < 1.0:
             self.alpha += self.lossDecay
             self.beta -= self.lossDecay
-        if PAIR_BCE and a1.is_cuda and a1.dtype == a2.dtype == heatmaps.dtype == torch.float32 and a1.shape == a2.shape == heatmaps.shape:
+        if self.mined:
+            # online hard keypoint mining / per-joint weights (csrc/bce_mined.hip): the launches of the pair loss below.  The
+            # selection counters move only where gradients are recorded: evaluation shows the trained loss and does not count
+            w = (self.alpha, self.beta) if self.lossDecay != -1 else (1.0, 1.0)
+            loss, loss2 = F_.MinedBCEFn.apply(a1, a2, heatmaps, self.mined_k, self._joint_w, w[0], w[1],
+                                              self.mining_counts if torch.is_grad_enabled() else None)
+            self.plane_loss = F_.MinedBCEFn.last_plane_loss
+        elif PAIR_BCE and a1.is_cuda and a1.dtype == a2.dtype == heatmaps.dtype == torch.float32 and a1.shape == a2.shape == heatmaps.shape:
             # both losses and their weighted sum as one node (two launches forward, one backward; the same floats)
             w = (self.alpha, self.beta) if self.lossDecay != -1 else (1.0, 1.0)
             loss, loss2 = F_.PairBCEFn.apply(a1, a2, heatmaps, w[0], w[1])

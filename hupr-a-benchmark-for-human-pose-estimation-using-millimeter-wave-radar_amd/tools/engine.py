@@ -144,8 +144,8 @@ class TrainEngine:
         alpha/beta loss weights would be frozen at their capture-time values), ``sync_lr()`` after LR changes.
         With ``TRAINING.targets: subpixel`` the joints must be a floating tensor: the static buffer keeps their dtype (an integer
         buffer would truncate every later batch), and a conversion to fp32 is a device kernel inside the captured region.
-        The gradient guard (``TRAINING.gradClip``) and the weight average (``TRAINING.emaDecay``) are device-side and replay with
-        the step.
+        The gradient guard (``TRAINING.gradClip``), the weight average (``TRAINING.emaDecay``) and the mined loss with its counters
+        (``TRAINING.ohkm``, ``TRAINING.jointWeights``) are device-side and replay with the step.
         The ``warmup`` eager steps are real optimisation steps."""
         self._refuse_while_swapped("capture")
         tr = self.buckets.transport
@@ -184,6 +184,20 @@ class TrainEngine:
         device: per epoch, not per step.  A skipped step leaves parameters, optimiser state and step count as they were; the
         BatchNorm running statistics of its forward pass have moved all the same (as under torch's GradScaler)."""
         return self.optimizer.guard_stats()
+
+    def mining_stats(self):
+        """With ``TRAINING.ohkm`` or ``TRAINING.jointWeights`` set: {"k": joints kept per head and sample, "counts": (2, K) int64
+        ndarray, how often each joint was kept by the first head (row 0) and the PRGCN head (row 1) in the training losses so far,
+        "samples": the samples those losses saw, "plane_loss": the last loss's (2, B, K) unweighted plane losses (None before the
+        first; between ``capture()`` and the first replay it is the captured step's buffer, which no step has filled yet)}; None
+        otherwise.  The counters live on the device and replay with a captured step; they are diagnostics, not part
+        of a checkpoint.  Synchronises the device: per epoch, not per step."""
+        lc = self.lossComputer
+        if not lc.mined:
+            return None
+        counts = lc.mining_counts.cpu().numpy()
+        return {"k": lc.mined_k, "counts": counts, "samples": int(counts[1].sum()) // lc.mined_k,
+                "plane_loss": lc.plane_loss.cpu().numpy() if lc.plane_loss is not None else None}
 
     # -- averaged weights (TRAINING.emaDecay) -----------------------------------------------------------------------------------
     def ema_stats(self):

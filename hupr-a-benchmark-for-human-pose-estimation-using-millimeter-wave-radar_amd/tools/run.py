@@ -153,6 +153,7 @@ class Runner(BaseRunner):
         for epoch in range(self.start_epoch, self.cfg.TRAINING.epochs):
             loss_list = []
             guard0 = self.engine.guard_stats()
+            mined0 = self.engine.mining_stats()
             self.logger.clear(len(self.trainLoader.dataset))
             if hasattr(self.trainLoader.sampler, "set_epoch"):
                 self.trainLoader.sampler.set_epoch(epoch)
@@ -169,6 +170,13 @@ class Runner(BaseRunner):
                 skipped = self.engine.guard_stats()["skipped"] - guard0["skipped"]
                 if skipped and self.rank == 0:
                     print("==========>Skipped %d optimizer step(s) with non-finite gradients in epoch %d" % (skipped, epoch))
+            if mined0 is not None and self.rank == 0:
+                # TRAINING.ohkm / TRAINING.jointWeights: in which share of this epoch's samples the PRGCN head kept each joint
+                mined = self.engine.mining_stats()
+                kept, n = mined["counts"][1] - mined0["counts"][1], mined["samples"] - mined0["samples"]
+                print("==========>Mined joints in epoch %d (PRGCN head, %d of %d kept, %d samples): %s" % (
+                    epoch, mined["k"], self.numKeypoints, n,
+                    "  ".join("%s: %.3f" % (name, c / max(n, 1)) for name, c in zip(self.cfg.DATASET.idxToJoints, kept))))
             with self.engine.averaged_weights() if averaged else contextlib.nullcontext():
                 accAP = self.eval(visualization=False, epoch=epoch)
             if self.rank == 0:

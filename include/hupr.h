@@ -490,6 +490,35 @@ int hupr_bce_pair_fwd_f32(const float* p1, const float* p2, const float* t, long
                           size_t ws_bytes, hupr_stream_t stream);
 int hupr_bce_pair_bwd_f32(const float* p1, const float* p2, const float* t, const float* grad_loss, const float* grad_loss2_or_null,
                           float alpha, float beta, float* dp1, float* dp2, long n, hupr_stream_t stream);
+/* The pair loss with online hard keypoint mining (the top-k joint selection of CPN's RefineNet and HRNet's JointsOHKMMSELoss) and
+ * per-joint weights (HRNet's target_weight), csrc/bce_mined.hip.  New, no reference counterpart; with k = K and no weights it is
+ * hupr_bce_pair_fwd_f32 up to the order of summation.  Two launches forward, one backward, no workspace, no atomics: every output
+ * is bit-identical from run to run.  p1, p2, t: float [B][K][HW]; head h = 0 is p1, h = 1 is p2.
+ *   Plane loss   l[h,b,j] = the mean over the plane's HW cells of -(t log p + (1 - t) log(1 - p)), both logs clamped at -100 (the
+ *                term of hupr_bce_fwd_f32 for every number; a NaN cell, or p outside [0, 1], gives a NaN plane loss), summed by one workgroup in an order fixed by HW alone: planes with equal contents give
+ *                equal bits.  v[h,b,j] = w[j] * l[h,b,j], with w = joint_w_or_null (K floats) or all ones when it is null.
+ *                plane_loss (2, B, K) receives l, not v.
+ *   Selection    the K planes of one (head, sample) are ordered by v descending; a NaN ranks above every number (a non-finite
+ *                forward reaches the loss, it is not mined away); equal values, and two NaNs, order by lower joint index first.
+ *                sel[h,b,j] = 1 for the first k planes in that order and 0 for the rest.  Each head mines on its own.
+ *   Losses       L_h = (1 / (B k)) sum_b sum_j sel * v, summed in fp64 in an order fixed by (B, K).
+ *                loss3 = {alpha L_0 + beta L_1, L_0, L_1}; the two products and the sum are rounded separately, as in
+ *                hupr_bce_pair_fwd_f32.
+ *   Coefficients coef[h,b,j] (2, B, K) = sel ? w[j] / (B k HW) : 0  — what the backward scales a plane by.
+ *   Counters     with counts_or_null non-null (2, K) int64: counts[h,j] += sum_b sel[h,b,j].  Plain adds by one workgroup; the
+ *                caller zeroes the array once.
+ *   Backward     dp_h[b,j,x] = G_h * coef[h,b,j] * (p - t) / max(p (1 - p), 1e-12), G_0 = g * alpha, G_1 = g * beta (+ g2): the
+ *                arithmetic of hupr_bce_pair_bwd_f32 with a per-plane scale.  No gradient flows through the selection.  A plane
+ *                whose scale G_h * coef is zero is written as zeros without being read; every cell of dp1 and dp2 is written.
+ * Both return -1 (HUPR_ERR_ARG) before any launch for a null pointer (the two _or_null ones excepted), K outside [1, 64], B < 1,
+ * HW < 1, B * K * HW beyond the 64-bit index arithmetic, and the forward for k outside [1, K].  16-byte loads and stores where
+ * HW % 4 == 0 and the maps are 16-byte aligned, 4-byte ones otherwise. */
+int hupr_bce_mined_fwd_f32(const float* p1, const float* p2, const float* t, long B, int K, long HW, int k,
+                           const float* joint_w_or_null, float alpha, float beta, float* loss3, float* plane_loss, float* coef,
+                           long long* counts_or_null, hupr_stream_t stream);
+int hupr_bce_mined_bwd_f32(const float* p1, const float* p2, const float* t, const float* coef, const float* grad_loss,
+                           const float* grad_loss2_or_null, float alpha, float beta, float* dp1, float* dp2, long B, int K, long HW,
+                           hupr_stream_t stream);
 int hupr_gaussian_targets_f32(const long long* joints, const float* patch, float* t, int BK, int H, int rad,
                               float stride, hupr_stream_t stream);
 int hupr_argmax_rows_f32(const float* p, long rows, int n, int* idx, float* maxval, hupr_stream_t stream);
