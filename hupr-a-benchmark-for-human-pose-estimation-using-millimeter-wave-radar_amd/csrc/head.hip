@@ -1,9 +1,9 @@
 // Row softmax (attention), PRGCN adjacency/bias epilogue, sigmoid heads, BCE loss, Gaussian
-// targets, arg-max decode and the fused Adam and SGD-momentum steps.  All HBM-bound or tiny.
+// targets and arg-max decode.  All HBM-bound or tiny.
 //
 // Reference semantics: models/layers.py:126-133 (softmax over keys), models/gcn_networks.py:23-29,
 // 53-64 (X.A, W.(XA)+b, ReLU, sigmoid), models/networks.py:40, misc/losses.py:23-45,
-// misc/utils.py:6-66, misc/metrics.py:10-38, tools/base.py:44-47 (SGD momentum 0.9 / Adam, coupled L2 decay).
+// misc/utils.py:6-66, misc/metrics.py:10-38.
 #include "hupr_common.h"
 
 namespace hupr {
@@ -185,8 +185,7 @@ __global__ __launch_bounds__(256) void hupr_k_bce_fwd(const float* __restrict__ 
 __global__ void hupr_k_bce_final(const double* __restrict__ partial, int nblk, double inv_n, float* __restrict__ out) {
     double s = 0.0;
     for (int i = threadIdx.x; i < nblk; i += 64) s += partial[i];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    s = wave_sum_f64(s);
     if (threadIdx.x == 0) out[0] = (float)(s * inv_n);
 }
 // The two BCE losses of a step (first head and PRGCN head against the same targets, reference misc/losses.py:24-33) and their
@@ -214,8 +213,7 @@ __global__ void hupr_k_bce_pair_final(const double* __restrict__ partial, int nb
     const int head = threadIdx.x >> 6, lane = threadIdx.x & 63;
     double s = 0.0;
     for (int i = lane; i < nblk; i += 64) s += partial[(long)head * nblk + i];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    s = wave_sum_f64(s);
     if (lane == 0) l[head] = (float)(s * inv_n);
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -274,118 +272,6 @@ __global__ __launch_bounds__(64) void hupr_k_argmax_rows(const float* __restrict
     int bi;
     wave_argmax_row(p + (long)blockIdx.x * n, n, threadIdx.x, best, bi);
     if (threadIdx.x == 0) { idx[blockIdx.x] = bi; maxval[blockIdx.x] = best; }
-}
-
-// ---- Adam with coupled L2 weight decay (torch.optim.Adam semantics), one flat launch --------------
-__device__ __forceinline__ void adam_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                          float* __restrict__ v, long n, float lr, float b1, float b2, float eps, float wd,
-                                          float bc1, float bc2_sqrt, float gscale) {
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-        const float pv = p[i];
-        const float gr = fmaf(wd, pv, g[i] * gscale);
-        const float mv = fmaf(b1, m[i], (1.f - b1) * gr);
-        const float vv = fmaf(b2, v[i], (1.f - b2) * gr * gr);
-        m[i] = mv;
-        v[i] = vv;
-        const float denom = sqrtf(vv) / bc2_sqrt + eps;
-        p[i] = pv - (lr / bc1) * (mv / denom);
-    }
-}
-
-__global__ __launch_bounds__(256) void hupr_k_adam(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                   float* __restrict__ v, long n, float lr, float b1, float b2, float eps,
-                                                   float wd, float bc1, float bc2_sqrt, float gscale) {
-    adam_body(p, g, m, v, n, lr, b1, b2, eps, wd, bc1, bc2_sqrt, gscale);
-}
-
-// the bias corrections of step `step` as hupr_adam_step_f32 forms them on the host
-__device__ __forceinline__ void adam_bias_corrections(float b1, float b2, float step_f, float& bc1, float& bc2_sqrt) {
-    const double step = (double)step_f;
-    bc1 = (float)(1.0 - pow((double)b1, step));
-    bc2_sqrt = (float)sqrt(1.0 - pow((double)b2, step));
-}
-
-// same update with the learning rate and the step count read from device memory (state = {lr, step}): the launch
-// arguments of a captured hipGraph are frozen, the bias corrections must not be
-__global__ __launch_bounds__(256) void hupr_k_adam_dev(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                       float* __restrict__ v, long n, const float* __restrict__ state, float b1,
-                                                       float b2, float eps, float wd, float gscale) {
-    float bc1, bc2_sqrt;
-    adam_bias_corrections(b1, b2, state[1], bc1, bc2_sqrt);
-    adam_body(p, g, m, v, n, state[0], b1, b2, eps, wd, bc1, bc2_sqrt, gscale);
-}
-
-// hupr_k_adam_dev behind the gradient guard (grad_guard.hip; guard = {coef, norm, skipped, finite}): nothing is written when the
-// step's gradients were not finite, otherwise the gradient scale carries the clipping coefficient (one fp32 product; coef = 1
-// leaves gscale's bits, so the unclipped step is hupr_k_adam_dev's)
-__global__ __launch_bounds__(256) void hupr_k_adam_guard(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                         float* __restrict__ v, long n, const float* __restrict__ state,
-                                                         const float* __restrict__ guard, float b1, float b2, float eps, float wd,
-                                                         float gscale) {
-    if (guard[3] == 0.f) return;
-    float bc1, bc2_sqrt;
-    adam_bias_corrections(b1, b2, state[1], bc1, bc2_sqrt);
-    adam_body(p, g, m, v, n, state[0], b1, b2, eps, wd, bc1, bc2_sqrt, gscale * guard[0]);
-}
-
-// ---- SGD with momentum and coupled L2 weight decay (torch.optim.SGD, dampening 0, no Nesterov), one flat launch -------------
-// torch's single-tensor order of roundings: d = g + wd * p (one fma), buf = (buf * m) + d (two roundings: mul_ then add_, not
-// fused), p = p - lr * buf (one fma).  The first step copies d into the buffer as torch's clone(d_p) does: buf * m + d over a
-// zero buffer would turn a -0 of d into +0.  Measured bit-identical to torch.optim.SGD's foreach and single-tensor paths on
-// the MI355X.  20 B per element, HBM-bound: float4 when p, g and buf are all 16-byte aligned.
-__device__ __forceinline__ float sgd_elem(float& p, float g, float buf, float lr, float m, float wd, float gscale, bool first) {
-#pragma clang fp contract(off)
-    const float d = fmaf(wd, p, g * gscale);
-    const float b = first ? d : buf * m + d;
-    p = fmaf(-lr, b, p);
-    return b;
-}
-
-__device__ __forceinline__ void sgd_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf, long n,
-                                         float lr, float m, float wd, float gscale, bool first, bool vec) {
-    const long tid = (long)blockIdx.x * 256 + threadIdx.x, stride = (long)gridDim.x * 256;
-    long head = 0;
-    if (vec) {
-        const long n4 = n >> 2;
-        for (long i = tid; i < n4; i += stride) {
-            float4 pv = reinterpret_cast<const float4*>(p)[i];
-            const float4 gv = reinterpret_cast<const float4*>(g)[i];
-            float4 bv = reinterpret_cast<const float4*>(buf)[i];
-            bv.x = sgd_elem(pv.x, gv.x, bv.x, lr, m, wd, gscale, first);
-            bv.y = sgd_elem(pv.y, gv.y, bv.y, lr, m, wd, gscale, first);
-            bv.z = sgd_elem(pv.z, gv.z, bv.z, lr, m, wd, gscale, first);
-            bv.w = sgd_elem(pv.w, gv.w, bv.w, lr, m, wd, gscale, first);
-            reinterpret_cast<float4*>(p)[i] = pv;
-            reinterpret_cast<float4*>(buf)[i] = bv;
-        }
-        head = n4 << 2;
-    }
-    for (long i = head + tid; i < n; i += stride) {        // unaligned launches, and the (< 4-element) tail of aligned ones
-        float pv = p[i];
-        buf[i] = sgd_elem(pv, g[i], buf[i], lr, m, wd, gscale, first);
-        p[i] = pv;
-    }
-}
-
-__global__ __launch_bounds__(256) void hupr_k_sgd(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
-                                                  long n, float lr, float m, float wd, float gscale, int first, int vec) {
-    sgd_body(p, g, buf, n, lr, m, wd, gscale, first != 0, vec != 0);
-}
-
-// same update with the learning rate and the step count read from device memory (state = {lr, step}, the layout of
-// hupr_k_adam_dev): "first" is step == 1, so a captured hipGraph replays the right branch
-__global__ __launch_bounds__(256) void hupr_k_sgd_dev(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
-                                                      long n, const float* __restrict__ state, float m, float wd, float gscale,
-                                                      int vec) {
-    sgd_body(p, g, buf, n, state[0], m, wd, gscale, state[1] == 1.f, vec != 0);
-}
-
-// hupr_k_sgd_dev behind the gradient guard, as hupr_k_adam_guard
-__global__ __launch_bounds__(256) void hupr_k_sgd_guard(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
-                                                        long n, const float* __restrict__ state, const float* __restrict__ guard,
-                                                        float m, float wd, float gscale, int vec) {
-    if (guard[3] == 0.f) return;
-    sgd_body(p, g, buf, n, state[0], m, wd, gscale * guard[0], state[1] == 1.f, vec != 0);
 }
 
 static inline int grid1d(long n, int bs = 256, long cap = 4096) { return (int)min(cap, (n + bs - 1) / bs); }
@@ -638,78 +524,5 @@ extern "C" int hupr_argmax_rows_f32(const float* p, long rows, int n, int* idx, 
     HUPR_REQUIRE(p && idx && maxval && rows > 0 && n > 0 && rows < (1L << 31), "hupr_argmax_rows_f32: bad argument");
     HUPR_LAUNCH(hupr_k_argmax_rows, dim3((unsigned)rows), dim3(64), 0, as_stream(stream), p, n, idx, maxval);
     HUPR_LAUNCH_OK("hupr_k_argmax_rows");
-    return HUPR_OK;
-}
-
-// step = 1-based step count after increment; gscale multiplies the gradient (e.g. 1/world_size)
-extern "C" int hupr_adam_step_f32(float* p, const float* g, float* exp_avg, float* exp_avg_sq, long n, float lr, float beta1,
-                                  float beta2, float eps, float weight_decay, int step, float gscale, hupr_stream_t stream) {
-    HUPR_REQUIRE(p && g && exp_avg && exp_avg_sq && n > 0 && step >= 1, "hupr_adam_step_f32: bad argument");
-    const double bc1 = 1.0 - pow((double)beta1, (double)step);
-    const double bc2 = 1.0 - pow((double)beta2, (double)step);
-    HUPR_LAUNCH(hupr_k_adam, dim3(grid1d(n, 256, 8192)), dim3(256), 0, as_stream(stream), p, g, exp_avg, exp_avg_sq, n, lr,
-                       beta1, beta2, eps, weight_decay, (float)bc1, (float)sqrt(bc2), gscale);
-    HUPR_LAUNCH_OK("hupr_k_adam");
-    return HUPR_OK;
-}
-
-// Same as hupr_adam_step_f32 with {lr, step} in device memory (dev_state[0] = learning rate, dev_state[1] = step count,
-// both float): usable inside a captured hipGraph whose launch arguments are frozen.
-extern "C" int hupr_adam_step_dev_f32(float* p, const float* g, float* exp_avg, float* exp_avg_sq, long n,
-                                      const float* dev_state, float beta1, float beta2, float eps, float weight_decay,
-                                      float gscale, hupr_stream_t stream) {
-    HUPR_REQUIRE(p && g && exp_avg && exp_avg_sq && dev_state && n > 0, "hupr_adam_step_dev_f32: bad argument");
-    HUPR_LAUNCH(hupr_k_adam_dev, dim3(grid1d(n, 256, 8192)), dim3(256), 0, as_stream(stream), p, g, exp_avg, exp_avg_sq, n,
-                       dev_state, beta1, beta2, eps, weight_decay, gscale);
-    HUPR_LAUNCH_OK("hupr_k_adam_dev");
-    return HUPR_OK;
-}
-
-// hupr_adam_step_dev_f32 behind the gradient guard: guard = the 4 floats hupr_grad_guard_f32 wrote on this stream before
-extern "C" int hupr_adam_step_guard_f32(float* p, const float* g, float* exp_avg, float* exp_avg_sq, long n,
-                                        const float* dev_state, const float* guard, float beta1, float beta2, float eps,
-                                        float weight_decay, float gscale, hupr_stream_t stream) {
-    HUPR_REQUIRE(p && g && exp_avg && exp_avg_sq && dev_state && guard && n > 0,
-                 "hupr_adam_step_guard_f32: bad argument (null pointer or n <= 0)");
-    HUPR_LAUNCH(hupr_k_adam_guard, dim3(grid1d(n, 256, 8192)), dim3(256), 0, as_stream(stream), p, g, exp_avg, exp_avg_sq, n,
-                dev_state, guard, beta1, beta2, eps, weight_decay, gscale);
-    HUPR_LAUNCH_OK("hupr_k_adam_guard");
-    return HUPR_OK;
-}
-
-// float4 path only when all three streams are 16-byte aligned; grid = min(ceil(n / (256 * 4)), 2048) with a grid-stride loop
-static inline int sgd_vec(const float* p, const float* g, const float* buf) {
-    return ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(buf)) & 15) == 0;
-}
-
-// first != 0: the parameter's first step (the buffer's old contents are ignored); gscale multiplies the gradient (e.g. 1/world_size)
-extern "C" int hupr_sgd_step_f32(float* p, const float* g, float* momentum_buf, long n, float lr, float momentum,
-                                 float weight_decay, int first, float gscale, hupr_stream_t stream) {
-    HUPR_REQUIRE(p && g && momentum_buf && n > 0, "hupr_sgd_step_f32: bad argument (null pointer or n <= 0)");
-    HUPR_LAUNCH(hupr_k_sgd, dim3(grid1d(n, 256 * 4, 2048)), dim3(256), 0, as_stream(stream), p, g, momentum_buf, n, lr, momentum,
-                weight_decay, gscale, first != 0, sgd_vec(p, g, momentum_buf));
-    HUPR_LAUNCH_OK("hupr_k_sgd");
-    return HUPR_OK;
-}
-
-// Same as hupr_sgd_step_f32 with {lr, step} in device memory (dev_state[0] = learning rate, dev_state[1] = step count after
-// this step's increment, both float; step 1 is the first step): usable inside a captured hipGraph.
-extern "C" int hupr_sgd_step_dev_f32(float* p, const float* g, float* momentum_buf, long n, const float* dev_state,
-                                     float momentum, float weight_decay, float gscale, hupr_stream_t stream) {
-    HUPR_REQUIRE(p && g && momentum_buf && dev_state && n > 0, "hupr_sgd_step_dev_f32: bad argument (null pointer or n <= 0)");
-    HUPR_LAUNCH(hupr_k_sgd_dev, dim3(grid1d(n, 256 * 4, 2048)), dim3(256), 0, as_stream(stream), p, g, momentum_buf, n, dev_state,
-                momentum, weight_decay, gscale, sgd_vec(p, g, momentum_buf));
-    HUPR_LAUNCH_OK("hupr_k_sgd_dev");
-    return HUPR_OK;
-}
-
-// hupr_sgd_step_dev_f32 behind the gradient guard (hupr_grad_guard_f32 advanced dev_state[1] on this stream before)
-extern "C" int hupr_sgd_step_guard_f32(float* p, const float* g, float* momentum_buf, long n, const float* dev_state,
-                                       const float* guard, float momentum, float weight_decay, float gscale, hupr_stream_t stream) {
-    HUPR_REQUIRE(p && g && momentum_buf && dev_state && guard && n > 0,
-                 "hupr_sgd_step_guard_f32: bad argument (null pointer or n <= 0)");
-    HUPR_LAUNCH(hupr_k_sgd_guard, dim3(grid1d(n, 256 * 4, 2048)), dim3(256), 0, as_stream(stream), p, g, momentum_buf, n, dev_state,
-                guard, momentum, weight_decay, gscale, sgd_vec(p, g, momentum_buf));
-    HUPR_LAUNCH_OK("hupr_k_sgd_guard");
     return HUPR_OK;
 }

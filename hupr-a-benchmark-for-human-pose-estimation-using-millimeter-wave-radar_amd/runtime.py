@@ -168,13 +168,13 @@ SIGNATURES = {
     "hupr_adam_step_dev_f32": (c_int, [c_void_p] * 4 + [c_long, c_void_p] + [c_float] * 5 + [c_void_p]),
     "hupr_sgd_step_f32": (c_int, [c_void_p] * 3 + [c_long] + [c_float] * 3 + [c_int, c_float, c_void_p]),
     "hupr_sgd_step_dev_f32": (c_int, [c_void_p] * 3 + [c_long, c_void_p] + [c_float] * 3 + [c_void_p]),
-    # gradient guard (csrc/grad_guard.hip; the two guarded steps sit beside their _dev forms in head.hip)
+    # gradient guard (csrc/optim.hip, as the optimiser steps above and the averaged weights below)
     "hupr_grad_sumsq_partials": (c_int, []),
     "hupr_grad_sumsq_f32": (c_int, [c_void_p, c_long, c_void_p, c_void_p]),
     "hupr_grad_guard_f32": (c_int, [c_void_p, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p]),
     "hupr_adam_step_guard_f32": (c_int, [c_void_p] * 4 + [c_long, c_void_p, c_void_p] + [c_float] * 5 + [c_void_p]),
     "hupr_sgd_step_guard_f32": (c_int, [c_void_p] * 3 + [c_long, c_void_p, c_void_p] + [c_float] * 3 + [c_void_p]),
-    # averaged weights (csrc/weight_ema.hip)
+    # averaged weights
     "hupr_ema_tick_f32": (c_int, [c_void_p, c_float, c_void_p, c_void_p]),
     "hupr_ema_update_f32": (c_int, [c_void_p, c_void_p, c_long, c_void_p, c_void_p]),
     "hupr_swap_f32": (c_int, [c_void_p, c_void_p, c_long, c_void_p]),

@@ -5,8 +5,8 @@ optimiser step, ``w = 1 - min(decay, (1 + k) / (10 + k))`` after ``k`` earlier u
 are not dominated by the initial weights).  The reference has nothing of the kind: it evaluates, selects and deploys ``self.model``
 as trained (tools/run.py:35-63).
 
-Everything a step needs is a launch on the step's stream (``hupr_ema_tick_f32`` + one ``hupr_ema_update_f32`` per bucket, csrc/
-weight_ema.hip): the update count and this step's weight live in device memory and the tick reads the gradient guard's decision, so
+Everything a step needs is a launch on the step's stream (``hupr_ema_tick_f32`` + one ``hupr_ema_update_f32`` per bucket,
+csrc/optim.hip): the update count and this step's weight live in device memory and the tick reads the gradient guard's decision, so
 the average follows a step replayed from a hipGraph and stands still across a step the guard skipped.  ``swap()`` exchanges
 parameters and average in place (``hupr_swap_f32``), which is how the engine evaluates with the averaged weights without a second
 model.  Allocation, ``state_dict`` and ``load_state_dict`` are host-side bookkeeping on tensors of any device.

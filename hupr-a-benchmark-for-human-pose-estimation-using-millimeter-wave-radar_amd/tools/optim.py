@@ -157,6 +157,43 @@ class _FlatBucketOptimizer(torch.optim.Optimizer):
             self._dev_lr = self.param_groups[0]["lr"]
             self._dev_state[0] = self._dev_lr
 
+    # -- the step: one launch per flat bucket, or one per parameter tensor without buckets ------------------------------
+    def _launch_bucket(self, L, s, form, p, g, st, group):
+        """One bucket's update.  form: "host" (lr and ``st["step"]`` as launch arguments), "dev" ({lr, step} read from
+        ``_dev_state``) or "guard" ("dev" obeying ``_guard``)."""
+        raise NotImplementedError
+
+    def _launch_param(self, L, s, p, g, st, group):
+        """One parameter tensor's update with torch's per-parameter state ``st`` (created here on the first step)."""
+        raise NotImplementedError
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        L = rt.lib()
+        s = rt.stream()
+        from .. import functional as F_
+        F_.invalidate_packed()             # parameters change below without bumping torch's version counters
+        if self._flat is None:
+            for group in self.param_groups:
+                for p in group["params"]:
+                    if p.grad is not None:
+                        self._launch_param(L, s, p, p.grad if p.grad.is_contiguous() else p.grad.contiguous(), self.state[p], group)
+            return loss
+        form = "guard" if self._guard is not None else "dev" if self._dev_state is not None else "host"
+        if form == "guard":
+            self._guard_launches(L, s)       # advances the device-side step count unless the step is skipped
+        elif form == "dev":
+            self._dev_state[1] += 1          # device-side step count (captured as a graph node); SGD: step 1 is the first
+        for (p, g), st in zip(self._flat, self._flat_state):
+            if form != "guard":
+                st["step"] += 1              # host mirror (checkpoints); during replay only the device copy advances
+            self._launch_bucket(L, s, form, p, g, st, self.param_groups[0])
+        return loss
+
 
 class FusedAdam(_FlatBucketOptimizer):
     _state_keys = ("exp_avg", "exp_avg_sq")
@@ -172,56 +209,24 @@ class FusedAdam(_FlatBucketOptimizer):
     def _entry_step(self, entry):
         return int(round(float(entry["step"])))
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        L = rt.lib()
-        s = rt.stream()
-        from .. import functional as F_
-        F_.invalidate_packed()             # parameters change below without bumping torch's version counters
-        if self._flat is not None:
-            g0 = self.param_groups[0]
-            b1, b2 = g0["betas"]
-            if self._guard is not None:
-                self._guard_launches(L, s)       # advances the device-side step count unless the step is skipped
-                for (p, g), st in zip(self._flat, self._flat_state):
-                    rt.check(L.hupr_adam_step_guard_f32(rt.ptr(p), rt.ptr(g), rt.ptr(st["exp_avg"]), rt.ptr(st["exp_avg_sq"]),
-                                                        p.numel(), rt.ptr(self._dev_state), rt.ptr(self._guard), b1, b2,
-                                                        g0["eps"], g0["weight_decay"], self.grad_scale, s))
-                return loss
-            if self._dev_state is not None:
-                self._dev_state[1] += 1          # device-side step count (captured as a graph node)
-                for (p, g), st in zip(self._flat, self._flat_state):
-                    st["step"] += 1              # host mirror (checkpoints); during replay only the device copy advances
-                    rt.check(L.hupr_adam_step_dev_f32(rt.ptr(p), rt.ptr(g), rt.ptr(st["exp_avg"]), rt.ptr(st["exp_avg_sq"]),
-                                                      p.numel(), rt.ptr(self._dev_state), b1, b2, g0["eps"],
-                                                      g0["weight_decay"], self.grad_scale, s))
-                return loss
-            for (p, g), st in zip(self._flat, self._flat_state):
-                st["step"] += 1
-                rt.check(L.hupr_adam_step_f32(rt.ptr(p), rt.ptr(g), rt.ptr(st["exp_avg"]), rt.ptr(st["exp_avg_sq"]),
-                                              p.numel(), g0["lr"], b1, b2, g0["eps"], g0["weight_decay"], st["step"],
-                                              self.grad_scale, s))
-            return loss
-        for group in self.param_groups:
-            b1, b2 = group["betas"]
-            for p in group["params"]:
-                if p.grad is None:
-                    continue
-                st = self.state[p]
-                if len(st) == 0:
-                    st["step"] = torch.tensor(0.0)
-                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                st["step"] += 1
-                g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
-                rt.check(L.hupr_adam_step_f32(rt.ptr(p), rt.ptr(g), rt.ptr(st["exp_avg"]), rt.ptr(st["exp_avg_sq"]),
-                                              p.numel(), group["lr"], b1, b2, group["eps"], group["weight_decay"],
-                                              int(st["step"].item()), self.grad_scale, s))
-        return loss
+    def _launch_bucket(self, L, s, form, p, g, st, group):
+        b1, b2 = group["betas"]
+        arrays = (rt.ptr(p), rt.ptr(g), rt.ptr(st["exp_avg"]), rt.ptr(st["exp_avg_sq"]), p.numel())
+        hyper = (b1, b2, group["eps"], group["weight_decay"])
+        if form == "guard":
+            rt.check(L.hupr_adam_step_guard_f32(*arrays, rt.ptr(self._dev_state), rt.ptr(self._guard), *hyper, self.grad_scale, s))
+        elif form == "dev":
+            rt.check(L.hupr_adam_step_dev_f32(*arrays, rt.ptr(self._dev_state), *hyper, self.grad_scale, s))
+        else:
+            rt.check(L.hupr_adam_step_f32(*arrays, group["lr"], *hyper, int(st["step"]), self.grad_scale, s))
+
+    def _launch_param(self, L, s, p, g, st, group):
+        if len(st) == 0:
+            st["step"] = torch.tensor(0.0)
+            st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+        st["step"] += 1
+        self._launch_bucket(L, s, "host", p, g, st, group)
 
 
 class FusedSGD(_FlatBucketOptimizer):
@@ -267,50 +272,22 @@ class FusedSGD(_FlatBucketOptimizer):
             self._check_group(group)
         super().load_state_dict({**state_dict, "param_groups": groups})
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        L = rt.lib()
-        s = rt.stream()
-        from .. import functional as F_
-        F_.invalidate_packed()             # parameters change below without bumping torch's version counters
-        if self._flat is not None:
-            g0 = self.param_groups[0]
-            if self._guard is not None:
-                self._guard_launches(L, s)       # advances the device-side step count unless the step is skipped
-                for (p, g), st in zip(self._flat, self._flat_state):
-                    rt.check(L.hupr_sgd_step_guard_f32(rt.ptr(p), rt.ptr(g), rt.ptr(st["momentum_buffer"]), p.numel(),
-                                                       rt.ptr(self._dev_state), rt.ptr(self._guard), g0["momentum"],
-                                                       g0["weight_decay"], self.grad_scale, s))
-                return loss
-            if self._dev_state is not None:
-                self._dev_state[1] += 1          # device-side step count (captured as a graph node): step 1 is the first
-                for (p, g), st in zip(self._flat, self._flat_state):
-                    st["step"] += 1              # host mirror (checkpoints); during replay only the device copy advances
-                    rt.check(L.hupr_sgd_step_dev_f32(rt.ptr(p), rt.ptr(g), rt.ptr(st["momentum_buffer"]), p.numel(),
-                                                     rt.ptr(self._dev_state), g0["momentum"], g0["weight_decay"],
-                                                     self.grad_scale, s))
-                return loss
-            for (p, g), st in zip(self._flat, self._flat_state):
-                st["step"] += 1
-                rt.check(L.hupr_sgd_step_f32(rt.ptr(p), rt.ptr(g), rt.ptr(st["momentum_buffer"]), p.numel(), g0["lr"],
-                                             g0["momentum"], g0["weight_decay"], int(st["step"] == 1), self.grad_scale, s))
-            return loss
-        for group in self.param_groups:
-            for p in group["params"]:
-                if p.grad is None:
-                    continue
-                st = self.state[p]
-                first = "momentum_buffer" not in st
-                if first:
-                    st["momentum_buffer"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
-                rt.check(L.hupr_sgd_step_f32(rt.ptr(p), rt.ptr(g), rt.ptr(st["momentum_buffer"]), p.numel(), group["lr"],
-                                             group["momentum"], group["weight_decay"], int(first), self.grad_scale, s))
-        return loss
+    def _launch_bucket(self, L, s, form, p, g, st, group, first=None):
+        arrays = (rt.ptr(p), rt.ptr(g), rt.ptr(st["momentum_buffer"]), p.numel())
+        hyper = (group["momentum"], group["weight_decay"])
+        if form == "guard":
+            rt.check(L.hupr_sgd_step_guard_f32(*arrays, rt.ptr(self._dev_state), rt.ptr(self._guard), *hyper, self.grad_scale, s))
+        elif form == "dev":
+            rt.check(L.hupr_sgd_step_dev_f32(*arrays, rt.ptr(self._dev_state), *hyper, self.grad_scale, s))
+        else:
+            first = st["step"] == 1 if first is None else first
+            rt.check(L.hupr_sgd_step_f32(*arrays, group["lr"], *hyper, int(first), self.grad_scale, s))
+
+    def _launch_param(self, L, s, p, g, st, group):
+        first = "momentum_buffer" not in st
+        if first:
+            st["momentum_buffer"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+        self._launch_bucket(L, s, "host", p, g, st, group, first)
 
 
 def grad_clip_setting(cfg):

@@ -560,7 +560,7 @@ int hupr_sgd_step_f32(float* p, const float* g, float* momentum_buf, long n, flo
 int hupr_sgd_step_dev_f32(float* p, const float* g, float* momentum_buf, long n, const float* dev_state,
                           float momentum, float weight_decay, float gscale, hupr_stream_t stream);
 
-/* (a11) Gradient guard: global-norm clipping and the skip of a non-finite step, decided on the device (csrc/grad_guard.hip).
+/* (a11) Gradient guard: global-norm clipping and the skip of a non-finite step, decided on the device (csrc/optim.hip).
  * New, no reference counterpart: the reference steps on whatever backward left (tools/run.py:78-79).  Per optimiser step and
  * stream: hupr_grad_sumsq_f32 once per gradient bucket, hupr_grad_guard_f32 once, then the *_step_guard_f32 entry per bucket.
  * No atomics: results are bit-identical from run to run.  All of it is stream-ordered and capturable in a hipGraph. */
@@ -584,7 +584,7 @@ int hupr_adam_step_guard_f32(float* p, const float* g, float* exp_avg, float* ex
 int hupr_sgd_step_guard_f32(float* p, const float* g, float* momentum_buf, long n, const float* dev_state, const float* guard,
                             float momentum, float weight_decay, float gscale, hupr_stream_t stream);
 
-/* (a12) Exponential moving average of the weights, kept and swapped on the device (csrc/weight_ema.hip; TRAINING.emaDecay).
+/* (a12) Exponential moving average of the weights, kept and swapped on the device (csrc/optim.hip; TRAINING.emaDecay).
  * New, no reference counterpart: the reference evaluates `self.model` as trained, `tools/run.py:35-63`.  Per optimiser step and
  * stream, behind the optimiser's launches: hupr_ema_tick_f32 once, then hupr_ema_update_f32 once per parameter bucket.
  * No atomics: results are bit-identical from run to run.  All of it is stream-ordered and capturable in a hipGraph. */
