@@ -22,7 +22,8 @@ struct HaloArgs {
     int TD, log2TW;          // tile: TD x 8 x (1 << log2TW), TD * 8 * TW == 128
     int nd, nh, nw;          // tiles per axis
     int n_co_tiles;
-    int ablate;              // profiling only: bit0 skip halo fill, bit1 skip MFMA stages, bit2 skip epilogue stores
+    int ablate;              // profiling only (128-voxel kernel): bit0 skip halo fill, bit2 skip epilogue stores; always 0 — its setter
+                             // hupr_debug_halo_ablate went with the script that used it (the debug header holds at most 13 entries)
     unsigned long long* trace;  // profiling only: s_memtime stamps of workgroup 0 / wave 0 (scripts/halo_trace.py) or null
     double* stats;           // 256-voxel kernel, bf16 output, no bias / residual: per-workgroup column sums [grid][2][Co] of the
                              // stored (rounded) output and its square — the BatchNorm statistics pass fused into the epilogue
@@ -70,6 +71,7 @@ void launch_conv_halo256(const HaloArgs& a, int route, hipStream_t s);
 bool conv_halo256_supported(const HaloArgs& a, int Bn, bool abf);
 bool conv_halo256_stats_ok(const HaloArgs& a, int Bn);                         // fused BatchNorm statistics available for this launch?
 void set_halo_tiles(int mask);                                                // test aid: which tiles of the 256-voxel kernel are in use (conv_halo256m_bf16.hip)
+void set_halo_two_plane(int on);                                              // A/B aid: 0 = depth-2 layers on the four-plane form of the 2 x 8 x 16 tile
 constexpr int kHalo256Grid = 256;      // persistent workgroups (= partial rows of HaloArgs::stats)
 
 // Epilogue of both kernels.  The MFMAs are issued as D' = W * X^T, so a lane holds ONE voxel (column lane & 31 of the

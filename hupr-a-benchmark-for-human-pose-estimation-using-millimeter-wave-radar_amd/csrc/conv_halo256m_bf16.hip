@@ -50,23 +50,45 @@ typedef float f32x4c __attribute__((ext_vector_type(4)));
 // 64-byte rows have their own bank keys (see the fragment addresses).  The kernel walks Ci / 32 chunks per tile, so it also takes 64-channel
 // layers (two chunks: the two halo images then replace the one 64-channel image); measured on layer 1 (64 -> 64, B = 32): 192 us against
 // 182 us of the KC = 64 form (207 us with one image and a commit burst per chunk) — not dispatched (profiles/r06_conv_ci32_ab.txt).
-template <int TD, int TH, int TW, int KD, int NCOT = 0, int NWN = 2, int KC = 64>
+// TP (two planes; the 2 x 8 x 16 tile at D = 2, encoder level 3 — launch_conv_halo256 takes it exactly when TD == 2, D == 2, nd == 1):
+// the tile spans the whole depth, so the first and last of the general form's four halo planes are always the zero padding, and a
+// third of its MFMAs (the depth-0 waves in the kz = 0 stages, the depth-1 waves in the kz = 2 stages) add exact zeros.  This form
+// holds the two real planes only (2 x 10 x 18 voxels = 46 080 B, six halo items per thread instead of twelve; the padding planes are
+// never loaded, zeroed or read) and runs SIX stages per (tile, chunk): stage s = (phase s / 3, kx = s % 3).  In phase ph every wave
+// reads halo plane ph (= dz + kz - 1 for both depth groups — xlane has no depth term); the depth-0 waves (0-3) multiply by the weight
+// column (kz = ph + 1, kx), the depth-1 waves (4-7) by (kz = ph, kx): a stage carries TWO column images (Bs[2][6][8 KB] = 98 304 B,
+// six DMA pieces per stage; the kz = 1 column travels twice, from L2) and the waves differ in a wave-uniform offset folded into woff.
+// One wave of each group per SIMD: balanced.  Every output sums its non-zero products in the general form's order (depth 0: kz = 1, 2;
+// depth 1: kz = 0, 1; kx, kk, ky inside as before) and the dropped MFMAs only added +-0 to accumulators that started at +0: outputs
+// and statistics partials are bit for bit those of the four-plane form for finite weights (tests/test_conv_halo_two_plane_gpu.py).
+// The one visible difference: a NON-FINITE weight in a tap that only meets the padding gave NaN (0 x inf) and does not now.
+// Barrier waits: the six items ride under stage 0's six taps, so Y0, Y1, Y2 = 5, 1, 0 by the same formulas (+ 4 parked-tile stores in
+// stage 0); six stages per item keep the global stage counter even: the weight buffer of a stage is a compile-time st_ & 1.
+// Resources (gfx950): plain 204 registers, 0 spills; statistics 228 registers, 0 register spills (12 scalar spills); LDS 144 384 B
+// (general form: 240 / 256 registers, 0 / 2 spills, 141 312 B).  Measured (profiles/conv_two_plane_ab.txt, B = 32, 16 x 16 maps, one
+// process, alternating blocks): 128 -> 256 statistics 26.8 -> 21.9 us, 256 -> 256 statistics 45.2 -> 36.2, plain 43.1 -> 34.4,
+// residual 44.2 -> 35.7 (18-20 %; 33 % of the MFMAs removed, barriers, fills, stores and the epilogue stay); in the step (rocprofv3,
+// profiles/conv_two_plane_kernels_{before,after}.md) 46.0 -> 39.0 / 45.1 -> 38.2 / 27.9 -> 24.2 us.
+// hupr_debug_halo_two_plane(0) sends D = 2 launches to the general form (same route codes).
+template <int TD, int TH, int TW, int KD, int NCOT = 0, int NWN = 2, int KC = 64, bool TP = false>
 __global__ __launch_bounds__(512) void hupr_k_conv_halo256m_bf16(HaloArgs p) {
     constexpr int LDK = KC, BN = 32 * NWN, TS = KC == 64 ? 3 : 9, C8 = KC / 8, L2C8 = KC == 64 ? 3 : 2;
     static_assert(KC == 64 || (KC == 32 && KD == 3 && NWN == 2 && NCOT == 0), "32-channel rows: 3 x 3 x 3 taps, 64 output channels per tile");
-    constexpr int HD = TD + KD - 1, HH = TH + 2, HW = TW + 2;
+    static_assert(!TP || (TD == 2 && KD == 3 && NWN == 2 && KC == 64), "two-plane form: the 2 x 8 x 16 tile at D == 2 (launcher: nd == 1)");
+    constexpr int NIMG = TP ? 2 * TS : TS;                     // weight images per stage (TP: one (kz, kx) column per depth group)
+    constexpr int HD = TP ? TD : TD + KD - 1, HH = TH + 2, HW = TW + 2;
     static_assert(TD * TH * TW == 64 * (8 / NWN) && TH % 8 == 0 && TW % 8 == 0 && (KD == 1 || KD == 3) && (NWN == 2 || NCOT == 0),
                   "256 (512) voxels per tile, 8 x 8 per wave");
-    constexpr int NVOX = HD * HH * HW;                         // 600 (4 x 8 x 8) / 720 (2 x 8 x 16) halo voxels
-    constexpr int T = 9 * KD, NSTAGE = KC == 64 ? 3 * KD : KD, NTAP = KC == 64 ? 6 : 9;      // stage = (kz, kx); its taps: K-step kk (2) x ky (3)  [KC = 32: stage = kz; taps: kx (3) x ky (3)]
+    constexpr int NVOX = HD * HH * HW;                         // 600 (4 x 8 x 8) / 720 (2 x 8 x 16) / 360 (2 x 8 x 16, two planes) halo voxels
+    constexpr int T = 9 * KD, NSTAGE = TP ? 6 : (KC == 64 ? 3 * KD : KD), NTAP = KC == 64 ? 6 : 9;      // stage = (kz, kx); its taps: K-step kk (2) x ky (3)  [KC = 32: stage = kz; taps: kx (3) x ky (3)]
     // NWN = 1: the tile spans the whole depth (launcher: D == TD), so the halo's first and last planes are the zero padding — never
     // loaded, zeroed once in the prologue; the items cover planes 1 .. TD only (13 per thread instead of 16: the register file is full)
     constexpr bool FULLD = NWN == 1;
     constexpr int NVOXL = FULLD ? TD * HH * HW : NVOX, VOX0 = FULLD ? HH * HW : 0;
-    constexpr int NH = (NVOXL * C8 + 511) / 512;               // 10 / 12 / 13 halo items (8 channels of a voxel) per thread
+    constexpr int NH = (NVOXL * C8 + 511) / 512;               // 10 / 12 / 13 (TP: 6) halo items (8 channels of a voxel) per thread
     // items are issued one per tap from the item's first tap on; in front of the barriers of stages 0, 1, 2 (each in front of the stage's
     // sixth tap) the items of taps 6 s - 1 .. 6 s + 4 are younger than the weight pieces the barrier waits for
-    // (stage s: the items NTAP s - 1 .. NTAP s + NTAP - 2)
+    // (stage s: the items NTAP s - 1 .. NTAP s + NTAP - 2; TP, NH = 6: 5, 1, 0 — the six items ride under stage 0's six taps)
     constexpr int Y0 = NH < NTAP - 1 ? NH : NTAP - 1, Y1 = NH - (NTAP - 1) < 0 ? 0 : (NH - (NTAP - 1) > NTAP ? NTAP : NH - (NTAP - 1)),
                   Y2 = NH - (2 * NTAP - 1) < 0 ? 0 : (NH - (2 * NTAP - 1) > NTAP ? NTAP : NH - (2 * NTAP - 1));
     static_assert(NH <= NTAP * NSTAGE - 1 && NH <= 3 * NTAP - 1, "halo items must all be issued in front of the item's last barrier (and within three stages)");
@@ -74,7 +96,7 @@ __global__ __launch_bounds__(512) void hupr_k_conv_halo256m_bf16(HaloArgs p) {
     // is committed to the other one, one ds_write_b128 per tap under the MFMAs of the item's last stage — no commit burst and no barrier
     // at the item boundary (the last stage's barrier already stands between those writes and the first reads of the next item)
     __shared__ __attribute__((aligned(16))) __bf16 Hs[(KC == 32 ? 2 : 1) * NVOX * LDK];
-    __shared__ __attribute__((aligned(16))) __bf16 Bs[2][TS][BN * LDK];
+    __shared__ __attribute__((aligned(16))) __bf16 Bs[2][NIMG][BN * LDK];
     // fused BatchNorm statistics: per lane and output-channel tile the running sums of its eight channels over its voxels (bf16-ROUNDED
     // outputs) in REGISTERS — ssum / ssq [tile][cg][r] — reduced over the sixteen voxel lanes and the four voxel-block waves once,
     // after the tile loop, in double (through the halo image's LDS, dead by then)
@@ -101,7 +123,7 @@ __global__ __launch_bounds__(512) void hupr_k_conv_halo256m_bf16(HaloArgs p) {
     const int wrow_ = NWN == 2 ? 8 * wave + (lane >> 3) : ((8 * wave + (lane >> 3)) & 31);
     const int wsrc_lane = (wrow_ * T * p.Ci + (((lane & 7) ^ (wrow_ >> 1)) & 7) * 8) * 2 +
                           (NWN == 2 ? 0 : (wave >> 2) * (3 * p.Ci * 2));                       // bytes; < 2^31
-    constexpr int NDMA = NWN == 2 ? TS : 2, DMA_TAPS = NWN == 2 ? 1 : 2;
+    constexpr int NDMA = NWN == 2 ? NIMG : 2, DMA_TAPS = NWN == 2 ? 1 : 2;
     // KC = 32: piece pc = 8 j + wave (1 KB = 16 rows of 64 B) of a stage's 36: tap slot pc >> 2 = kx * 3 + ky, rows 16 (pc & 3) + (lane >> 2);
     // chunk c of weight row n lives at position c ^ (((n >> 3) & 1) << 1) (the four rows n = v mod 4 of a ds_read_b128 lane group then
     // hold four different positions)
@@ -129,13 +151,17 @@ __global__ __launch_bounds__(512) void hupr_k_conv_halo256m_bf16(HaloArgs p) {
         const int wbase_ = (((COT_) * BN * T + ((S_) / 3) * 9 + ((S_) % 3)) * p.Ci + (CH_) * KC) * 2 + wsrc_lane;   \
         _Pragma("unroll") for (int j = 0; j < NDMA; ++j) {                                                          \
             if (NWN == 2 || j == 0 || wave < 4) {                                                                   \
+                /* TP: stage S_ = (phase S_ / 3, kx): images 0-2 = column (kz = phase + 1, kx) for the depth-0 waves, */ \
+                /* images 3-5 = column (kz = phase, kx) for the depth-1 waves; ky = j % 3 either way */               \
+                const int tap_ = (j < 3 ? 9 : 0) + 3 * (j % 3);                                                     \
                 unsigned keep_;                                                                                     \
                 asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %3, 0 offen lds\n\t" \
                              "s_mov_b32 m0, %0"                                                                     \
                              : "=&s"(keep_)                                                                         \
-                             : "s"(NWN == 2 ? wdst_wave + ((PAR_) * TS + j) * (BN * LDK * 2)                        \
+                             : "s"(NWN == 2 ? wdst_wave + ((PAR_) * NIMG + j) * (BN * LDK * 2)                      \
                                             : wdst_wave + (PAR_) * TS * (BN * LDK * 2) + j * 8192),                 \
-                               "v"(NWN == 2 ? wbase_ + j * (3 * p.Ci * 2) : wbase_ + j * DMA_TAPS * (3 * p.Ci * 2)), "s"(wrs) \
+                               "v"(TP ? wbase_ + tap_ * (p.Ci * 2)                                                  \
+                                      : (NWN == 2 ? wbase_ + j * (3 * p.Ci * 2) : wbase_ + j * DMA_TAPS * (3 * p.Ci * 2))), "s"(wrs) \
                              : "memory");                                                                           \
             }                                                                                                       \
         }                                                                                                           \
@@ -152,7 +178,7 @@ __global__ __launch_bounds__(512) void hupr_k_conv_halo256m_bf16(HaloArgs p) {
         const int hx = vox % HW;                                                                                    \
         const int t_ = vox / HW;                                                                                    \
         const int hy = t_ % HH, hz = t_ / HH;                                                                       \
-        const int d = (D0_) + hz - (FULLD ? 0 : KD / 2), h = (H0_) + hy - 1, w = (W0_) + hx - 1;                    \
+        const int d = (D0_) + hz - (FULLD || TP ? 0 : KD / 2), h = (H0_) + hy - 1, w = (W0_) + hx - 1;                    \
         const bool ok = (COND_) && it < NVOXL * C8 && (unsigned)d < (unsigned)p.D && (unsigned)h < (unsigned)p.H && \
                         (unsigned)w < (unsigned)p.W;                                                                \
         const int off = (((((B_) * p.D + d) * p.H + h) * p.W + w) * p.in_ld + (C0_) + c8 * 8) * 2;                  \
@@ -203,12 +229,14 @@ __global__ __launch_bounds__(512) void hupr_k_conv_halo256m_bf16(HaloArgs p) {
         for (int kk = 0; kk < 2; ++kk) {
             const int n = 32 * wn + 16 * cg + idx;
             woff[cg][kk] = KC == 64 ? n * LDK + (((4 * kk + kq) ^ ((n >> 1) & 7)) << 3) : n * LDK + ((kq ^ (((n >> 3) & 1) << 1)) << 3);
+            if constexpr (TP) woff[cg][kk] += dzw * (TS * BN * LDK);      // wave-uniform: the depth-1 waves multiply by images 3-5 of a stage
         }
     // activations: halo voxel (wm + kz, rho + yy, wx + kx).  Halo row swizzle of THIS kernel: 16-byte chunk c of voxel (hy, hx) lives at
     // chunk c ^ (((hx >> 1) & 3) << 1).  A 16-lane ds_read_b128 group holds eight lanes of chunk parity 0 and eight of parity 1 such
     // that the two rows yy of a column differ in that parity; voxel pitch 128 B puts the column parity into bank bit 5; the key separates
     // the four columns of one parity in chunk bits 1-2: all 64 banks, every tap (SQ_LDS_BANK_CONFLICT = 0, profiles/r04b_conv_sq_pmc.txt)
-    const int xlane = ((dzw * HH + yw0 + yy) * HW + xw0 + wx) * LDK;
+    // (TP: in phase ph every wave reads halo plane ph = dz + kz - 1 — no depth term; the depth groups differ in their weight column only)
+    const int xlane = (((TP ? 0 : dzw) * HH + yw0 + yy) * HW + xw0 + wx) * LDK;
     // KC = 32 (64-byte rows): a voxel's four chunks sit at chunk ^ ((halo row & 1) << 1).  A ds_read_b128 lane group holds, for each
     // voxel class (index mod 4 = a 64-byte bank quarter), the four lanes (kq, row), (kq, row + 1), (kq + 1, row), (kq + 1, row + 1): positions
     // kq ^ {0, 2} and (kq + 1) ^ {0, 2} — all four.  KK_ there = kx (the stage is the kz plane ST_).
@@ -227,7 +255,8 @@ __global__ __launch_bounds__(512) void hupr_k_conv_halo256m_bf16(HaloArgs p) {
               : *reinterpret_cast<const bf16x8*>(&Hs[hrd + xlane + (((ST_) * HH + (RHO_)) * HW + (KK_)) * LDK +     \
                     ((kq ^ (((yy + (RHO_)) & 1) << 1)) << 3)]))
 #define HUPR_WF(BUF_, KY_, CG_, KK_)                                                                                \
-    (KC == 64 ? *reinterpret_cast<const bf16x8*>(&Bs[BUF_][KY_][woff[CG_][KK_]])                                    \
+    (TP ? *reinterpret_cast<const bf16x8*>(&Bs[0][0][0] + ((BUF_) * NIMG + (KY_)) * (BN * LDK) + woff[CG_][KK_])    \
+     : KC == 64 ? *reinterpret_cast<const bf16x8*>(&Bs[BUF_][KY_][woff[CG_][KK_]])                                  \
               : *reinterpret_cast<const bf16x8*>(&Bs[BUF_][3 * (KK_) + (KY_)][woff[CG_][0]]))
 
     f32x4c c[4][2];
@@ -327,7 +356,7 @@ __global__ __launch_bounds__(512) void hupr_k_conv_halo256m_bf16(HaloArgs p) {
         }
 #pragma unroll
         for (int st_ = 0; st_ < NSTAGE; ++st_) {
-            const int par = (g + st_) & 1;
+            const int par = TP ? (st_ & 1) : ((g + st_) & 1);      // (TP: six stages per item — g stays even)
 #pragma unroll
             for (int tau = 0; tau < NTAP; ++tau) {
                 const int kk = tau / 3, ky = tau % 3;
@@ -545,17 +574,29 @@ __global__ __launch_bounds__(512) void hupr_k_conv_halo256m_bf16(HaloArgs p) {
 #undef HUPR_VMCNT_LGKM0
 }
 
+// A/B aid (hupr_debug_halo_two_plane): 0 = depth-2 layers on the general four-plane instantiation of the 2 x 8 x 16 tile (same route code)
+static int g_halo_two_plane = 1;
+void set_halo_two_plane(int on) { g_halo_two_plane = on; }
+
 void launch_conv_halo256(const HaloArgs& a, int route, hipStream_t s) {      // one persistent workgroup per CU
     const dim3 grid(kHalo256Grid), wg(512);
+    // the 2 x 8 x 16 tile spans the whole depth: the two-plane form (every other depth, D = 6 for one, has interior tiles: four planes)
+    const bool tp = g_halo_two_plane && a.TD == 2 && a.D == 2 && a.nd == 1;
     switch (route) {
     case kRouteCi32: HUPR_LAUNCH((hupr_k_conv_halo256m_bf16<4, 8, 8, 3, 0, 2, 32>), grid, wg, 0, s, a); break;
     case kRouteCo32: HUPR_LAUNCH((hupr_k_conv_halo256m_bf16<8, 8, 8, 3, 0, 1>), grid, wg, 0, s, a); break;
     case kRoute1x16x16: HUPR_LAUNCH((hupr_k_conv_halo256m_bf16<1, 16, 16, 1>), grid, wg, 0, s, a); break;
     case kRouteStats4x8x8One: HUPR_LAUNCH((hupr_k_conv_halo256m_bf16<4, 8, 8, 3, 1>), grid, wg, 0, s, a); break;
     case kRouteStats4x8x8Two: HUPR_LAUNCH((hupr_k_conv_halo256m_bf16<4, 8, 8, 3, 2>), grid, wg, 0, s, a); break;
-    case kRouteStats2x8x16: HUPR_LAUNCH((hupr_k_conv_halo256m_bf16<2, 8, 16, 3, 1>), grid, wg, 0, s, a); break;
+    case kRouteStats2x8x16:
+        if (tp) HUPR_LAUNCH((hupr_k_conv_halo256m_bf16<2, 8, 16, 3, 1, 2, 64, true>), grid, wg, 0, s, a);
+        else HUPR_LAUNCH((hupr_k_conv_halo256m_bf16<2, 8, 16, 3, 1>), grid, wg, 0, s, a);
+        break;
     case kRoute4x8x8: HUPR_LAUNCH((hupr_k_conv_halo256m_bf16<4, 8, 8, 3>), grid, wg, 0, s, a); break;
-    case kRoute2x8x16: HUPR_LAUNCH((hupr_k_conv_halo256m_bf16<2, 8, 16, 3>), grid, wg, 0, s, a); break;
+    case kRoute2x8x16:
+        if (tp) HUPR_LAUNCH((hupr_k_conv_halo256m_bf16<2, 8, 16, 3, 0, 2, 64, true>), grid, wg, 0, s, a);
+        else HUPR_LAUNCH((hupr_k_conv_halo256m_bf16<2, 8, 16, 3>), grid, wg, 0, s, a);
+        break;
     }
 }
 

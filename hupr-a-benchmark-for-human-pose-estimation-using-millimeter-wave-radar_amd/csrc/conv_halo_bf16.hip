@@ -403,13 +403,12 @@ extern "C" int hupr_pack_conv_weights_bf16(const float* w, void* wp_bf16, int Co
     return HUPR_OK;
 }
 
-static int g_halo_ablate = 0;
 static int g_halo_variant = 0;      // 0 auto, 1 force the 128-voxel kernel (A/B comparisons)
 static unsigned long long* g_halo_trace = nullptr;
 extern "C" void hupr_debug_halo_trace(void* buf) { g_halo_trace = reinterpret_cast<unsigned long long*>(buf); }
-extern "C" void hupr_debug_halo_ablate(int bits) { g_halo_ablate = bits; }   // profiling aids (scripts/halo_ablation.py)
 extern "C" void hupr_debug_halo_variant(int v) { g_halo_variant = v; }
 extern "C" void hupr_debug_halo_tiles(int mask) { set_halo_tiles(mask); }      // 256-voxel kernel: bit 0 / 1 / 2 = its 4 x 8 x 8 / 2 x 8 x 16 / 1 x 16 x 16 tile in use
+extern "C" void hupr_debug_halo_two_plane(int on) { set_halo_two_plane(on); }  // 256-voxel kernel, D = 2: 0 = the four-plane form of the 2 x 8 x 16 tile
 static int g_halo_split_k = 1;      // A/B aid: 0 = never slice the reduction of small grids
 extern "C" void hupr_debug_halo_split_k(int on) { g_halo_split_k = on; }
 
@@ -498,7 +497,7 @@ static int conv3x3_halo(const void* x, const void* wp_bf16, const float* bias, c
     a.x = x; a.wp = reinterpret_cast<const __bf16*>(wp_bf16); a.bias = bias; a.res = res; a.y = y;
     a.Bn = Bn; a.D = D; a.H = H; a.W = W; a.Ci = Ci; a.in_ld = in_ld; a.Co = Co; a.out_ld = out_ld; a.res_ld = res_ld;
     a.kd = kd;
-    a.ablate = g_halo_ablate;
+    a.ablate = 0;
     a.trace = g_halo_trace;
     a.stats = stats;
     a.part = nullptr;
@@ -606,7 +605,7 @@ extern "C" int hupr_conv3x3_halo_bf16act_partial(const void* x, const void* wp_b
 extern "C" int hupr_conv3x3_halo_stats_supported(int Bn, int D, int H, int W, int Ci, int Co, int kd) {
     HaloArgs a{};
     a.kd = kd; a.D = D; a.H = H; a.W = W; a.Ci = Ci; a.Co = Co; a.in_ld = Ci;
-    a.ablate = g_halo_ablate; a.trace = g_halo_trace;
+    a.trace = g_halo_trace;
     return (Bn > 0 && conv_halo256_stats_ok(a, Bn)) ? 1 : 0;
 }
 extern "C" int hupr_conv3x3_halo_stats_rows(void) { return kHalo256Grid; }

@@ -79,9 +79,9 @@ SIGNATURES = {
                                     + [c_long, c_int, c_void_p]),
     "hupr_pack_conv_weights_table": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     "hupr_debug_attn_trace": (None, [c_void_p]),
-    "hupr_debug_halo_ablate": (None, [c_int]),
     "hupr_debug_halo_variant": (None, [c_int]),
     "hupr_debug_halo_tiles": (None, [c_int]),
+    "hupr_debug_halo_two_plane": (None, [c_int]),
     "hupr_debug_halo_trace": (None, [c_void_p]),
     "hupr_debug_wgrad_ci32": (None, [c_int]),
     "hupr_debug_wgrad_m16": (None, [c_int]),
