@@ -1,4 +1,4 @@
-// The optimiser family: the fused Adam and SGD-momentum steps, the gradient guard in front of them and the weight average behind
+// The optimiser family: the fused Adam, SGD-momentum and LAMB steps, the gradient guard in front of them and the weight average behind
 // them.  All of it streams over the flat parameter / gradient buckets once per step and is HBM-bound.
 //
 // Adam and SGD (reference tools/base.py:44-47: SGD momentum 0.9 / Adam, coupled L2 decay), three forms each:
@@ -24,6 +24,18 @@
 // 8 B read + 4 B written (update), 8 B + 8 B (swap) per element.  float4 accesses where both arrays share their offset to a 16-byte
 // boundary, 4-byte accesses otherwise; the update is one explicit fmaf on every path, so the bits do not depend on the path.
 //
+// LAMB (You et al. 2020, the update rule of apex's FusedLAMB): Adam's direction rescaled per parameter tensor by the trust ratio
+// |p| / |u|.  New, no reference counterpart (the reference's choice is tools/base.py:44-47).  A parameter tensor is a segment of its
+// flat bucket; the norms per tensor are a segmented reduction over a chunk table built on the host from the bucket layout: every
+// segment is cut from its own start into chunks of kLambChunk elements, so a chunk never spans two tensors.
+//   hupr_lamb_stage1_f32   one launch per bucket, one workgroup per chunk: new m and v, u, one fp64 pair {sum p^2, sum u^2} per chunk
+//   hupr_lamb_ratio_f32    one launch per bucket, one workgroup per segment: the chunk pairs added in table order -> |p|, |u|, r
+//   hupr_lamb_stage2_f32   one launch per bucket: u recomputed from p, m, v by stage 1's lamb_u, p <- p - lr r u
+// 16 B read + 8 B written (stage 1), 12 B + 4 B (stage 2): 40 B per element, as much as a stored u would cost.  {lr, step} always
+// come from device memory and the guard pointer is nullable.  Thread t of a chunk's workgroup takes elements 4t .. 4t + 3 of every
+// 1024 of the chunk, as one float4 where the chunk starts on a 16-byte boundary in every array and 4 bytes at a time otherwise,
+// through the same per-element function: which thread adds which element depends on the segment lengths alone.
+//
 // No atomics anywhere: every element belongs to one thread, and which thread adds which element of the square sum, and every
 // reduction order, are fixed by (n, alignment of g) alone, so the result is bit-identical from run to run.
 #include <type_traits>
@@ -37,6 +49,7 @@ constexpr int kThreads = 256;
 constexpr int kPartials = 1024;       // workgroups per hupr_grad_sumsq_f32 launch = partials it writes (4 per CU on 256 CUs)
 constexpr long kMaxBlocks = 2048;     // 8 workgroups per CU on 256 CUs; the rest of the array is walked grid-stride
 constexpr long kAdamBlocks = 8192;
+constexpr int kLambChunk = 2048;      // elements per chunk of the LAMB table = per workgroup of stages 1 and 2: two rounds of 256 float4
 
 template <int U> using Unroll = std::integral_constant<int, U>;
 
@@ -442,5 +455,232 @@ extern "C" int hupr_swap_f32(float* a, float* b, long n, hupr_stream_t stream) {
     const Span w = span_of(a, n, vec);
     HUPR_LAUNCH(hupr_k_swap, grid_for(vec ? w.n4 / 2 : n, kMaxBlocks), dim3(kThreads), 0, as_stream(stream), a, b, n, w.head, w.n4);
     HUPR_LAUNCH_OK("hupr_k_swap");
+    return HUPR_OK;
+}
+
+// ---- LAMB ----
+// The chunk table, int64 words (tools/optim.py lamb_chunk_table builds it, lamb_table_ok below checks the host copy in front of
+// every launch, the kernels read the device copy):
+//   [0] segments S   [1] chunks K   [2] chunk size   [3] n
+//   S x {start, length, first chunk, chunk count, adapted}     segments tile [0, n) in order
+//   K x {segment, start relative to the segment}                chunks of a segment are consecutive, relative starts 0, C, 2C, ...
+namespace {
+constexpr int kLambHead = 4, kLambSegWords = 5, kLambChunkWords = 2;
+
+const char* lamb_table_error(const long* t, long words, long n) {
+    if (words < kLambHead) return "shorter than its header";
+    const long S = t[0], K = t[1];
+    if (t[2] != kLambChunk) return "built for another chunk size than hupr_lamb_chunk()";
+    if (t[3] != n) return "built for another n";
+    if (S <= 0 || K <= 0 || S > n || K > n || K > 0x7fffffffL) return "segment or chunk count out of range";
+    if (words != kLambHead + kLambSegWords * S + kLambChunkWords * K) return "length does not match its segment and chunk counts";
+    const long* seg = t + kLambHead;
+    const long* chunk = seg + kLambSegWords * S;
+    long at = 0, first = 0;
+    for (long s = 0; s < S; ++s, seg += kLambSegWords) {
+        if (seg[0] < at) return "segments overlap";
+        if (seg[0] > at) return "segments leave a gap";
+        if (seg[1] <= 0 || seg[1] > n - at) return "a segment is empty or runs past n";
+        const long count = (seg[1] + kLambChunk - 1) / kLambChunk;
+        if (seg[2] != first || seg[3] != count || first + count > K) return "a segment's chunk range is not ceil(length / chunk) from the last one's end";
+        if (seg[4] != 0 && seg[4] != 1) return "an adapted flag is neither 0 nor 1";
+        for (long k = 0; k < count; ++k)
+            if (chunk[kLambChunkWords * (first + k)] != s || chunk[kLambChunkWords * (first + k) + 1] != k * kLambChunk)
+                return "a chunk does not sit at its place in its segment";
+        at += seg[1];
+        first += count;
+    }
+    if (at != n) return "segments do not reach n";
+    if (first != K) return "chunks left over behind the last segment";
+    return nullptr;
+}
+
+// The bias corrections of step `step` in the form of adam_bias_corrections.  The betas stay fp64 up to here and 1 - beta is rounded
+// to fp32 once: 1.f - 0.999f is 1.3e-5 away from 0.001, which a norm ratio over a whole tensor does not average out
+__device__ __forceinline__ void lamb_bias_corrections(double b1, double b2, float step_f, float& bc1, float& bc2_sqrt) {
+    const double step = (double)step_f;
+    bc1 = (float)(1.0 - pow(b1, step));
+    bc2_sqrt = (float)sqrt(1.0 - pow(b2, step));
+}
+
+// Adam's direction plus the decoupled decay of an adapted tensor.  THE function of both stages: stage 2 sees stage 1's bits
+__device__ __forceinline__ float lamb_u(float p, float m, float v, float bc1, float bc2_sqrt, float eps, float wd, bool adapted) {
+#pragma clang fp contract(off)
+    const float d = (m / bc1) / (sqrtf(v) / bc2_sqrt + eps);
+    return adapted ? fmaf(wd, p, d) : d;
+}
+
+// new moments (Adam's, without its coupled decay) and u for one element; the squares go to the thread's fp64 sums
+__device__ __forceinline__ void lamb_elem1(float p, float g, float& m, float& v, float gs, float b1, float b2, float omb1,
+                                           float omb2, float bc1, float bc2_sqrt, float eps, float wd, bool adapted, double& sp,
+                                           double& su) {
+#pragma clang fp contract(off)
+    const float gr = g * gs;
+    m = fmaf(b1, m, omb1 * gr);
+    v = fmaf(b2, v, omb2 * gr * gr);
+    const float u = lamb_u(p, m, v, bc1, bc2_sqrt, eps, wd, adapted);
+    sp = fma((double)p, (double)p, sp);
+    su = fma((double)u, (double)u, su);
+}
+
+struct LambChunk { long base; int len; int seg; bool adapted; };
+__device__ __forceinline__ LambChunk lamb_chunk_of(const long* __restrict__ table) {
+    const long* seg = table + kLambHead;
+    const long* chunk = seg + kLambSegWords * table[0] + kLambChunkWords * (long)blockIdx.x;
+    seg += kLambSegWords * chunk[0];
+    const long left = seg[1] - chunk[1];
+    return {seg[0] + chunk[1], (int)(left < kLambChunk ? left : kLambChunk), (int)chunk[0], seg[4] != 0};
+}
+
+__device__ __forceinline__ bool aligned16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
+}  // namespace
+
+__global__ __launch_bounds__(kThreads) void hupr_k_lamb_stage1(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                               float* __restrict__ v, const long* __restrict__ table,
+                                                               const float* __restrict__ state, const float* __restrict__ guard,
+                                                               double beta1, double beta2, float eps, float wd, float gscale,
+                                                               double* __restrict__ partials) {
+    if (guard && guard[3] == 0.f) return;
+    const float gs = guard ? gscale * guard[0] : gscale;
+    const float b1 = (float)beta1, b2 = (float)beta2, omb1 = (float)(1.0 - beta1), omb2 = (float)(1.0 - beta2);
+    float bc1, bc2_sqrt;
+    lamb_bias_corrections(beta1, beta2, state[1], bc1, bc2_sqrt);
+    const LambChunk c = lamb_chunk_of(table);
+    p += c.base, g += c.base, m += c.base, v += c.base;
+    const bool vec = aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v);
+    double sp = 0.0, su = 0.0;
+#pragma unroll
+    for (int e = 4 * threadIdx.x; e < kLambChunk; e += 4 * kThreads) {
+        if (vec && e + 4 <= c.len) {
+            const float4 pv = *reinterpret_cast<const float4*>(p + e), gv = *reinterpret_cast<const float4*>(g + e);
+            float4 mv = *reinterpret_cast<const float4*>(m + e), vv = *reinterpret_cast<const float4*>(v + e);
+            lamb_elem1(pv.x, gv.x, mv.x, vv.x, gs, b1, b2, omb1, omb2, bc1, bc2_sqrt, eps, wd, c.adapted, sp, su);
+            lamb_elem1(pv.y, gv.y, mv.y, vv.y, gs, b1, b2, omb1, omb2, bc1, bc2_sqrt, eps, wd, c.adapted, sp, su);
+            lamb_elem1(pv.z, gv.z, mv.z, vv.z, gs, b1, b2, omb1, omb2, bc1, bc2_sqrt, eps, wd, c.adapted, sp, su);
+            lamb_elem1(pv.w, gv.w, mv.w, vv.w, gs, b1, b2, omb1, omb2, bc1, bc2_sqrt, eps, wd, c.adapted, sp, su);
+            *reinterpret_cast<float4*>(m + e) = mv;
+            *reinterpret_cast<float4*>(v + e) = vv;
+        } else {
+            for (int k = e; k < e + 4 && k < c.len; ++k) {
+                float mv = m[k], vv = v[k];
+                lamb_elem1(p[k], g[k], mv, vv, gs, b1, b2, omb1, omb2, bc1, bc2_sqrt, eps, wd, c.adapted, sp, su);
+                m[k] = mv;
+                v[k] = vv;
+            }
+        }
+    }
+    const double tp = block_sum_f64(sp);
+    __syncthreads();                                        // block_sum_f64's staging is reused
+    const double tu = block_sum_f64(su);
+    if (threadIdx.x == 0) {
+        partials[2 * (long)blockIdx.x] = tp;
+        partials[2 * (long)blockIdx.x + 1] = tu;
+    }
+}
+
+// One workgroup per segment; thread t adds the pairs of the segment's chunks t, t + 256, ... in order.  stats = |p|, |u|, r, S each
+__global__ __launch_bounds__(kThreads) void hupr_k_lamb_ratio(const double* __restrict__ partials, const long* __restrict__ table,
+                                                              const float* __restrict__ guard, float* __restrict__ stats) {
+    if (guard && guard[3] == 0.f) return;
+    const long S = table[0];
+    const long* seg = table + kLambHead + kLambSegWords * (long)blockIdx.x;
+    const long first = seg[2], count = seg[3];
+    double sp = 0.0, su = 0.0;
+    for (long k = threadIdx.x; k < count; k += kThreads) {
+        sp += partials[2 * (first + k)];
+        su += partials[2 * (first + k) + 1];
+    }
+    const double tp = block_sum_f64(sp);
+    __syncthreads();
+    const double tu = block_sum_f64(su);
+    if (threadIdx.x != 0) return;
+    const double pn = sqrt(tp), un = sqrt(tu);
+    stats[blockIdx.x] = (float)pn;
+    stats[S + blockIdx.x] = (float)un;
+    stats[2 * S + blockIdx.x] = seg[4] != 0 && pn > 0.0 && un > 0.0 ? (float)(pn / un) : 1.f;
+}
+
+__global__ __launch_bounds__(kThreads) void hupr_k_lamb_stage2(float* __restrict__ p, const float* __restrict__ m,
+                                                               const float* __restrict__ v, const long* __restrict__ table,
+                                                               const float* __restrict__ state, const float* __restrict__ guard,
+                                                               double beta1, double beta2, float eps, float wd,
+                                                               const float* __restrict__ stats) {
+    if (guard && guard[3] == 0.f) return;
+    float bc1, bc2_sqrt;
+    lamb_bias_corrections(beta1, beta2, state[1], bc1, bc2_sqrt);
+    const LambChunk c = lamb_chunk_of(table);
+    const float step = state[0] * stats[2 * table[0] + c.seg];             // lr r: one fp32 product
+    p += c.base, m += c.base, v += c.base;
+    const bool vec = aligned16(p) && aligned16(m) && aligned16(v);
+#pragma unroll
+    for (int e = 4 * threadIdx.x; e < kLambChunk; e += 4 * kThreads) {
+        if (vec && e + 4 <= c.len) {
+            float4 pv = *reinterpret_cast<const float4*>(p + e);
+            const float4 mv = *reinterpret_cast<const float4*>(m + e), vv = *reinterpret_cast<const float4*>(v + e);
+            pv.x = fmaf(-step, lamb_u(pv.x, mv.x, vv.x, bc1, bc2_sqrt, eps, wd, c.adapted), pv.x);
+            pv.y = fmaf(-step, lamb_u(pv.y, mv.y, vv.y, bc1, bc2_sqrt, eps, wd, c.adapted), pv.y);
+            pv.z = fmaf(-step, lamb_u(pv.z, mv.z, vv.z, bc1, bc2_sqrt, eps, wd, c.adapted), pv.z);
+            pv.w = fmaf(-step, lamb_u(pv.w, mv.w, vv.w, bc1, bc2_sqrt, eps, wd, c.adapted), pv.w);
+            *reinterpret_cast<float4*>(p + e) = pv;
+        } else {
+            for (int k = e; k < e + 4 && k < c.len; ++k) p[k] = fmaf(-step, lamb_u(p[k], m[k], v[k], bc1, bc2_sqrt, eps, wd, c.adapted), p[k]);
+        }
+    }
+}
+
+extern "C" int hupr_lamb_chunk(void) { return kLambChunk; }
+
+// host only, no launch: 0 when table_host[0 .. words) is a chunk table over [0, n) as documented above
+extern "C" int hupr_lamb_table_check(const long* table_host, long words, long n) {
+    HUPR_REQUIRE(table_host && n > 0, "hupr_lamb_table_check: bad argument (null table or n <= 0)");
+    const char* why = lamb_table_error(table_host, words, n);
+    HUPR_REQUIRE(!why, "hupr_lamb_table_check: bad chunk table: %s", why);
+    return HUPR_OK;
+}
+
+#define HUPR_LAMB_TABLE(name)                                                                       \
+    do {                                                                                            \
+        const char* why__ = lamb_table_error(table_host, words, n);                                 \
+        HUPR_REQUIRE(!why__, name ": bad chunk table: %s", why__);                                  \
+    } while (0)
+
+// table_host / table_dev: the same chunk table in host and in device memory (words int64 each); partials: 2 doubles per chunk
+extern "C" int hupr_lamb_stage1_f32(float* p, const float* g, float* exp_avg, float* exp_avg_sq, long n, const long* table_host,
+                                    long words, const long* table_dev, const float* dev_state, const float* guard, double beta1,
+                                    double beta2, float eps, float weight_decay, float gscale, double* partials,
+                                    hupr_stream_t stream) {
+    HUPR_REQUIRE(p && g && exp_avg && exp_avg_sq && table_host && table_dev && dev_state && partials && n > 0,
+                 "hupr_lamb_stage1_f32: bad argument (null pointer or n <= 0)");
+    HUPR_REQUIRE((reinterpret_cast<uintptr_t>(partials) & 7) == 0, "hupr_lamb_stage1_f32: partials must be 8-byte aligned");
+    HUPR_REQUIRE(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0, "hupr_lamb_stage1_f32: betas must be inside [0, 1)");
+    HUPR_LAMB_TABLE("hupr_lamb_stage1_f32");
+    HUPR_LAUNCH(hupr_k_lamb_stage1, dim3((unsigned)table_host[1]), dim3(kThreads), 0, as_stream(stream), p, g, exp_avg, exp_avg_sq,
+                table_dev, dev_state, guard, beta1, beta2, eps, weight_decay, gscale, partials);
+    HUPR_LAUNCH_OK("hupr_k_lamb_stage1");
+    return HUPR_OK;
+}
+
+// seg_stats: 3 floats per segment, |p| of every segment, then |u|, then r
+extern "C" int hupr_lamb_ratio_f32(const double* partials, long n, const long* table_host, long words, const long* table_dev,
+                                   const float* guard, float* seg_stats, hupr_stream_t stream) {
+    HUPR_REQUIRE(partials && table_host && table_dev && seg_stats && n > 0, "hupr_lamb_ratio_f32: bad argument (null pointer or n <= 0)");
+    HUPR_REQUIRE((reinterpret_cast<uintptr_t>(partials) & 7) == 0, "hupr_lamb_ratio_f32: partials must be 8-byte aligned");
+    HUPR_LAMB_TABLE("hupr_lamb_ratio_f32");
+    HUPR_LAUNCH(hupr_k_lamb_ratio, dim3((unsigned)table_host[0]), dim3(kThreads), 0, as_stream(stream), partials, table_dev, guard,
+                seg_stats);
+    HUPR_LAUNCH_OK("hupr_k_lamb_ratio");
+    return HUPR_OK;
+}
+
+extern "C" int hupr_lamb_stage2_f32(float* p, const float* exp_avg, const float* exp_avg_sq, long n, const long* table_host,
+                                    long words, const long* table_dev, const float* dev_state, const float* guard, double beta1,
+                                    double beta2, float eps, float weight_decay, const float* seg_stats, hupr_stream_t stream) {
+    HUPR_REQUIRE(p && exp_avg && exp_avg_sq && table_host && table_dev && dev_state && seg_stats && n > 0,
+                 "hupr_lamb_stage2_f32: bad argument (null pointer or n <= 0)");
+    HUPR_REQUIRE(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0, "hupr_lamb_stage2_f32: betas must be inside [0, 1)");
+    HUPR_LAMB_TABLE("hupr_lamb_stage2_f32");
+    HUPR_LAUNCH(hupr_k_lamb_stage2, dim3((unsigned)table_host[1]), dim3(kThreads), 0, as_stream(stream), p, exp_avg, exp_avg_sq,
+                table_dev, dev_state, guard, beta1, beta2, eps, weight_decay, seg_stats);
+    HUPR_LAUNCH_OK("hupr_k_lamb_stage2");
     return HUPR_OK;
 }

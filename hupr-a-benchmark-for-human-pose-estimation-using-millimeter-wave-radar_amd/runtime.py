@@ -178,6 +178,12 @@ SIGNATURES = {
     "hupr_ema_tick_f32": (c_int, [c_void_p, c_float, c_void_p, c_void_p]),
     "hupr_ema_update_f32": (c_int, [c_void_p, c_void_p, c_long, c_void_p, c_void_p]),
     "hupr_swap_f32": (c_int, [c_void_p, c_void_p, c_long, c_void_p]),
+    # LAMB over the flat buckets (csrc/optim.hip): chunk table in host and device memory, three launches per bucket
+    "hupr_lamb_chunk": (c_int, []),
+    "hupr_lamb_table_check": (c_int, [c_void_p, c_long, c_long]),
+    "hupr_lamb_stage1_f32": (c_int, [c_void_p] * 4 + [c_long, c_void_p, c_long] + [c_void_p] * 3 + [ctypes.c_double] * 2 + [c_float] * 3 + [c_void_p] * 2),
+    "hupr_lamb_ratio_f32": (c_int, [c_void_p, c_long, c_void_p, c_long] + [c_void_p] * 4),
+    "hupr_lamb_stage2_f32": (c_int, [c_void_p] * 3 + [c_long, c_void_p, c_long] + [c_void_p] * 3 + [ctypes.c_double] * 2 + [c_float] * 2 + [c_void_p] * 2),
     # bf16-activation variants (same argument lists as their fp32-activation counterparts)
     "hupr_conv3x3_halo_bf16act": (c_int, [c_void_p] * 5 + [c_int] * 10 + [c_void_p]),
     "hupr_conv3x3_halo_splitk_ws_bytes": (c_size_t, [c_int] * 7),

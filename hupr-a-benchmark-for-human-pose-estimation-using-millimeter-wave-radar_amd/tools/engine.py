@@ -1,5 +1,5 @@
 """Training/inference engine shared by the Runner and bench.py: HuPRNet + LossComputer +
-flat gradient buckets (+ RCCL all-reduce when world_size > 1) + fused Adam or SGD, optionally fed by the
+flat gradient buckets (+ RCCL all-reduce when world_size > 1) + fused Adam, SGD or LAMB, optionally fed by the
 on-GPU FFT loader (int16 ADC cubes -> normalised network input, config "C3" of BASELINE.json)."""
 
 import contextlib
@@ -31,6 +31,8 @@ class TrainEngine:
         self.optimizer = make_optimizer(cfg, self.model.parameters(), lr if lr is not None else cfg.TRAINING.lr)
         self.optimizer.attach_flat_buckets(self.buckets.flat_pairs(), self.buckets.layout())
         self.optimizer.grad_scale = 1.0 / self.world_size
+        # (TRAINING.optimizer: lamb takes its norms per parameter tensor over these buckets.  Data parallel needs no exchange for
+        # them: the parameters are identical on every rank and the gradients all-reduced, so every rank computes the same ratios)
         # TRAINING.gradClip: clip the global gradient norm / skip a non-finite step, decided on the device between finish() and
         # the update (so the norm is that of the mean gradient over ranks and micro-batches, identical on every rank)
         if self.optimizer.grad_clip is not None:
@@ -184,6 +186,18 @@ class TrainEngine:
         device: per epoch, not per step.  A skipped step leaves parameters, optimiser state and step count as they were; the
         BatchNorm running statistics of its forward pass have moved all the same (as under torch's GradScaler)."""
         return self.optimizer.guard_stats()
+
+    def lamb_stats(self):
+        """With ``TRAINING.optimizer: lamb``: {parameter name: (|p|, |u|, r)} of the last optimiser step that was not skipped —
+        the parameter's norm before that step, the norm of its update direction and its trust ratio (1 for every parameter with
+        ``ndim <= 1``; all zeros before the first step); None with another optimiser.  Synchronises the device: per epoch, not
+        per step."""
+        stats = getattr(self.optimizer, "lamb_stats", lambda: None)()
+        if stats is None:
+            return None
+        names = {id(p): name for name, p in self.model.named_parameters()}
+        return {names[id(p)]: (float(pn[i]), float(un[i]), float(r[i]))
+                for entries, (pn, un, r) in zip(self.buckets.layout(), stats) for i, (p, _, _) in enumerate(entries)}
 
     def mining_stats(self):
         """With ``TRAINING.ohkm`` or ``TRAINING.jointWeights`` set: {"k": joints kept per head and sample, "counts": (2, K) int64

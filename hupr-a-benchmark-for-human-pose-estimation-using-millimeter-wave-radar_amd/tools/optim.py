@@ -1,4 +1,4 @@
-"""Adam and SGD with momentum, both with coupled L2 weight decay, on the gfx950 fused kernels.
+"""Adam and SGD with momentum, both with coupled L2 weight decay, and LAMB, on the gfx950 fused kernels.
 
 The reference builds one of the two from ``TRAINING.optimizer`` (tools/base.py:44-47): ``optim.SGD(lr, momentum=0.9,
 weight_decay=1e-4)`` or ``optim.Adam(lr, betas=(0.9, 0.999), weight_decay=1e-4)`` on every parameter (``make_optimizer``).
@@ -9,6 +9,9 @@ parameters were flattened by ``tools.distributed``.
 ``TRAINING.gradClip`` (absent from the reference's YAML; ``-1`` = off) puts the gradient guard in front of the flat-bucket step:
 global-norm clipping (``torch.nn.utils.clip_grad_norm_``'s rule) and the skip of a step whose gradients are not finite, both
 decided on the device (``enable_grad_guard``).
+
+``TRAINING.optimizer: lamb`` (new, no reference counterpart) is the large-batch optimiser: Adam's direction rescaled per parameter
+tensor by the trust ratio (``FusedLAMB``), with ``TRAINING.lambWeightDecay`` (absent = 0.01) as its decoupled decay.
 """
 import torch
 
@@ -290,6 +293,134 @@ class FusedSGD(_FlatBucketOptimizer):
         self._launch_bucket(L, s, "host", p, g, st, group, first)
 
 
+def lamb_chunk_table(segments, chunk):
+    """The chunk table of one flat bucket for the LAMB kernels (``include/hupr.h`` (a13)), as a flat list of ints.
+    ``segments``: [(start, length, adapted)] tiling the bucket in order; ``chunk``: elements per chunk (``hupr_lamb_chunk()``).
+    Layout: ``[S, K, chunk, n]``, then per segment ``start, length, first chunk, chunk count, adapted``, then per chunk ``segment,
+    start relative to the segment``.  Every segment is cut from its own start, so no chunk spans two segments, the chunks of a
+    segment are consecutive, and moving a segment inside its bucket changes nothing but its ``start``."""
+    chunk = int(chunk)
+    if chunk <= 0:
+        raise ValueError("lamb_chunk_table: chunk must be positive, got %r" % (chunk,))
+    segs, chunks, at = [], [], 0
+    for s, (start, length, adapted) in enumerate(segments):
+        start, length = int(start), int(length)
+        if start != at or length <= 0:
+            raise ValueError("lamb_chunk_table: segment %d = (start %d, length %d) does not continue the bucket at %d"
+                             % (s, start, length, at))
+        count = -(-length // chunk)
+        segs += [start, length, len(chunks) // 2, count, 1 if adapted else 0]
+        for k in range(count):
+            chunks += [s, k * chunk]
+        at += length
+    if not segs:
+        raise ValueError("lamb_chunk_table: no segment")
+    return [len(segs) // 5, len(chunks) // 2, chunk, at] + segs + chunks
+
+
+class FusedLAMB(_FlatBucketOptimizer):
+    """LAMB (You et al., "Large Batch Optimization for Deep Learning", 2020) with the update rule of apex's ``FusedLAMB``, over the
+    flat buckets only.  Per parameter tensor, ``k`` the 1-based step count and ``g' = g * grad_scale * coef`` (``coef``: the
+    gradient guard's clipping coefficient, 1 without the guard)::
+
+        m <- b1 m + (1 - b1) g'          v <- b2 v + (1 - b2) g'^2
+        d = (m / (1 - b1^k)) / (sqrt(v) / sqrt(1 - b2^k) + eps)
+        p.ndim > 1 :   u = d + wd p ;   r = |p| / |u| if both norms > 0 else 1
+        p.ndim <= 1:   u = d ;          r = 1           (biases, BatchNorm, PReLU: no decay, no adaptation)
+        p <- p - lr r u
+
+    No clamp on ``r`` and no function other than the identity on ``|p|``; ``|p|`` is taken before the update.  An adapted tensor
+    whose gradient is zero at step 1 has ``u = wd p`` and therefore ``r = 1 / wd``: it shrinks by the factor ``1 - lr`` on that
+    step.  That is the rule, not a special case.  Three launches per bucket (``csrc/optim.hip``): the new moments and the
+    squares per chunk, the norms and ratios per tensor, the update.  ``{lr, step}`` live in device memory from
+    ``attach_flat_buckets`` on, so an eager step and a step replayed from a hipGraph are the same launches and the same bits.
+    State per parameter in ``state_dict()``: Adam's ``{step, exp_avg, exp_avg_sq}``; ``param_groups[0]`` carries the marker
+    ``trust_ratio: True``, by which ``load_state_dict`` tells a LAMB checkpoint from an Adam one."""
+    _state_keys = ("exp_avg", "exp_avg_sq")
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.01):
+        if lr < 0.0 or not weight_decay >= 0.0 or weight_decay == float("inf"):
+            raise ValueError("FusedLAMB: invalid lr %r or weight_decay %r" % (lr, weight_decay))
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, trust_ratio=True))
+
+    def attach_flat_buckets(self, buckets, layout=None):
+        if layout is None:
+            raise RuntimeError("FusedLAMB needs the bucket layout (GradientBuckets.layout()): its trust ratios are per parameter "
+                               "tensor")
+        super().attach_flat_buckets(buckets, layout)
+        chunk = rt.lib().hupr_lamb_chunk()
+        for (p, _), entries, st in zip(buckets, layout, self._flat_state):
+            table = torch.tensor(lamb_chunk_table([(off, n, q.ndim > 1) for q, off, n in entries], chunk), dtype=torch.int64)
+            rt.check(rt.lib().hupr_lamb_table_check(table.data_ptr(), table.numel(), p.numel()))
+            nseg, nchunk = int(table[0]), int(table[1])
+            # beside the bucket's state, not a state key: the table in host and device memory, the fp64 pair per chunk and |p|, |u|, r
+            # per parameter tensor
+            st["lamb"] = dict(host=table, dev=table.to(p.device), words=table.numel(), segments=nseg,
+                              partials=torch.zeros(2 * nchunk, dtype=torch.float64, device=p.device),
+                              stats=torch.zeros(3 * nseg, dtype=torch.float32, device=p.device))
+        self.use_device_state()      # always: the kernels have no form with host arguments
+
+    def _param_entry(self, step, slices):
+        return {"step": torch.tensor(float(step)), **slices}      # Adam's entry: {step, exp_avg, exp_avg_sq}
+
+    def _entry_step(self, entry):
+        return int(round(float(entry["step"])))
+
+    def load_state_dict(self, state_dict):
+        for entry in state_dict["state"].values():
+            if entry and "momentum_buffer" in entry:
+                raise ValueError("FusedLAMB cannot load this optimizer state: it was written by SGD (torch.optim.SGD or FusedSGD; "
+                                 "entries hold %s); TRAINING.optimizer must match the checkpoint's optimiser" % sorted(entry))
+            if entry and not all(k in entry for k in ("step",) + self._state_keys):
+                raise ValueError("FusedLAMB cannot load this optimizer state: entries hold %s, not 'step', 'exp_avg', 'exp_avg_sq'"
+                                 % sorted(entry))
+        for group in state_dict["param_groups"]:
+            if group.get("trust_ratio") is not True:
+                raise ValueError("FusedLAMB cannot load this optimizer state: it was written by Adam (torch.optim.Adam or "
+                                 "FusedAdam; its param_groups lack 'trust_ratio').  The state keys are the same, but Adam's eps "
+                                 "and coupled weight_decay would replace LAMB's; TRAINING.optimizer must match the checkpoint's "
+                                 "optimiser")
+        super().load_state_dict(state_dict)
+
+    def _launch_bucket(self, L, s, form, p, g, st, group):
+        t = st["lamb"]
+        b1, b2 = group["betas"]
+        n = p.numel()
+        table = (t["host"].data_ptr(), t["words"], rt.ptr(t["dev"]))
+        state, guard = rt.ptr(self._dev_state), rt.ptr(self._guard) if form == "guard" else None
+        hyper = (b1, b2, group["eps"], group["weight_decay"])
+        m, v, partials, stats = rt.ptr(st["exp_avg"]), rt.ptr(st["exp_avg_sq"]), rt.ptr(t["partials"]), rt.ptr(t["stats"])
+        rt.check(L.hupr_lamb_stage1_f32(rt.ptr(p), rt.ptr(g), m, v, n, *table, state, guard, *hyper, self.grad_scale, partials, s))
+        rt.check(L.hupr_lamb_ratio_f32(partials, n, *table, guard, stats, s))
+        rt.check(L.hupr_lamb_stage2_f32(rt.ptr(p), m, v, n, *table, state, guard, *hyper, stats, s))
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        if self._flat is None:
+            raise RuntimeError("FusedLAMB.step needs flat gradient buckets (attach_flat_buckets first): its trust ratios are taken "
+                               "per parameter tensor over the buckets")
+        if not torch.cuda.is_current_stream_capturing():
+            self.sync_lr()                   # a changed param_groups lr (Runner.adjustLR); a captured step reads it on replay
+        return super().step(closure)
+
+    def lamb_stats(self):
+        """Per bucket ``(|p|, |u|, r)``, one float tensor each with one value per parameter tensor in ``layout()`` order, as the
+        last step that was not skipped left them (zeros before the first).  Reads device memory, so it synchronises."""
+        if self._flat is None:
+            return None
+        return [tuple(st["lamb"]["stats"].view(3, st["lamb"]["segments"]).cpu()) for st in self._flat_state]
+
+
+def lamb_weight_decay_setting(cfg):
+    """``TRAINING.lambWeightDecay`` -> None (absent) or the decay as a float (a finite number >= 0).  Anything else is refused."""
+    if not hasattr(cfg.TRAINING, "lambWeightDecay"):
+        return None
+    v = cfg.TRAINING.lambWeightDecay
+    if isinstance(v, (int, float)) and not isinstance(v, bool) and 0 <= v < float("inf"):      # False for NaN
+        return float(v)
+    raise ValueError("TRAINING.lambWeightDecay must be a finite number >= 0 (absent = 0.01), got %r" % (v,))
+
+
 def grad_clip_setting(cfg):
     """``TRAINING.gradClip`` -> None (absent or -1: off, the YAML's own "-1 = off" idiom) or the max norm as a float (``.inf``:
     guard only, no clipping).  Anything else (0, another negative number, NaN, not a number) is refused."""
@@ -303,16 +434,24 @@ def grad_clip_setting(cfg):
 
 
 def make_optimizer(cfg, params, lr):
-    """The optimiser ``TRAINING.optimizer`` selects, built as the reference builds it (tools/base.py:44-47).  The reference
+    """The optimiser ``TRAINING.optimizer`` selects: ``sgd`` and ``adam`` built as the reference builds them (tools/base.py:44-47),
+    ``lamb`` with ``TRAINING.lambWeightDecay`` (absent = 0.01; set together with another optimiser it is an error).  The reference
     leaves ``self.optimizer`` unset for any other name and fails later; this raises here.  ``TRAINING.gradClip`` is read into
     ``optimizer.grad_clip``; the caller enables the guard once the flat buckets are attached (``TrainEngine``)."""
     name = cfg.TRAINING.optimizer
     clip = grad_clip_setting(cfg)
-    if name == "adam":
+    wd = lamb_weight_decay_setting(cfg)
+    if wd is not None and name in ("adam", "sgd"):
+        raise ValueError("TRAINING.lambWeightDecay is set but TRAINING.optimizer is %r: the key belongs to 'lamb' (%r decays by "
+                         "1e-4, coupled, as the reference does)" % (name, name))
+    if name == "lamb":
+        opt = FusedLAMB(params, lr=lr, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.01 if wd is None else wd)
+    elif name == "adam":
         opt = FusedAdam(params, lr=lr, betas=(0.9, 0.999), weight_decay=1e-4)
     elif name == "sgd":
         opt = FusedSGD(params, lr=lr, momentum=0.9, weight_decay=1e-4)
     else:
-        raise ValueError("TRAINING.optimizer must be 'sgd' or 'adam' (tools/base.py:44-47), got %r" % (name,))
+        raise ValueError("TRAINING.optimizer must be 'sgd' or 'adam' (tools/base.py:44-47) or 'lamb' (large batches), got %r"
+                         % (name,))
     opt.grad_clip = clip
     return opt

@@ -44,6 +44,16 @@ def loss_labels(batch, mode):
     return batch["jointsFloat"].float()
 
 
+def trust_ratio_line(epoch, stats, params):
+    """TRAINING.optimizer: lamb — the epoch's line: minimum, median and maximum trust ratio of the last step over the adapted
+    tensors (``ndim > 1``; the others have ratio 1 by rule) and the names of the two extremes."""
+    r = sorted((v[2], name) for name, v in stats.items() if params[name].ndim > 1)
+    if not r:
+        return "==========>Trust ratios in epoch %d: no adapted tensor" % epoch
+    return "==========>Trust ratios in epoch %d (%d adapted tensors): min %.4g (%s)  median %.4g  max %.4g (%s)" % (
+        epoch, len(r), r[0][0], r[0][1], float(np.median([x for x, _ in r])), r[-1][0], r[-1][1])
+
+
 class Runner(BaseRunner):
     def __init__(self, args, cfg):
         super().__init__(args, cfg)
@@ -177,6 +187,9 @@ class Runner(BaseRunner):
                 print("==========>Mined joints in epoch %d (PRGCN head, %d of %d kept, %d samples): %s" % (
                     epoch, mined["k"], self.numKeypoints, n,
                     "  ".join("%s: %.3f" % (name, c / max(n, 1)) for name, c in zip(self.cfg.DATASET.idxToJoints, kept))))
+            lamb = self.engine.lamb_stats()
+            if lamb is not None and self.rank == 0:
+                print(trust_ratio_line(epoch, lamb, dict(self.model.named_parameters())))
             with self.engine.averaged_weights() if averaged else contextlib.nullcontext():
                 accAP = self.eval(visualization=False, epoch=epoch)
             if self.rank == 0:

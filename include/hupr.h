@@ -601,6 +601,39 @@ int hupr_ema_update_f32(float* ema, const float* p, long n, const float* ema_sta
 /* a[0 .. n) <-> b[0 .. n), every bit pattern kept.  Alignment handled as in hupr_ema_update_f32; overlapping ranges are refused. */
 int hupr_swap_f32(float* a, float* b, long n, hupr_stream_t stream);
 
+/* (a13) LAMB: Adam's direction rescaled per parameter tensor by the trust ratio |p| / |u| (csrc/optim.hip; TRAINING.optimizer:
+ * lamb).  New, no reference counterpart: the reference's choice is SGD or Adam, `tools/base.py:44-47`.  Per tensor, k = dev_state[1],
+ * g' = g * gscale * (guard ? guard[0] : 1) (one fp32 product), bias corrections as hupr_adam_step_dev_f32 forms them:
+ *   m <- b1 m + (1 - b1) g',  v <- b2 v + (1 - b2) g'^2,  d = (m / (1 - b1^k)) / (sqrt(v) / sqrt(1 - b2^k) + eps)
+ *   adapted tensor: u = d + wd p, r = |p| / |u| if both norms > 0 else 1;  other tensor: u = d, r = 1;  p <- p - lr r u
+ * No clamp on r; |p| is taken before the update.  The parameter tensors are the segments of a flat bucket, described by a chunk
+ * table of int64 words that the caller builds once per bucket and keeps in host AND device memory:
+ *   {segments S, chunks K, hupr_lamb_chunk(), n},  S x {start, length, first chunk, chunk count, adapted (0 | 1)},
+ *   K x {segment, start relative to the segment}
+ * The segments tile [0, n) in order; a segment is cut from its own start into ceil(length / hupr_lamb_chunk()) chunks, consecutive
+ * in the table, so no chunk spans two tensors.  Every entry checks the host copy in front of its launch and the kernels read the
+ * device copy.  Per optimiser step, bucket and stream: stage1, ratio, stage2.  {lr, step} are always read from dev_state (the 2
+ * floats of hupr_adam_step_dev_f32); guard is null or the 4 floats of hupr_grad_guard_f32, and guard[3] == 0 makes all three
+ * launches return before their first store.  The betas are doubles: 1 - beta is rounded to fp32 once (1.f - 0.999f is 1.3e-5 away
+ * from 0.001).  fp32 data, fp64 norms, no atomics; which thread adds which element depends on the
+ * segment lengths only, never on the addresses: the bits repeat from run to run and do not change when a bucket moves by a few
+ * floats.  All of it is stream-ordered and capturable in a hipGraph. */
+/* elements per chunk */
+int hupr_lamb_chunk(void);
+/* host only, launches nothing: 0 when table_host[0 .. words) is such a table over [0, n), -1 with a message otherwise */
+int hupr_lamb_table_check(const long* table_host, long words, long n);
+/* new exp_avg, exp_avg_sq over [0, n); partials[2c], partials[2c + 1] <- {sum p^2, sum u^2} of chunk c in fp64 (8-byte aligned) */
+int hupr_lamb_stage1_f32(float* p, const float* g, float* exp_avg, float* exp_avg_sq, long n, const long* table_host, long words,
+                         const long* table_dev, const float* dev_state, const float* guard, double beta1, double beta2, float eps,
+                         float weight_decay, float gscale, double* partials, hupr_stream_t stream);
+/* per segment s the pairs of its chunks added in table order: seg_stats[s] <- |p|, seg_stats[S + s] <- |u|, seg_stats[2 S + s] <- r */
+int hupr_lamb_ratio_f32(const double* partials, long n, const long* table_host, long words, const long* table_dev,
+                        const float* guard, float* seg_stats, hupr_stream_t stream);
+/* u recomputed from p and the new exp_avg, exp_avg_sq (stage 1's bits); p <- p - (lr * seg_stats[2 S + s]) * u, one fused multiply-add */
+int hupr_lamb_stage2_f32(float* p, const float* exp_avg, const float* exp_avg_sq, long n, const long* table_host, long words,
+                         const long* table_dev, const float* dev_state, const float* guard, double beta1, double beta2, float eps,
+                         float weight_decay, const float* seg_stats, hupr_stream_t stream);
+
 /* ---- bf16-activation variants ("bf16act") -------------------------------------------------------------
  * Same operators with the ACTIVATION tensors (x, y, dy, dx, residual) stored as bf16 in HBM; parameters,
  * statistics, weight gradients and all arithmetic stay fp32 (fp32 accumulate on the matrix pipe).  The
