@@ -1720,6 +1720,75 @@ class MinedBCEFn(torch.autograd.Function):
         return dp1, dp2, None, None, None, None, None, None
 
 
+@_math_scoped
+class CoordLossFn(torch.autograd.Function):
+    """Integral (soft-arg-max) coordinate loss on both heads (csrc/coord_loss.hip; the rule is stated beside
+    hupr_coord_loss_fwd_f32 in include/hupr.h): an L1 on the offset of each heat-map's mass centroid from its joint, in heat-map
+    pixels.  ``CoordLossFn.apply(p1, p2, joints, stride, snap, joint_w, a0, a1, acc)`` -> (coord_loss, c_heads): coord_loss =
+    a0 C_0 + a1 C_1, c_heads the detached (C_0, C_1); two launches forward, one backward.  p1, p2: fp32 GPU tensors of one shape
+    (B, K, H, H); ``joints``: (B, K, 2) image pixels of any real dtype on that device; ``stride``: image pixels per heat-map pixel;
+    ``snap``: the joints' target is the whole heat-map pixel ``gaussian_targets`` centres its patch on; ``joint_w``: None or K fp32
+    weights on the device; ``acc``: None or 3 fp64 on the device, which accumulate (C_0, C_1, 1) per call.  The damping of the
+    rule is ``CoordLossFn.eps``.  ``CoordLossFn.last_residual`` is the (2, B, K, 2) residuals of the latest forward, detached.  No
+    gradient flows to the joints.  Anything else raises: there is no fallback."""
+
+    eps = 1.0
+    last_residual = None
+
+    @staticmethod
+    def forward(ctx, p1, p2, joints, stride, snap, joint_w, a0, a1, acc):
+        for name, x in (("p1", p1), ("p2", p2)):
+            if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float32:
+                raise ValueError("CoordLossFn: %s must be an fp32 GPU tensor, got %s" % (
+                    name, "%s on %s" % (x.dtype, x.device) if isinstance(x, torch.Tensor) else type(x).__name__))
+        if p1.shape != p2.shape or p1.device != p2.device or p1.dim() != 4 or p1.shape[2] != p1.shape[3] or p1.numel() == 0:
+            raise ValueError("CoordLossFn: p1 and p2 must share one shape (B, K, H, H) and one device, got %s, %s" % (
+                tuple(p1.shape), tuple(p2.shape)))
+        B, K, H = p1.shape[0], p1.shape[1], p1.shape[2]
+        if K > 64 or H > 4096:
+            raise ValueError("CoordLossFn: K <= 64 and H <= 4096, got K = %d, H = %d" % (K, H))
+        if not isinstance(joints, torch.Tensor) or joints.device != p1.device or tuple(joints.shape) != (B, K, 2) \
+                or joints.dtype == torch.bool or joints.is_complex():
+            raise ValueError("CoordLossFn: joints must be (%d, %d, 2) of a real dtype on %s, got %s" % (
+                B, K, p1.device, "%s %s on %s" % (tuple(joints.shape), joints.dtype, joints.device)
+                if isinstance(joints, torch.Tensor) else type(joints).__name__))
+        if isinstance(stride, bool) or not isinstance(stride, (int, float)) or not (0 < stride < float("inf")):
+            raise ValueError("CoordLossFn: stride must be a positive finite number, got %r" % (stride,))
+        if joint_w is not None and not (isinstance(joint_w, torch.Tensor) and joint_w.device == p1.device and joint_w.is_contiguous()
+                                        and joint_w.dtype == torch.float32 and tuple(joint_w.shape) == (K,)):
+            raise ValueError("CoordLossFn: joint_w must be None or %d contiguous fp32 weights on %s" % (K, p1.device))
+        if acc is not None and not (isinstance(acc, torch.Tensor) and acc.device == p1.device and acc.is_contiguous()
+                                    and acc.dtype == torch.float64 and tuple(acc.shape) == (3,)):
+            raise ValueError("CoordLossFn: acc must be None or 3 contiguous fp64 on %s" % (p1.device,))
+        p1, p2, joints = _c(p1), _c(p2), _c(joints.to(torch.float32))
+        out = torch.empty(3, dtype=torch.float32, device=p1.device)
+        resid = torch.empty((2, B, K, 2), dtype=torch.float32, device=p1.device)
+        scale = torch.empty((2, B, K), dtype=torch.float32, device=p1.device)
+        rt.check(rt.lib().hupr_coord_loss_fwd_f32(rt.ptr(p1), rt.ptr(p2), rt.ptr(joints), B, K, H, float(stride), int(bool(snap)),
+                                                  rt.ptr(joint_w), float(CoordLossFn.eps), float(a0), float(a1), rt.ptr(out),
+                                                  rt.ptr(resid), rt.ptr(scale), rt.ptr(acc), rt.stream()))
+        ctx.save_for_backward(resid, scale, joints)
+        ctx.args = (B, K, H, float(stride), int(bool(snap)), float(a0), float(a1))
+        ctx.set_materialize_grads(False)
+        CoordLossFn.last_residual = resid
+        c_heads = out[1:]
+        ctx.mark_non_differentiable(c_heads)
+        return out[0], c_heads
+
+    @staticmethod
+    def backward(ctx, g, _g_heads):
+        resid, scale, joints = ctx.saved_tensors
+        B, K, H, stride, snap, a0, a1 = ctx.args
+        if g is None:
+            g = torch.zeros(1, dtype=torch.float32, device=resid.device)
+        dp1 = torch.empty((B, K, H, H), dtype=torch.float32, device=resid.device)
+        dp2 = torch.empty_like(dp1)
+        g = _c(g.reshape(1).to(torch.float32))
+        rt.check(rt.lib().hupr_coord_loss_bwd_f32(rt.ptr(resid), rt.ptr(scale), rt.ptr(joints), rt.ptr(g), B, K, H, stride, snap, a0, a1,
+                                                  rt.ptr(dp1), rt.ptr(dp2), rt.stream()))
+        return dp1, dp2, None, None, None, None, None, None, None
+
+
 _PATCH_CACHE = {}
 
 

@@ -52,6 +52,19 @@ def joint_weights_setting(cfg):
                      "got %r" % (K, v))
 
 
+def coord_loss_setting(cfg):
+    """``TRAINING.coordLoss`` (not a key of the reference's YAML) -> None (absent or -1: off) or the weight lambda, a finite number
+    > 0, of the integral coordinate loss that computeLoss adds to the heat-map loss (``functional.CoordLossFn``).  Anything else (0, a
+    negative, nan, inf, a bool, a string, a list) raises here, where the config is read."""
+    v = getattr(getattr(cfg, "TRAINING", None), "coordLoss", -1)
+    if isinstance(v, (int, float)) and not isinstance(v, bool):
+        if v == -1:
+            return None
+        if math.isfinite(v) and v > 0:
+            return float(v)
+    raise ValueError("TRAINING.coordLoss must be -1 (off) or a finite weight > 0, got %r" % (v,))
+
+
 class LossComputer():
     def __init__(self, cfg, device):
         self.device = device
@@ -73,6 +86,13 @@ class LossComputer():
         self._joint_w = torch.tensor(self.jointWeights, dtype=torch.float32, device=device) if self.jointWeights is not None else None
         self.mining_counts = torch.zeros((2, self.numKeypoints), dtype=torch.int64, device=device) if self.mined else None
         self.plane_loss = None          # the last mined loss's (2, B, K) unweighted plane losses, on the device
+        # TRAINING.coordLoss: computeLoss adds lambda times the integral coordinate loss of both heads (csrc/coord_loss.hip); its
+        # accumulator {sum C_0, sum C_1, steps} lives on the device from the start, as the selection counters do
+        self.coordLoss = coord_loss_setting(cfg)
+        self.coord_acc = torch.zeros(3, dtype=torch.float64, device=device) if self.coordLoss is not None else None
+        self.coord_residual = None      # the last coordinate loss's (2, B, K, 2) residuals in heat-map pixels, on the device
+        if self.coordLoss is not None:
+            self.computeLoss = self._computeLossWithCoord       # without the key computeLoss stays the method below, untouched
         self.alpha = 0.0
         self.beta = 1.0
 
@@ -121,3 +141,18 @@ class LossComputer():
         pred2d, _ = final(preds2.detach().reshape(-1, K, H, W))
         gt2d, _ = get_max_preds(heatmaps)
         return loss, loss2, pred2d, gt2d
+
+    def _computeLossWithCoord(self, preds, gt, decode=True):
+        """computeLoss with ``TRAINING.coordLoss`` set: the same tuple, ``loss`` being the heat-map loss plus lambda times the
+        coordinate term of both heads on every valid joint, whatever the mining keeps; ``loss2`` stays the second head's BCE.  The
+        head weights are those the BCE pair just got.  The accumulator moves only where gradients are recorded, as the selection
+        counters do."""
+        loss, loss2, pred2d, gt2d = LossComputer.computeLoss(self, preds, gt, decode)
+        K, H, W = self.numKeypoints, self.height, self.width
+        w = (self.alpha, self.beta) if self.lossDecay != -1 else (1.0, 1.0)
+        coord, _ = F_.CoordLossFn.apply(preds[0].reshape(-1, K, H, W), preds[1].reshape(-1, K, H, W), gt.to(self.device),
+                                        self.imgSize / self.heatmapSize, self.targets_mode == "integer", self._joint_w,
+                                        self.coordLoss * w[0], self.coordLoss * w[1],
+                                        self.coord_acc if torch.is_grad_enabled() else None)
+        self.coord_residual = F_.CoordLossFn.last_residual
+        return loss + coord, loss2, pred2d, gt2d

@@ -160,6 +160,10 @@ SIGNATURES = {
     # the pair loss with online hard keypoint mining and per-joint weights (csrc/bce_mined.hip)
     "hupr_bce_mined_fwd_f32": (c_int, [c_void_p] * 3 + [c_long, c_int, c_long, c_int, c_void_p, c_float, c_float] + [c_void_p] * 5),
     "hupr_bce_mined_bwd_f32": (c_int, [c_void_p] * 6 + [c_float, c_float, c_void_p, c_void_p, c_long, c_int, c_long, c_void_p]),
+    # the integral coordinate loss on both heads (csrc/coord_loss.hip)
+    "hupr_coord_loss_fwd_f32": (c_int, [c_void_p] * 3 + [c_long, c_int, c_int, c_float, c_int, c_void_p, c_float, c_float, c_float]
+                                + [c_void_p] * 5),
+    "hupr_coord_loss_bwd_f32": (c_int, [c_void_p] * 4 + [c_long, c_int, c_int, c_float, c_int, c_float, c_float] + [c_void_p] * 3),
     "hupr_gaussian_targets_f32": (c_int, [c_void_p] * 3 + [c_int, c_int, c_int, c_float, c_void_p]),
     "hupr_argmax_rows_f32": (c_int, [c_void_p, c_long, c_int, c_void_p, c_void_p, c_void_p]),
     # sub-pixel Gaussian targets (csrc/targets.hip)

@@ -146,8 +146,9 @@ class TrainEngine:
         alpha/beta loss weights would be frozen at their capture-time values), ``sync_lr()`` after LR changes.
         With ``TRAINING.targets: subpixel`` the joints must be a floating tensor: the static buffer keeps their dtype (an integer
         buffer would truncate every later batch), and a conversion to fp32 is a device kernel inside the captured region.
-        The gradient guard (``TRAINING.gradClip``), the weight average (``TRAINING.emaDecay``) and the mined loss with its counters
-        (``TRAINING.ohkm``, ``TRAINING.jointWeights``) are device-side and replay with the step.
+        The gradient guard (``TRAINING.gradClip``), the weight average (``TRAINING.emaDecay``), the mined loss with its counters
+        (``TRAINING.ohkm``, ``TRAINING.jointWeights``) and the coordinate loss with its accumulator (``TRAINING.coordLoss``) are
+        device-side and replay with the step.
         The ``warmup`` eager steps are real optimisation steps."""
         self._refuse_while_swapped("capture")
         tr = self.buckets.transport
@@ -212,6 +213,20 @@ class TrainEngine:
         counts = lc.mining_counts.cpu().numpy()
         return {"k": lc.mined_k, "counts": counts, "samples": int(counts[1].sum()) // lc.mined_k,
                 "plane_loss": lc.plane_loss.cpu().numpy() if lc.plane_loss is not None else None}
+
+    def coord_stats(self):
+        """With ``TRAINING.coordLoss`` set: {"weight": lambda, "sum": (sum of C_0, sum of C_1) over the training losses so far — C_h the
+        coordinate loss of the first head and of the PRGCN head in heat-map pixels, before lambda and the head weights —, "steps": how
+        many losses those sums hold, "residual": the last loss's (2, B, K, 2) ndarray of centroid offsets from the joints (None
+        before the first; between ``capture()`` and the first replay it is the captured step's buffer, which no step has filled
+        yet)}; None otherwise.  The accumulator lives on the device and replays with a captured step; it is a diagnostic, not part
+        of a checkpoint.  Synchronises the device: per epoch, not per step."""
+        lc = self.lossComputer
+        if lc.coordLoss is None:
+            return None
+        acc = lc.coord_acc.cpu().numpy()
+        return {"weight": lc.coordLoss, "sum": (float(acc[0]), float(acc[1])), "steps": int(round(acc[2])),
+                "residual": lc.coord_residual.cpu().numpy() if lc.coord_residual is not None else None}
 
     # -- averaged weights (TRAINING.emaDecay) -----------------------------------------------------------------------------------
     def ema_stats(self):

@@ -106,7 +106,7 @@ class Runner(BaseRunner):
         written to ``<phase>_results.json`` by rank 0 and scored with the OKS evaluator against the ground truth the
         reference uses: the float joints of ``<phase>_gt.json`` (not the integer-truncated ``jointsGroup`` the loss sees by default;
         with ``TRAINING.targets: subpixel`` the loss sees the float joints too, ``loss_labels``).  When ``TRAINING.targets`` or
-        ``TEST.decode`` is ``subpixel`` one more line is printed, the mean per-joint position error in image pixels
+        ``TEST.decode`` is ``subpixel``, or ``TRAINING.coordLoss`` is set, one more line is printed, the mean per-joint position error in image pixels
         (``mean_position_error``): AP's OKS thresholds are too coarse to show a sub-pixel change.
         ``--keypoints`` prints the per-joint APs (``evaluateEach``) instead of the summary line."""
         self.logger.clear(len(self.testLoader.dataset))
@@ -147,7 +147,7 @@ class Runner(BaseRunner):
             stats = evaluate_keypoints(gts, savePreds)
             print("  ".join("%s: %.3f" % (n, s) for n, s in zip(names, stats)))
             ap = float(stats[0])
-            if "subpixel" in (self.lossComputer.targets_mode, self.lossComputer.decode):
+            if "subpixel" in (self.lossComputer.targets_mode, self.lossComputer.decode) or self.lossComputer.coordLoss is not None:
                 print("MPJPE: %.3f px (n = %d)" % mean_position_error(gts, savePreds)[::2])
         if self.world > 1:
             box = [ap]
@@ -164,6 +164,7 @@ class Runner(BaseRunner):
             loss_list = []
             guard0 = self.engine.guard_stats()
             mined0 = self.engine.mining_stats()
+            coord0 = self.engine.coord_stats()
             self.logger.clear(len(self.trainLoader.dataset))
             if hasattr(self.trainLoader.sampler, "set_epoch"):
                 self.trainLoader.sampler.set_epoch(epoch)
@@ -187,6 +188,13 @@ class Runner(BaseRunner):
                 print("==========>Mined joints in epoch %d (PRGCN head, %d of %d kept, %d samples): %s" % (
                     epoch, mined["k"], self.numKeypoints, n,
                     "  ".join("%s: %.3f" % (name, c / max(n, 1)) for name, c in zip(self.cfg.DATASET.idxToJoints, kept))))
+            if coord0 is not None and self.rank == 0:
+                # TRAINING.coordLoss: this epoch's mean of C_h, the weighted per-axis mean offset of each head's mass centroid from the joint
+                coord = self.engine.coord_stats()
+                n = coord["steps"] - coord0["steps"]
+                print("==========>Coordinate loss in epoch %d: first head %.4f  PRGCN head %.4f heat-map px (weight %g, %d steps)" % (
+                    epoch, (coord["sum"][0] - coord0["sum"][0]) / max(n, 1), (coord["sum"][1] - coord0["sum"][1]) / max(n, 1),
+                    coord["weight"], n))
             lamb = self.engine.lamb_stats()
             if lamb is not None and self.rank == 0:
                 print(trust_ratio_line(epoch, lamb, dict(self.model.named_parameters())))

@@ -519,6 +519,43 @@ int hupr_bce_mined_fwd_f32(const float* p1, const float* p2, const float* t, lon
 int hupr_bce_mined_bwd_f32(const float* p1, const float* p2, const float* t, const float* coef, const float* grad_loss,
                            const float* grad_loss2_or_null, float alpha, float beta, float* dp1, float* dp2, long B, int K, long HW,
                            hupr_stream_t stream);
+/* Integral (soft-arg-max) coordinate loss on both heads (Sun et al., "Integral Human Pose Regression", ECCV 2018; Nibali et al., DSNT),
+ * csrc/coord_loss.hip: an L1 on the offset of each plane's mass centroid from its joint, in heat-map pixels.  New, no reference
+ * counterpart.  Two launches forward, one backward, no workspace, no atomics, no scratch: every output is bit-identical from run to
+ * run, and equal planes with equal joints give equal bits.  p1, p2: float [B][K][H][H] probabilities, p[b][j][y][x]; head h = 0 is
+ * p1, h = 1 is p2.  joints_xy: float [B][K][2] = (x, y) in image pixels.  Per row (h, b, j) and axis, in fp32:
+ *   Position     a = joint / stride; with snap != 0, a = (float)(int)(a + 0.5f): the pixel hupr_gaussian_targets_f32 centres its
+ *                patch on, with the truncating cast and the guard of hupr_gaussian_targets_subpixel_f32 (decided in float
+ *                arithmetic, the cast is not executed on a NaN, an infinity or a + 0.5f outside [-2^31, 2^31): the row is invalid).
+ *   Validity     the row is valid iff both a are finite and 0 <= a <= H - 1.
+ *   Residual     S = sum p, N_x = sum p (x - a_x), N_y = sum p (y - a_y) over the plane, r = N / (S + eps): the offset of the mass
+ *                centroid from the joint, shrunk by S / (S + eps).  Relative to the joint, so eps biases nothing at the optimum
+ *                (r = 0 exactly when the centroid is on the joint), and the gradient stays bounded by about H / eps on a nearly
+ *                empty plane.  A NaN cell in a valid plane gives a NaN residual; it is not masked.
+ *   Row loss     l = w[j] (|r_x| + |r_y|) for a valid row and exactly 0 for an invalid one, whose plane is not read; w =
+ *                joint_w_or_null (K floats) or all ones when it is null.
+ *   Head loss    C_h = (1 / (2 B K)) sum_b sum_j l: a fixed denominator, invalid rows count as zeros; summed in fp64 in an order
+ *                fixed by (B, K).
+ *   Outputs      loss3 = {a0 C_0 + a1 C_1, C_0, C_1}, the two products and the sum rounded separately as in hupr_bce_pair_fwd_f32;
+ *                resid (2, B, K, 2) receives r (zeros for an invalid row); scale (2, B, K) receives w[j] / (S + eps) for a valid row
+ *                and 0 for an invalid one.
+ *   Accumulator  with acc_or_null non-null (3 doubles): acc[0] += C_0, acc[1] += C_1, acc[2] += 1.  Plain adds by one workgroup;
+ *                the caller zeroes the array once.
+ *   Backward     dp_h[b,j,y,x] = G_h scale[h,b,j] / (2 B K) * (sgn(r_x) (x - a_x - r_x) + sgn(r_y) (y - a_y - r_y)), G_0 = g a0,
+ *                G_1 = g a1, sgn(0) = 0.  It reads resid, scale, the joints and g, never the maps: a store-only kernel.  Every cell
+ *                of dp1 and dp2 is written; a row whose factor G_h scale / (2 B K) is zero is written as zeros; a NaN factor or
+ *                residual reaches every cell of its plane.  No gradient flows to the joints.
+ * Reduction shape: one 256-thread workgroup (four wave64) per plane; a thread adds its H * H / 256 cells (16 at H = 64, 64 at
+ * H = 128) in index order into fp32 partials of S, N_x, N_y; then the wave butterfly (6 additions) and the four waves through LDS in
+ * wave order.  16-byte loads and stores where H % 4 == 0 and the maps are 16-byte aligned, 4-byte ones otherwise.
+ * Both return -1 (HUPR_ERR_ARG) before any launch for a null pointer (the two _or_null ones excepted), B < 1, K outside [1, 64],
+ * H outside [1, 4096], B * K * H * H beyond the 64-bit index arithmetic, stride not finite or not positive, and the forward for eps
+ * not finite or not positive. */
+int hupr_coord_loss_fwd_f32(const float* p1, const float* p2, const float* joints_xy, long B, int K, int H, float stride, int snap,
+                            const float* joint_w_or_null, float eps, float a0, float a1, float* loss3, float* resid, float* scale,
+                            double* acc_or_null, hupr_stream_t stream);
+int hupr_coord_loss_bwd_f32(const float* resid, const float* scale, const float* joints_xy, const float* grad_loss, long B, int K, int H,
+                            float stride, int snap, float a0, float a1, float* dp1, float* dp2, hupr_stream_t stream);
 int hupr_gaussian_targets_f32(const long long* joints, const float* patch, float* t, int BK, int H, int rad,
                               float stride, hupr_stream_t stream);
 int hupr_argmax_rows_f32(const float* p, long rows, int n, int* idx, float* maxval, hupr_stream_t stream);
