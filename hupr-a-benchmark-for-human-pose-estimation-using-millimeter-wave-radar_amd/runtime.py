@@ -188,6 +188,13 @@ SIGNATURES = {
     "hupr_lamb_stage1_f32": (c_int, [c_void_p] * 4 + [c_long, c_void_p, c_long] + [c_void_p] * 3 + [ctypes.c_double] * 2 + [c_float] * 3 + [c_void_p] * 2),
     "hupr_lamb_ratio_f32": (c_int, [c_void_p, c_long, c_void_p, c_long] + [c_void_p] * 4),
     "hupr_lamb_stage2_f32": (c_int, [c_void_p] * 3 + [c_long, c_void_p, c_long] + [c_void_p] * 3 + [ctypes.c_double] * 2 + [c_float] * 2 + [c_void_p] * 2),
+    # radar augmentation and the flip-test merge (csrc/augment.hip)
+    "hupr_augment_state_bytes": (c_size_t, []),
+    "hupr_augment_plan": (c_int, [c_int, c_void_p, c_float, c_float] + [c_int] * 4 + [ctypes.c_uint, c_int, c_void_p, c_void_p, c_void_p]),
+    "hupr_adc_mirror_i16": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "hupr_augment_apply_f32": (c_int, [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p, c_int, c_void_p, ctypes.c_uint, c_int, c_void_p]),
+    "hupr_augment_joints": (c_int, [c_void_p, c_void_p, c_long, c_int, c_int, c_void_p, ctypes.POINTER(c_int), c_long, c_void_p]),
+    "hupr_flip_merge_f32": (c_int, [c_void_p] * 3 + [c_long] + [c_int] * 3 + [ctypes.POINTER(c_int), c_void_p]),
     # bf16-activation variants (same argument lists as their fp32-activation counterparts)
     "hupr_conv3x3_halo_bf16act": (c_int, [c_void_p] * 5 + [c_int] * 10 + [c_void_p]),
     "hupr_conv3x3_halo_splitk_ws_bytes": (c_size_t, [c_int] * 7),

@@ -90,6 +90,9 @@ class BaseRunner():
         if ema is not None:                  # TRAINING.emaDecay: two more keys; without it exactly the reference's four
             group["ema_state_dict"] = ema.state_dict(self.model)
             group["ema_updates"] = ema.stats()["updates"]
+        augment = getattr(getattr(self, "engine", None), "augment", None)
+        if augment is not None:              # TRAINING.aug*: the generator's counter, so a resumed run draws the plans that would have come next
+            group["augment_step"] = augment.stats()["steps"]
         return group
 
     def saveModelWeight(self, epoch, acc):
@@ -154,4 +157,8 @@ class BaseRunner():
                 ema.reset()
                 print("==========>NOTE: TRAINING.emaDecay is set but no weight average is taken from this checkpoint: the average starts "
                       "from the loaded weights at 0 updates")
+        augment = getattr(getattr(self, "engine", None), "augment", None)
+        if augment is not None and not self.args.eval and not getattr(self.args, "pretrained", False) and "augment_step" in ck:
+            augment.set_step(ck["augment_step"])
+            print("==========>Load the augmentation counter (%d plans drawn)" % ck["augment_step"])
         print("==========>Load the model weight from %s, saved at epoch %d" % (self.dir, ck["epoch"]))

@@ -11,6 +11,7 @@ import torch.distributed as dist
 from ..misc.losses import LossComputer
 from ..models import HuPRNet
 from ..preprocessing.process_iwr1843 import fft_chain_loader, fft_chain_loader_means
+from . import augment as aug
 from .distributed import GradientBuckets
 from .ema import WeightEMA, ema_decay_setting
 from .optim import make_optimizer
@@ -42,6 +43,14 @@ class TrainEngine:
         decay = ema_decay_setting(cfg)
         self.ema = WeightEMA(self.buckets.flat_pairs(), self.buckets.layout(), decay, module=self.model) if decay is not None else None
         self.G = cfg.DATASET.numGroupFrames
+        # TRAINING.augMirror / augNoise / augMaskRange / augMaskAngle: one plan per training step, drawn on the device from a counter in
+        # device memory (so a replayed step draws a fresh one); the rank is in the generator's key, so data-parallel ranks draw
+        # different plans without an exchange.  TEST.flip is read here only to refuse a bad value where the config is read
+        settings = aug.augment_settings(cfg)
+        aug.flip_setting(cfg)
+        self.augment = aug.Augmenter(cfg, settings, self.device, seed=seed, rank=dist.get_rank() if dist.is_initialized() else 0) \
+            if settings is not None else None
+        self._mirror_pairs = None
         self.fuse_elevation_mean = os.environ.get("HUPR_NO_FUSED_MEAN", "0") != "1"
         self._fft_ws = None
         self._seed = None
@@ -75,8 +84,18 @@ class TrainEngine:
         v = fft_chain_loader(adc_vert).view(B, self.G, 8, 2, 64, 64, 8)
         return h, v
 
+    def _augmented_from_adc(self, adc_hori, adc_vert, joints):
+        """The augmented training inputs of one (micro-)batch of raw cubes -> (hori, vert, joints): one plan, consumed by the ADC
+        mirror of the horizontal cube (out of place: callers reuse their cubes, and a captured step's static inputs are refilled,
+        not regenerated; the vertical cube is left as it is, tools/augment.py), by the noise and masks on both network inputs and
+        by the labels."""
+        a = self.augment
+        a.plan(adc_hori.shape[0] // self.G)
+        hori, vert = self.preprocess(a.adc(adc_hori), adc_vert)
+        return a.apply(hori, 0), a.apply(vert, 1), a.labels(joints)
+
     # -- steps ------------------------------------------------------------------------------------
-    def train_step(self, hori, vert, joints, decode=False, _last=True, _micro=1):
+    def train_step(self, hori, vert, joints, decode=False, _last=True, _micro=1, _augmented=False):
         """One forward + loss + backward (+ exchange + Adam when ``_last``).  ``decode="device"`` also runs the two
         arg-max decodes of the reference's per-iteration ``computeLoss`` (misc/losses.py:43-44) as kernels on the
         step's stream; their results stay on the device (``self.last_decode``).  ``joints`` (B,K,2) are what ``TRAINING.targets``
@@ -84,6 +103,13 @@ class TrainEngine:
         ``LossComputer.computeLoss`` as they come."""
         from .. import functional as F_
         self._refuse_while_swapped("train_step")
+        if self.augment is not None and not _augmented:
+            # already normalised inputs (stored cubes): noise and masks work on them, the mirror does not.  The engine owns neither
+            # tensor here, so the transformed inputs are new ones
+            if self.augment.mirrors:
+                raise RuntimeError(aug.MIRROR_NEEDS_ADC)
+            self.augment.plan(hori.shape[0])
+            hori, vert = self.augment.apply(hori.contiguous().clone(), 0), self.augment.apply(vert.contiguous().clone(), 1)
         self.model.train()
         self.buckets.prepare(reduce=_last)
         F_.BN_COUNTER_SINK = due = []
@@ -123,14 +149,24 @@ class TrainEngine:
         m = len(micro_batches)
         out = None
         for i, (a, b, joints) in enumerate(micro_batches):
-            h, v = self.preprocess(a, b) if from_adc else (a, b)
-            out = self.train_step(h, v, joints, decode=decode, _last=i == m - 1, _micro=m)
+            augmented = from_adc and self.augment is not None          # each micro-batch draws its own plan
+            if augmented:
+                h, v, joints = self._augmented_from_adc(a, b, joints)
+            else:
+                h, v = self.preprocess(a, b) if from_adc else (a, b)
+            out = self.train_step(h, v, joints, decode=decode, _last=i == m - 1, _micro=m, _augmented=augmented)
         return out
 
     def train_step_from_adc(self, adc_hori, adc_vert, joints, decode=False):
         if self._graph is not None:
             self._refuse_while_swapped("train_step")
             return self._replay(adc_hori, adc_vert, joints)
+        return self._step_from_adc(adc_hori, adc_vert, joints, decode)
+
+    def _step_from_adc(self, adc_hori, adc_vert, joints, decode):
+        if self.augment is not None:
+            h, v, joints = self._augmented_from_adc(adc_hori, adc_vert, joints)
+            return self.train_step(h, v, joints, decode=decode, _augmented=True)
         h, v = self.preprocess(adc_hori, adc_vert)
         return self.train_step(h, v, joints, decode=decode)
 
@@ -148,7 +184,8 @@ class TrainEngine:
         buffer would truncate every later batch), and a conversion to fp32 is a device kernel inside the captured region.
         The gradient guard (``TRAINING.gradClip``), the weight average (``TRAINING.emaDecay``), the mined loss with its counters
         (``TRAINING.ohkm``, ``TRAINING.jointWeights``) and the coordinate loss with its accumulator (``TRAINING.coordLoss``) are
-        device-side and replay with the step.
+        device-side and replay with the step; so is the augmentation (``TRAINING.aug*``): its plan is drawn by a launch from a counter in
+        device memory, so every replay draws a fresh plan.
         The ``warmup`` eager steps are real optimisation steps."""
         self._refuse_while_swapped("capture")
         tr = self.buckets.transport
@@ -168,14 +205,12 @@ class TrainEngine:
         side.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(side):
             for _ in range(warmup):
-                h, v = self.preprocess(self._g_in[0], self._g_in[1])
-                self.train_step(h, v, self._g_in[2], decode=decode)
+                self._step_from_adc(self._g_in[0], self._g_in[1], self._g_in[2], decode)
         torch.cuda.current_stream(self.device).wait_stream(side)
         torch.cuda.synchronize(self.device)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
-            h, v = self.preprocess(self._g_in[0], self._g_in[1])
-            self._g_out = self.train_step(h, v, self._g_in[2], decode=decode)
+            self._g_out = self._step_from_adc(self._g_in[0], self._g_in[1], self._g_in[2], decode)
         self._graph = g
 
     def sync_lr(self):
@@ -228,6 +263,14 @@ class TrainEngine:
         return {"weight": lc.coordLoss, "sum": (float(acc[0]), float(acc[1])), "steps": int(round(acc[2])),
                 "residual": lc.coord_residual.cpu().numpy() if lc.coord_residual is not None else None}
 
+    def augment_stats(self):
+        """With a ``TRAINING.aug*`` key set: {"steps": plans drawn so far (the generator's counter: it is what a checkpoint keeps as
+        ``augment_step``), "samples": the samples they covered, "mirrored": how many of those were mirrored, "mean_sigma": the mean
+        noise level drawn, "last_plan": the last plan's (B, 8) int32 table (tools/augment.py; between ``capture()`` and the first
+        replay it is the captured step's buffer)}; None otherwise.  The state lives on the device and replays with a captured step.
+        Synchronises the device: per epoch, not per step."""
+        return self.augment.stats() if self.augment is not None else None
+
     # -- averaged weights (TRAINING.emaDecay) -----------------------------------------------------------------------------------
     def ema_stats(self):
         """With ``TRAINING.emaDecay`` set: {"updates": updates of the average so far (skipped steps do not count), "weight": the
@@ -279,3 +322,22 @@ class TrainEngine:
     def infer(self, hori, vert):
         self.model.eval()
         return self.model(hori, vert)
+
+    @torch.no_grad()
+    def infer_from_adc(self, adc_hori, adc_vert, flip=False):
+        """Inference from raw cubes; never augmented.  ``flip``: the flip test — one forward on the input, one on the horizontal cube
+        with every frame mirrored (``hupr_adc_mirror_i16``; the same batch size, so the kernels route identically; the vertical
+        input is the same tensor, tools/augment.py), and both heads merged with the mirrored, left/right-exchanged maps of the
+        second pass (``hupr_flip_merge_f32``).  Twice the work of a plain call."""
+        hori, vert = self.preprocess(adc_hori, adc_vert)
+        preds = self.infer(hori, vert)
+        if not flip:
+            return preds
+        if self._mirror_pairs is None:
+            self._mirror_pairs = aug.mirror_pairs(self.cfg.DATASET.idxToJoints)
+        adc_m = aug.adc_mirror(adc_hori)
+        B = adc_m.shape[0] // self.G
+        hori_m = fft_chain_loader_means(adc_m).view(B, self.G, 16, 64, 64) if self.fuse_elevation_mean else \
+            fft_chain_loader(adc_m).view(B, self.G, 8, 2, 64, 64, 8)
+        preds_m = self.infer(hori_m, vert)
+        return tuple(aug.flip_merge(p, pm, self._mirror_pairs) for p, pm in zip(preds, preds_m))

@@ -18,6 +18,7 @@ from ..datasets.dataset import HuPRRawADC, SequenceGroupedSampler
 from ..misc.losses import TARGETS
 from ..misc.oks_eval import evaluate_keypoints, mean_position_error
 from ..misc.plot import plotHumanPose
+from .augment import flip_setting
 from .base import BaseRunner
 from .engine import TrainEngine
 
@@ -86,19 +87,22 @@ class Runner(BaseRunner):
         LR = cfg.TRAINING.lr if warm == -1 else cfg.TRAINING.lr / (cfg.TRAINING.warmupGrowth ** self.stepSize)
         self.engine = TrainEngine(cfg, device=torch.device("cuda", torch.cuda.current_device()), lr=LR, seed=args.seed)
         self.model, self.optimizer, self.lossComputer = self.engine.model, self.engine.optimizer, self.engine.lossComputer
+        self.flip = flip_setting(cfg)           # TEST.flip: eval() runs the flip test (raw-ADC batches only)
         for d in (self.dir, self.visDir):
             os.makedirs(d, exist_ok=True)
         if not args.eval:
             print("==========>Train set size:", len(self.trainLoader))
         print("==========>Test set size:", len(self.testLoader))
 
+    def _adc(self, batch):
+        dev = self.engine.device
+        B, G = batch["adc_hori"].shape[:2]
+        return (batch["adc_hori"].to(dev).reshape(B * G, 4, 192, 256, 2), batch["adc_vert"].to(dev).reshape(B * G, 4, 192, 256, 2))
+
     def _inputs(self, batch):
         dev = self.engine.device
         if "adc_hori" in batch:          # raw ADC cubes: FFT chain + loader glue on the GPU
-            B, G = batch["adc_hori"].shape[:2]
-            h = batch["adc_hori"].to(dev).reshape(B * G, 4, 192, 256, 2)
-            v = batch["adc_vert"].to(dev).reshape(B * G, 4, 192, 256, 2)
-            return self.engine.preprocess(h, v)
+            return self.engine.preprocess(*self._adc(batch))
         return batch["VRDAEmap_hori"].float().to(dev), batch["VRDAEmap_vert"].float().to(dev)
 
     def eval(self, visualization=True, epoch=-1):
@@ -106,15 +110,21 @@ class Runner(BaseRunner):
         written to ``<phase>_results.json`` by rank 0 and scored with the OKS evaluator against the ground truth the
         reference uses: the float joints of ``<phase>_gt.json`` (not the integer-truncated ``jointsGroup`` the loss sees by default;
         with ``TRAINING.targets: subpixel`` the loss sees the float joints too, ``loss_labels``).  When ``TRAINING.targets`` or
-        ``TEST.decode`` is ``subpixel``, or ``TRAINING.coordLoss`` is set, one more line is printed, the mean per-joint position error in image pixels
+        ``TEST.decode`` is ``subpixel``, or ``TRAINING.coordLoss`` or ``TEST.flip`` is set, one more line is printed, the mean per-joint position error in image pixels
         (``mean_position_error``): AP's OKS thresholds are too coarse to show a sub-pixel change.
         ``--keypoints`` prints the per-joint APs (``evaluateEach``) instead of the summary line."""
         self.logger.clear(len(self.testLoader.dataset))
         savePreds, gts = [], []
         for batch in self.testLoader:
             keypoints = batch["jointsGroup"]
-            hori, vert = self._inputs(batch)
-            preds = self.engine.infer(hori, vert)
+            if self.flip:
+                # TEST.flip: the mirror of this radar is a permutation of the raw cube (tools/augment.py), so stored cubes cannot take it
+                if "adc_hori" not in batch:
+                    raise RuntimeError("TEST.flip needs a dataset of raw ADC cubes ('adc_hori'); this one yields only %s" % sorted(batch))
+                preds = self.engine.infer_from_adc(*self._adc(batch), flip=True)
+            else:
+                hori, vert = self._inputs(batch)
+                preds = self.engine.infer(hori, vert)
             with torch.no_grad():
                 loss, loss2, pred2d, _ = self.lossComputer.computeLoss(preds, loss_labels(batch, self.lossComputer.targets_mode))
             self.logger.display(loss, loss2, keypoints.size(0), epoch)
@@ -147,7 +157,7 @@ class Runner(BaseRunner):
             stats = evaluate_keypoints(gts, savePreds)
             print("  ".join("%s: %.3f" % (n, s) for n, s in zip(names, stats)))
             ap = float(stats[0])
-            if "subpixel" in (self.lossComputer.targets_mode, self.lossComputer.decode) or self.lossComputer.coordLoss is not None:
+            if "subpixel" in (self.lossComputer.targets_mode, self.lossComputer.decode) or self.lossComputer.coordLoss is not None or self.flip:
                 print("MPJPE: %.3f px (n = %d)" % mean_position_error(gts, savePreds)[::2])
         if self.world > 1:
             box = [ap]
@@ -165,12 +175,18 @@ class Runner(BaseRunner):
             guard0 = self.engine.guard_stats()
             mined0 = self.engine.mining_stats()
             coord0 = self.engine.coord_stats()
+            aug0 = self.engine.augment_stats()
             self.logger.clear(len(self.trainLoader.dataset))
             if hasattr(self.trainLoader.sampler, "set_epoch"):
                 self.trainLoader.sampler.set_epoch(epoch)
             for idxBatch, batch in enumerate(self.trainLoader):
-                hori, vert = self._inputs(batch)
-                loss, loss2 = self.engine.train_step(hori, vert, loss_labels(batch, self.lossComputer.targets_mode))
+                labels = loss_labels(batch, self.lossComputer.targets_mode)
+                if aug0 is not None and "adc_hori" in batch:
+                    # TRAINING.aug*: raw cubes take the whole plan, the mirror in front of the FFT chain included
+                    loss, loss2 = self.engine.train_step_from_adc(*self._adc(batch), labels)
+                else:
+                    hori, vert = self._inputs(batch)
+                    loss, loss2 = self.engine.train_step(hori, vert, labels)
                 self.logger.display(loss, loss2, batch["jointsGroup"].size(0), epoch)
                 if idxBatch % self.cfg.TRAINING.lrDecayIter == 0:
                     self.adjustLR(epoch)
@@ -195,6 +211,13 @@ class Runner(BaseRunner):
                 print("==========>Coordinate loss in epoch %d: first head %.4f  PRGCN head %.4f heat-map px (weight %g, %d steps)" % (
                     epoch, (coord["sum"][0] - coord0["sum"][0]) / max(n, 1), (coord["sum"][1] - coord0["sum"][1]) / max(n, 1),
                     coord["weight"], n))
+            if aug0 is not None and self.rank == 0:
+                # TRAINING.aug*: what this epoch's plans drew (this rank's; the other ranks draw their own)
+                st = self.engine.augment_stats()
+                n = st["samples"] - aug0["samples"]
+                sig = st["mean_sigma"] * st["samples"] - aug0["mean_sigma"] * aug0["samples"]
+                print("==========>Augmentation in epoch %d: %d of %d samples mirrored, mean noise sigma %.4f (%d steps)" % (
+                    epoch, st["mirrored"] - aug0["mirrored"], n, sig / max(n, 1), st["steps"] - aug0["steps"]))
             lamb = self.engine.lamb_stats()
             if lamb is not None and self.rank == 0:
                 print(trust_ratio_line(epoch, lamb, dict(self.model.named_parameters())))

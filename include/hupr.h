@@ -671,6 +671,58 @@ int hupr_lamb_stage2_f32(float* p, const float* exp_avg, const float* exp_avg_sq
                          const long* table_dev, const float* dev_state, const float* guard, double beta1, double beta2, float eps,
                          float weight_decay, const float* seg_stats, hupr_stream_t stream);
 
+/* (a14) Radar augmentation on the device (csrc/augment.hip; TRAINING.augMirror / augNoise / augMaskRange / augMaskAngle, TEST.flip).
+ * New, no reference counterpart: the reference augments nothing and has no flip test.  One plan per training step, drawn by a
+ * launch from a counter in device memory, so a step replayed from a hipGraph draws a fresh plan although its launch arguments are
+ * frozen; the ADC mirror, the noise and masks and the labels consume that plan.  No atomics: every output is bit-identical from
+ * run to run.  All of it is stream-ordered and capturable in a hipGraph.
+ *
+ * Generator: Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; Weyl constants 0x9E3779B9, 0xBB67AE85), key (seed, 4 rank + domain),
+ * counter (step_lo, step_hi, b, q) for sample b.  A word w gives m = w >> 8 and u = m 2^-24 (exact in fp32); floor(u n) is formed
+ * exactly, as (m n) >> 24 in 64-bit integers.
+ *
+ * state: {counter (u64), mirrored samples (u64), samples (u64), sum of sigma (f64)} in device memory, 8-byte aligned,
+ * hupr_augment_state_bytes() bytes; the caller zeroes it (or sets the counter to resume).
+ * table: (B, 8) 32-bit words per sample: {mirror (int 0 | 1), sigma (float), range band length, range band start, azimuth band length,
+ * start of the horizontal map, azimuth band length, start of the vertical map}; a band covers [start, start + length). */
+size_t hupr_augment_state_bytes(void);
+/* Domain 0, step = state.counter.  Call q = 0 yields {mirror = u0 < p_mirror, sigma = sigma_max * u1 (one fp32 product), range length =
+ * floor(u2 (max_range + 1)), range start = floor(u3 (R - length + 1))}; call q = 1 the two azimuth bands the same way from max_angle
+ * and A.  Also flags[b] = mirror as a byte.  Then one thread adds, in sample order: counter += 1, mirrored += sum of mirror, samples
+ * += B, sum of sigma += sigma in fp64.  One launch of one workgroup.  A setting that is off is passed as 0 (p_mirror 0, sigma_max 0,
+ * a maximal band length 0).  p_mirror in [0, 1], sigma_max finite >= 0, max_range <= R / 2, max_angle <= A / 2, B in [1, 65535]. */
+int hupr_augment_plan(int B, void* state, float p_mirror, float sigma_max, int max_range, int max_angle, int R, int A, unsigned seed,
+                      int rank, void* table, unsigned char* flags, hupr_stream_t stream);
+/* The left/right mirror of the scene as a permutation of the raw cube adc[n_sf][4 rx][192 = 3 cc + tx][256][2] int16, in front of the
+ * FFT chain: out[f][rx][3 cc + tx] = adc[f][3 - rx][3 cc + 2 - tx] for the frames f with flags[f / G] != 0 (null: every frame), a
+ * plain copy for the others.  Reversing the receivers and swapping transmitters 0 and 2 reverses the 8 azimuth antennas and the
+ * elevated row on its columns 2..5; the chain's output for the permuted cube is its output at azimuth bin (62 - a) mod 64 times
+ * exp(-2 pi i 7 ((31 - a) mod 64) / 64), which no operation behind the chain's Normalize can form.  Out of place (overlap is
+ * refused); 16-byte accesses, both pointers 16-byte aligned; 786 432 B per frame each way. */
+int hupr_adc_mirror_i16(const void* adc, void* out, int n_sf, int G, const unsigned char* flags_or_null, hupr_stream_t stream);
+/* Noise and band masks on a contiguous network input x[B][P][R][A][E] (E = 1: the elevation-mean planes, E = 8: the reference-shaped
+ * tensor with P = G 8 2), y = x allowed.  sensor 0 | 1 = horizontal | vertical: generator domain 1 + sensor and that map's azimuth
+ * band.  step = state.counter - 1, the plan drawn last.  Elements 4 q .. 4 q + 3 of sample b (flat index inside the sample) take the four
+ * words {w0, w1, w2, w3} of call q: z0, z1 = r(w0) * {cospif, sinpif}(2 u(w1)), z2, z3 likewise from (w2, w3), r(w) = sqrtf(-2 ln u1)
+ * with u1 = ((w >> 8) + 0.5) 2^-24; the logarithm is logf(u1) for m < 2^23 and log1pf(-(1 - u1)) above, 1 - u1 = (2^24 - 1 - m + 0.5)
+ * 2^-24, so that its argument is exact in fp32 either way.  Precise library functions, no fast intrinsics.  y = fmaf(sigma_b, z, x);
+ * sigma_b == 0 reads no generator and keeps the element's bits.  Then every element with r inside the range band or a inside the
+ * map's azimuth band is set to 0.0f.  16-byte accesses when P R A E % 4 == 0 and x, y are 16-byte aligned, 4-byte accesses of the
+ * same quads otherwise: the same bits.  B in [1, 65535], a sample of at most 2^33 elements. */
+int hupr_augment_apply_f32(const float* x, float* y, int B, int P, int R, int A, int E, const void* table, int sensor, const void* state,
+                           unsigned seed, int rank, hupr_stream_t stream);
+/* The labels: joints (B, K, 2) = (x, y) in image pixels, int64 (is_float 0) or float32 (1), written out of place.  A sample with
+ * flags[b] != 0 (null: every sample): out[b][j] = (x_mirror - x, y) of joints[b][pair[j]]; others are copied.  x_mirror = stride (H - 1),
+ * the image column of the heat-map grid's centre doubled (252 for stride 4, H = 64): the decode maps heat-map pixel m to image 4 m, so
+ * only this axis makes the mirrored target the mirror m -> H - 1 - m of the target.  pair_host: K ints in HOST memory (K <= 64), an
+ * involution of [0, K); it travels by value with the launch.  No clamp: a coordinate beyond x_mirror goes negative. */
+int hupr_augment_joints(const void* joints, void* out, long B, int K, int is_float, const unsigned char* flags_or_null,
+                        const int* pair_host, long x_mirror, hupr_stream_t stream);
+/* The flip-test merge of a head's maps p (B, K, H, W) and the maps pm of the mirrored input:
+ * out[b][k][y][x] = 0.5f * (p[b][k][y][x] + pm[b][pair[k]][y][W - 1 - x]), the sum first.  pair_host as above.  out overlaps no input. */
+int hupr_flip_merge_f32(const float* p, const float* pm, float* out, long B, int K, int H, int W, const int* pair_host,
+                        hupr_stream_t stream);
+
 /* ---- bf16-activation variants ("bf16act") -------------------------------------------------------------
  * Same operators with the ACTIVATION tensors (x, y, dy, dx, residual) stored as bf16 in HBM; parameters,
  * statistics, weight gradients and all arithmetic stay fp32 (fp32 accumulate on the matrix pipe).  The
