@@ -84,7 +84,7 @@ __device__ __forceinline__ float wave_max(float v) {
 
 // Arg-max of one row of n floats by one 64-lane wave, first maximum wins (np.argmax): every lane returns with the same (best, bi).
 // A row without a value above -inf (all NaN, or n == 0) leaves bi = 0x7fffffff and best = -inf.  Shared by hupr_k_argmax_rows
-// (head.hip) and hupr_k_pose_decode (pose_decode.hip), so the two agree bit for bit.
+// (head.hip), hupr_k_pose_decode (pose_decode.hip) and hupr_k_pose_track (pose_track.hip), so the three agree bit for bit.
 __device__ __forceinline__ void wave_argmax_row(const float* row, int n, int lane, float& best, int& bi) {
     best = -INFINITY;
     bi = 0x7fffffff;

@@ -7,6 +7,7 @@
 //     smoothed pose and its velocity come out of the same launch — and of the same captured graph — as the decode
 // The rule is stated in full beside hupr_pose_decode_f32 in include/hupr.h.
 #include "hupr_common.h"
+#include "pose_refine.h"
 
 namespace hupr {
 
@@ -16,8 +17,6 @@ struct OneEuro {
     float rate, min_cutoff, beta, d_cutoff, min_score;
 };
 
-__device__ __forceinline__ bool finitef(float v) { return fabsf(v) < INFINITY; }      // false for NaN too
-__device__ __forceinline__ float signf(float v) { return v > 0.f ? 1.f : (v < 0.f ? -1.f : 0.f); }
 __device__ __forceinline__ float euro_alpha(float rate, float cutoff) { return 1.f / (1.f + rate / (6.283185307179586f * cutoff)); }
 
 // One wave = one row.  Nothing is shared between workgroups; the filter state of a row is read and written by lane 0 of its wave.
@@ -32,42 +31,11 @@ __global__ __launch_bounds__(64) void hupr_k_pose_decode(const float* __restrict
     int bi;
     wave_argmax_row(row, H * W, lane, best, bi);
 
-    // ---- refinement: every lane ends with the same offset --------------------------------------------------------------------
+    // ---- refinement: every lane ends with the same offset (pose_refine.h) ---------------------------------------------------------
     const int px = bi % W, py = bi / W;
     const bool positive = best > 0.f;                     // implies 0 <= bi < H * W
-    const bool interior = px > 0 && px < W - 1 && py > 0 && py < H - 1;
-    float ox = 0.f, oy = 0.f;
-    if (refine && positive && interior) {
-        // lane k < 9 holds neighbour (px + k % 3 - 1, py + k / 3 - 1); a NaN neighbour stays NaN through the log
-        float h = 1.f;
-        if (lane < 9) h = row[(long)(py + lane / 3 - 1) * W + (px + lane % 3 - 1)];
-        const float lg = (h != h) ? h : logf(fmaxf(h, 1e-10f));
-        float l[9];
-#pragma unroll
-        for (int k = 0; k < 9; ++k) l[k] = __shfl(lg, k, 64);
-        const float hxm = __shfl(h, 3, 64), hxp = __shfl(h, 5, 64), hym = __shfl(h, 1, 64), hyp = __shfl(h, 7, 64);
-        bool ok = true;
-#pragma unroll
-        for (int k = 0; k < 9; ++k) ok = ok && finitef(l[k]);
-        if (ok) {
-            const float dx = 0.5f * (l[5] - l[3]), dy = 0.5f * (l[7] - l[1]);
-            const float dxx = l[5] - 2.f * l[4] + l[3], dyy = l[7] - 2.f * l[4] + l[1];
-            const float dxy = 0.25f * (l[8] - l[6] - l[2] + l[0]);
-            const float det = dxx * dyy - dxy * dxy;
-            float tx, ty;
-            if (dxx < 0.f && det > 0.f) {
-                tx = -(dyy * dx - dxy * dy) / det;
-                ty = -(dxx * dy - dxy * dx) / det;
-            } else {
-                tx = 0.25f * signf(hxp - hxm);
-                ty = 0.25f * signf(hyp - hym);
-            }
-            if (finitef(tx) && finitef(ty)) {
-                ox = fminf(fmaxf(tx, -0.5f), 0.5f);
-                oy = fminf(fmaxf(ty, -0.5f), 0.5f);
-            }
-        }
-    }
+    float ox, oy;
+    peak_offset(row, H, W, px, py, positive, refine, lane, ox, oy);
     if (lane != 0) return;
 
     // a joint whose maximum is <= 0 decodes to (0, 0) (misc/metrics.py); with a zero offset these are the floats of

@@ -1872,3 +1872,47 @@ def pose_decode(heat, ratio, refine=True, filter_state=None, smoothing=None):
     rt.check(rt.lib().hupr_pose_decode_f32(rt.ptr(heat), rows, H, W, float(ratio), int(bool(refine)), rt.ptr(filter_state), *params,
                                            rt.ptr(idx), rt.ptr(mx), rt.ptr(raw), rt.ptr(kp), rt.ptr(vel), rt.stream()))
     return idx, mx, raw, kp, vel
+
+
+TRACK_UPDATED, TRACK_COASTED_MISSING, TRACK_COASTED_GATED, TRACK_STARTED, TRACK_LOST = range(5)      # pose_track's status codes
+_TRACK_PARAMS = ("rate_hz", "accel_psd", "meas_std", "heatmap_gain", "gate", "max_coast", "init_speed_std", "min_score", "horizon_s")
+
+
+def pose_track_state(rows, device):
+    """A zero-filled ("never seen") Kalman track state for ``rows`` (sample, joint) rows: (rows, 16) fp32 = x, y, vx, vy, the upper
+    triangle of the 4 x 4 covariance row by row, live, coast."""
+    n = int(rt.lib().hupr_pose_track_state_bytes(rows)) // 4
+    return torch.zeros((rows, n // max(rows, 1)), dtype=torch.float32, device=device)
+
+
+def pose_track(heat, ratio, refine=True, track_state=None, tracking=None):
+    """heat (..., H, W) fp32 GPU -> (idx int32 (...), maxval (...), raw keypoints (..., 2), filtered keypoints (..., 2), velocity
+    (..., 2), position covariance (..., 3) = (Pxx, Pxy, Pyy), forecast (..., 2), status int32 (...)) in one launch
+    (csrc/pose_track.hip; the rule is stated beside hupr_pose_track_f32 in include/hupr.h).  ``idx`` / ``maxval`` / raw keypoints are
+    ``pose_decode``'s bits.  ``track_state`` (``pose_track_state``, advanced in place) and ``tracking`` (an object with ``rate_hz``,
+    ``accel_psd``, ``meas_std``, ``heatmap_gain``, ``gate``, ``max_coast``, ``init_speed_std``, ``min_score``, ``horizon_s``:
+    tools.stream.PoseTracking) are both required.  One call is one frame.  Device tensors, no sync."""
+    if heat.dim() < 2:
+        raise ValueError("pose_track needs (..., H, W) heat-maps, got shape %r" % (tuple(heat.shape),))
+    if heat.dtype != torch.float32:
+        raise ValueError("pose_track needs fp32 heat-maps, got %s" % heat.dtype)
+    if track_state is None or tracking is None:
+        raise ValueError("pose_track needs its track_state and its tracking parameters")
+    heat = _c(heat)
+    lead, (H, W) = tuple(heat.shape[:-2]), heat.shape[-2:]
+    rows = int(np.prod(lead, dtype=np.int64))
+    if (not isinstance(track_state, torch.Tensor) or track_state.dtype != torch.float32 or not track_state.is_contiguous()
+            or track_state.numel() * 4 != int(rt.lib().hupr_pose_track_state_bytes(rows))):
+        raise ValueError("track_state must be the fp32 tensor pose_track_state(%d, device) returns" % rows)
+    if track_state.device != heat.device:
+        raise ValueError("track_state is on %s, the heat-maps on %s" % (track_state.device, heat.device))
+    params = tuple(int(getattr(tracking, k)) if k == "max_coast" else float(getattr(tracking, k)) for k in _TRACK_PARAMS)
+    idx = torch.empty(lead, dtype=torch.int32, device=heat.device)
+    mx = torch.empty(lead, dtype=torch.float32, device=heat.device)
+    raw, kp, vel, fc = (torch.empty(lead + (2,), dtype=torch.float32, device=heat.device) for _ in range(4))
+    cov = torch.empty(lead + (3,), dtype=torch.float32, device=heat.device)
+    status = torch.empty(lead, dtype=torch.int32, device=heat.device)
+    rt.check(rt.lib().hupr_pose_track_f32(rt.ptr(heat), rows, H, W, float(ratio), int(bool(refine)), rt.ptr(track_state), *params,
+                                          rt.ptr(idx), rt.ptr(mx), rt.ptr(raw), rt.ptr(kp), rt.ptr(vel), rt.ptr(cov), rt.ptr(fc),
+                                          rt.ptr(status), rt.stream()))
+    return idx, mx, raw, kp, vel, cov, fc, status

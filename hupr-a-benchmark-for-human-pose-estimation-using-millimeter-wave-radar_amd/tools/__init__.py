@@ -1,7 +1,8 @@
 from .optim import FusedAdam, FusedSGD  # noqa: F401
 
 _STREAM = ("PoseStream", "PoseFrame", "StreamSchedule", "stream_window_sources", "StreamError", "LookaheadError",
-           "FrameShapeError", "FrameDtypeError", "StreamEndedError", "PoseSmoothing", "DecodeError", "SmoothingError")
+           "FrameShapeError", "FrameDtypeError", "StreamEndedError", "PoseSmoothing", "DecodeError", "SmoothingError",
+           "PoseTracking", "TrackedPoseFrame", "TrackingError")
 
 
 def __getattr__(name):          # lazy: Runner pulls in datasets/models

@@ -18,10 +18,13 @@ window MNet, state advance, encoders / decoder / heads, arg-max, keypoint decode
 Decode: by default the keypoint is the arg-max pixel times imgSize / heatmapSize, as the reference decodes it.  ``decode="subpixel"``
 refines the peak to sub-pixel position and ``smooth=PoseSmoothing(rate_hz)`` runs a One-Euro filter over the keypoints, its state on
 the device; either replaces the two decode launches by one (csrc/pose_decode.hip), inside the captured graph like them.
+``track=PoseTracking(rate_hz)`` runs a constant-velocity Kalman filter per joint instead (csrc/pose_track.hip, one launch likewise):
+outliers are gated, drop-outs coast on the track's velocity, every joint carries a covariance and a forecast.
 
     python -m hupr_amd.tools.stream --config mscsa_prgcn.yaml --dir <logs name> --raw <dir with hori/ and vert/ adc_data.bin>
                                     [--lookahead N] [--math f32|bf16] [--no-graph] [--out poses.json]
                                     [--decode argmax|subpixel] [--smooth --rate FPS]
+                                    [--track --rate FPS [--predict-now] [--accel-psd Q] [--gate D2] [--max-coast N]]
 """
 import argparse
 import json
@@ -66,6 +69,11 @@ class SmoothingError(StreamError):
     """A ``PoseSmoothing`` parameter out of range, or ``smooth`` is not a ``PoseSmoothing``."""
 
 
+class TrackingError(StreamError):
+    """A ``PoseTracking`` parameter out of range, ``track`` is not a ``PoseTracking``, ``track`` together with ``smooth``, or
+    ``predict_now`` without ``track``."""
+
+
 DECODES = ("argmax", "subpixel")
 WEIGHTS = ("live", "averaged")      # which parameters of model_best.pth: as trained, or their moving average (TRAINING.emaDecay)
 
@@ -94,12 +102,60 @@ class PoseSmoothing:
         return "PoseSmoothing(%s)" % ", ".join("%s=%r" % (k, getattr(self, k)) for k in self.__slots__)
 
 
+class PoseTracking:
+    """Kalman tracker settings of a session (a constant-velocity filter per joint; the rule is stated beside hupr_pose_track_f32 in
+    include/hupr.h): ``rate_hz`` the frame rate of the stream; ``accel_psd`` (pixel^2 / s^3) the power of the white acceleration that
+    drives the process noise; the measurement noise is ``heatmap_gain`` times the spread of the heat-map around its peak plus
+    ``meas_std`` (pixel) squared; ``gate`` the largest squared Mahalanobis distance of an accepted measurement (a chi-square
+    quantile, 2 d.o.f.; the default is the 99.9 % one); ``max_coast`` the number of consecutive frames a track goes on without an
+    accepted measurement before it ends; ``init_speed_std`` (pixel / s) the velocity uncertainty of a new track; a joint whose score
+    is <= ``min_score`` has no measurement; ``horizon_s`` (s) how far ahead of the filtered pose the forecast looks.  The defaults
+    are guesses: good values for real captures are unmeasured."""
+    __slots__ = ("rate_hz", "accel_psd", "meas_std", "heatmap_gain", "gate", "max_coast", "init_speed_std", "min_score", "horizon_s")
+
+    def __init__(self, rate_hz, accel_psd=200.0, meas_std=1.0, heatmap_gain=1.0, gate=13.816, max_coast=5, init_speed_std=50.0,
+                 min_score=0.0, horizon_s=0.0):
+        vals = dict(rate_hz=rate_hz, accel_psd=accel_psd, meas_std=meas_std, heatmap_gain=heatmap_gain, gate=gate,
+                    init_speed_std=init_speed_std, min_score=min_score, horizon_s=horizon_s)
+        for k, v in vals.items():
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(v):
+                raise TrackingError("PoseTracking.%s must be a finite number, got %r" % (k, v))
+        for k in ("rate_hz", "meas_std", "gate", "init_speed_std"):
+            if not vals[k] > 0:
+                raise TrackingError("PoseTracking.%s must be positive, got %r" % (k, vals[k]))
+        for k in ("accel_psd", "heatmap_gain", "horizon_s"):
+            if vals[k] < 0:
+                raise TrackingError("PoseTracking.%s must not be negative, got %r" % (k, vals[k]))
+        if isinstance(max_coast, bool) or not isinstance(max_coast, (int, np.integer)) or not 0 <= max_coast < 2 ** 31:
+            raise TrackingError("PoseTracking.max_coast must be an integer >= 0, got %r" % (max_coast,))
+        for k, v in vals.items():
+            setattr(self, k, float(v))
+        self.max_coast = int(max_coast)
+
+    def __repr__(self):
+        return "PoseTracking(%s)" % ", ".join("%s=%r" % (k, getattr(self, k)) for k in self.__slots__)
+
+    def with_horizon(self, horizon_s):
+        """A copy that forecasts ``horizon_s`` seconds ahead."""
+        return PoseTracking(**dict({k: getattr(self, k) for k in self.__slots__}, horizon_s=horizon_s))
+
+
 def check_decode(decode, smooth):
     """The session's decode arguments: ``decode`` one of DECODES, ``smooth`` None or a PoseSmoothing."""
     if decode not in DECODES:
         raise DecodeError("decode must be 'argmax' or 'subpixel', got %r" % (decode,))
     if smooth is not None and not isinstance(smooth, PoseSmoothing):
         raise SmoothingError("smooth must be a PoseSmoothing or None, got %r" % (smooth,))
+
+
+def check_track(track, smooth, predict_now):
+    """The session's tracker arguments: ``track`` None or a PoseTracking, never beside ``smooth``; ``predict_now`` only with it."""
+    if track is not None and not isinstance(track, PoseTracking):
+        raise TrackingError("track must be a PoseTracking or None, got %r" % (track,))
+    if track is not None and smooth is not None:
+        raise TrackingError("track and smooth exclude each other: a session has one temporal filter")
+    if predict_now and track is None:
+        raise TrackingError("predict_now needs track: the forecast is the tracker's")
 
 
 def stream_window_sources(center, newest, G):
@@ -197,6 +253,22 @@ class PoseFrame:
         return self._map(lambda t: t.cpu())
 
 
+class TrackedPoseFrame(PoseFrame):
+    """What a tracking session (``track=PoseTracking(...)``) emits.  ``keypoints`` are the Kalman-filtered ones, ``raw_keypoints`` the
+    decoded ones, ``velocity`` the track's; ``covariance`` (lanes, K, 3) = (Pxx, Pxy, Pyy) of the filtered position in image pixels
+    squared; ``forecast`` (lanes, K, 2) the position ``horizon_s`` ahead; ``status`` (lanes, K) int32, one of ``STATUS``'s codes."""
+    __slots__ = ("covariance", "forecast", "status")
+    STATUS = ("UPDATED", "COASTED_MISSING", "COASTED_GATED", "STARTED", "LOST")
+
+    def __init__(self, frame, keypoints, scores, indices, heatmap, gcn_heatmap, raw_keypoints, velocity, covariance, forecast, status):
+        super().__init__(frame, keypoints, scores, indices, heatmap, gcn_heatmap, raw_keypoints, velocity)
+        self.covariance, self.forecast, self.status = covariance, forecast, status
+
+    def _map(self, fn):
+        return TrackedPoseFrame(self.frame, *[None if getattr(self, k) is None else fn(getattr(self, k))
+                                              for k in PoseFrame.__slots__[1:] + self.__slots__])
+
+
 class PoseStream:
     """Streaming session around a HuPRNet.  ``push(adc_hori, adc_vert)`` takes the new int16 frame of both sensors,
     (lanes, 4, 192, 256, 2) each — device tensors are used directly, host tensors go through the session's pinned staging and an
@@ -209,15 +281,22 @@ class PoseStream:
     the model at batch 2: bit-identical to the offline route on a batch of 2, not to two ``lanes = 1`` sessions (the existing kernels
     take other launch routes for a single sample).  ``decode="subpixel"`` refines every keypoint to sub-pixel
     position; ``smooth=PoseSmoothing(rate_hz, ...)`` filters the keypoints over time (the filter state is the session's, ``reset()``
-    clears it) and adds ``PoseFrame.velocity``.  With the defaults the session decodes exactly as before, in the same two launches."""
+    clears it) and adds ``PoseFrame.velocity``.  ``track=PoseTracking(rate_hz, ...)`` is the other temporal filter, in place of
+    ``smooth``: a constant-velocity Kalman filter per joint whose measurement noise is read off the heat-map; the session then emits
+    ``TrackedPoseFrame``s (filtered keypoints, velocity, position covariance, forecast, status), and with ``predict_now=True`` the
+    forecast horizon is ``lookahead / rate_hz`` — where the joint is at the newest frame, not at the emitted one — whatever the
+    tracker's own ``horizon_s``.  With the defaults the session decodes exactly as before, in the same two launches."""
 
-    def __init__(self, model, cfg, lanes=1, lookahead=None, graph=True, device=None, decode="argmax", smooth=None):
+    def __init__(self, model, cfg, lanes=1, lookahead=None, graph=True, device=None, decode="argmax", smooth=None, track=None,
+                 predict_now=False):
         D = cfg.DATASET
         self.G = D.numGroupFrames
         self.schedule = StreamSchedule(self.G, lookahead)
         self.lookahead = self.schedule.lookahead
         check_decode(decode, smooth)
-        self.decode, self.smooth = decode, smooth
+        check_track(track, smooth, predict_now)
+        self.decode, self.smooth, self.predict_now = decode, smooth, bool(predict_now)
+        self.track = track.with_horizon(self.lookahead / track.rate_hz) if predict_now else track
         if not isinstance(lanes, int) or lanes < 1:
             raise StreamError("lanes must be a positive integer, got %r" % (lanes,))
         self.device = torch.device(device) if device is not None else next(model.parameters()).device
@@ -255,6 +334,14 @@ class PoseStream:
             if smooth is not None:
                 self._raw, self._vel = torch.empty_like(self._kp), torch.empty_like(self._kp)
                 self._fstate = F_.pose_filter_state(lanes * self.K, dev)
+            # the tracking decode (csrc/pose_track.hip) likewise: _kp the filtered keypoints, _raw the decoded ones, _vel the track's
+            # velocity, _cov / _fc / _status its covariance, forecast and status, _tstate its state
+            self._cov = self._fc = self._status = self._tstate = None
+            if track is not None:
+                self._raw, self._vel, self._fc = torch.empty_like(self._kp), torch.empty_like(self._kp), torch.empty_like(self._kp)
+                self._cov = torch.empty((lanes, self.K, 3), dtype=torch.float32, device=dev)
+                self._status = torch.empty((lanes, self.K), dtype=torch.int32, device=dev)
+                self._tstate = F_.pose_track_state(lanes * self.K, dev)
             self._done = torch.cuda.Event()
         self._graphs = {}              # "host" / "device" input -> (CUDAGraph, (heatmap, gcn_heatmap))
         self._eager_emits = 0
@@ -294,6 +381,14 @@ class PoseStream:
         heat, gcn = self.model.forward_chirp_maps(*self._maps)
         L, s = rt.lib(), rt.stream()
         rows = self.lanes * self.K
+        if self.track is not None:
+            t = self.track
+            rt.check(L.hupr_pose_track_f32(rt.ptr(F_._c(gcn)), rows, self.H, self.W, self.ratio, int(self.decode == "subpixel"),
+                                           rt.ptr(self._tstate), t.rate_hz, t.accel_psd, t.meas_std, t.heatmap_gain, t.gate,
+                                           t.max_coast, t.init_speed_std, t.min_score, t.horizon_s, rt.ptr(self._idx),
+                                           rt.ptr(self._mx), rt.ptr(self._raw), rt.ptr(self._kp), rt.ptr(self._vel),
+                                           rt.ptr(self._cov), rt.ptr(self._fc), rt.ptr(self._status), s))
+            return heat, gcn
         if self._fused:
             f = self.smooth
             params = (0.0,) * 5 if f is None else (f.rate_hz, f.min_cutoff, f.beta, f.d_cutoff, f.min_score)
@@ -323,6 +418,9 @@ class PoseStream:
             self._busy = False
 
     def _frame(self, center, out):
+        if self.track is not None:
+            return TrackedPoseFrame(center, self._kp, self._mx, self._idx, out[0], out[1], self._raw, self._vel, self._cov, self._fc,
+                                    self._status)
         return PoseFrame(center, self._kp, self._mx, self._idx, out[0], out[1], self._raw, self._vel)
 
     # -- public ---------------------------------------------------------------------------------------------------------------
@@ -376,6 +474,8 @@ class PoseStream:
             rt.check(rt.lib().hupr_stream_reset(rt.ptr(self._state), rt.stream()))
             if self._fstate is not None:
                 self._fstate.zero_()                           # "never seen": the next valid sample of a joint starts its filter
+            if self._tstate is not None:
+                self._tstate.zero_()                           # likewise: the next usable measurement of a joint starts its track
         self.schedule.reset()
 
 
@@ -392,12 +492,35 @@ def parse(argv=None):
     p.add_argument("--decode", choices=DECODES, default="argmax", help="argmax: the reference's decode; subpixel: refined peaks")
     p.add_argument("--smooth", action="store_true", help="One-Euro filter over the keypoints (needs --rate); adds the velocity")
     p.add_argument("--rate", type=float, default=None, help="frames per second of the capture (required with --smooth)")
+    p.add_argument("--track", action="store_true", help="Kalman filter per joint (needs --rate, excludes --smooth); adds velocity, "
+                   "covariance, forecast and status")
+    p.add_argument("--predict-now", action="store_true", help="with --track: forecast every joint to the newest frame (lookahead / rate)")
+    p.add_argument("--accel-psd", type=float, default=None, help="with --track: white-acceleration power, pixel^2 / s^3 (default 200)")
+    p.add_argument("--gate", type=float, default=None, help="with --track: largest accepted squared Mahalanobis distance (default 13.816)")
+    p.add_argument("--max-coast", type=int, default=None, help="with --track: frames a track survives without a measurement (default 5)")
     p.add_argument("--weights", choices=WEIGHTS, default="live", help="live: model_state_dict as trained; averaged: ema_state_dict "
                    "(a run with TRAINING.emaDecay)")
     args = p.parse_args(argv)
     if args.smooth and args.rate is None:
         p.error("--smooth needs --rate (frames per second)")
+    if args.track and args.rate is None:
+        p.error("--track needs --rate (frames per second)")
+    if args.track and args.smooth:
+        p.error("--track and --smooth exclude each other: a session has one temporal filter")
+    if not args.track:
+        for flag, given in (("--predict-now", args.predict_now), ("--accel-psd", args.accel_psd is not None),
+                            ("--gate", args.gate is not None), ("--max-coast", args.max_coast is not None)):
+            if given:
+                p.error("%s needs --track" % flag)
     return args
+
+
+def tracking_from_args(args):
+    """The PoseTracking of a parsed command line (None without --track)."""
+    if not args.track:
+        return None
+    kw = {k: getattr(args, k) for k in ("accel_psd", "gate", "max_coast") if getattr(args, k) is not None}
+    return PoseTracking(args.rate, **kw)
 
 
 def load_model_best(model, log_dir, device, weights="live"):
@@ -447,7 +570,8 @@ def main(argv=None):
         frames.append(dca1000_frames(raw))                      # (frames, 4, 192, 256, 2) int16, de-interleaved on the GPU
     n = min(frames[0].shape[0], frames[1].shape[0])
     session = PoseStream(model, cfg, lanes=1, lookahead=args.lookahead, graph=not args.no_graph, device=dev, decode=args.decode,
-                         smooth=PoseSmoothing(args.rate) if args.smooth else None)
+                         smooth=PoseSmoothing(args.rate) if args.smooth else None, track=tracking_from_args(args),
+                         predict_now=args.predict_now)
     records = []
 
     def record(pf):
@@ -455,6 +579,10 @@ def main(argv=None):
         records.append({"frame": int(pf.frame), "keypoints": [[float(x), float(y), float(s)] for x, y, s in kp]})
         if pf.velocity is not None:
             records[-1]["velocity"] = [[float(vx), float(vy)] for vx, vy in pf.velocity.cpu().numpy()[0]]
+        if isinstance(pf, TrackedPoseFrame):
+            records[-1]["covariance"] = [[float(v) for v in c] for c in pf.covariance.cpu().numpy()[0]]
+            records[-1]["forecast"] = [[float(x), float(y)] for x, y in pf.forecast.cpu().numpy()[0]]
+            records[-1]["status"] = [int(c) for c in pf.status.cpu().numpy()[0]]
 
     for i in range(n):
         pf = session.push(frames[0][i:i + 1], frames[1][i:i + 1])

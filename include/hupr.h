@@ -343,6 +343,52 @@ size_t hupr_pose_filter_state_bytes(long rows);
 int hupr_pose_decode_f32(const float* heat, long rows, int H, int W, float ratio, int refine, float* filter_state_or_null,
                          float rate_hz, float min_cutoff, float beta, float d_cutoff, float min_score, int* idx, float* maxval,
                          float* raw_keypoints, float* keypoints_or_null, float* velocity_or_null, hupr_stream_t stream);
+/* Keypoint decode with a constant-velocity Kalman filter per row in one launch (csrc/pose_track.hip): arg-max, sub-pixel refinement,
+ * a measurement covariance read off the heat-map, predict / gate / update, and a forecast.  One 64-lane wave per row, no scratch, no
+ * LDS.  All positions are image pixels, all times seconds; one call is one frame, dt = 1 / rate_hz.
+ * Decode.  heat, idx, maxval and raw_keypoints = z are those of hupr_pose_decode_f32 for the same refine, bit for bit, the (0, 0) of a
+ *   non-positive maximum included.
+ * Measurement covariance.  On the window of radius 3 around the arg-max pixel (px, py), clipped to the map, with window-relative
+ *   coordinates u, v in -3..3 (u = x - px, v = y - py) and weights w = fmaxf(h, 0) (a NaN pixel weighs 0; all 0 where maxval <= 0):
+ *     m = sum w;  cu = sum w u / m, cv = sum w v / m;
+ *     Sxx = sum w (u - cu)^2 / m,  Sxy = sum w (u - cu)(v - cv) / m,  Syy = sum w (v - cv)^2 / m   (heat-map pixels squared)
+ *     R = ratio^2 heatmap_gain [[Sxx, Sxy], [Sxy, Syy]] + meas_std^2 I.
+ *   heatmap_gain = 0 gives the constant isotropic R.  S is a spread measure, not an estimate of the peak's width: the window truncates
+ *   a wide peak (a Gaussian of sigma 2 measures about 2.67 per axis, not 4), and heatmap_gain scales it.
+ * Usable measurement: maxval > min_score, z finite, m > 0 and R finite.
+ * state : float [rows][16] = (x, y, vx, vy, P00, P01, P02, P03, P11, P12, P13, P22, P23, P33, live, coast): the state vector in the
+ *   order (x, y, vx, vy), the upper triangle of its symmetric 4 x 4 covariance P row by row, live = 1 while a track exists, coast =
+ *   the number of consecutive frames it went without an accepted measurement.  hupr_pose_track_state_bytes(rows) bytes, 16-byte
+ *   aligned; all zero = never seen.  Required; it advances with every launch.
+ * Predict (live track only): x- = F x, P- = F P F^T + Q with the constant-velocity F = [[I, dt I], [0, I]] and, per axis, the white-
+ *   acceleration Q = accel_psd [[dt^3 / 3, dt^2 / 2], [dt^2 / 2, dt]] (Bar-Shalom, Li & Kirubarajan 2001, section 6.2.2).
+ * Gate and update (live track only), H = [I 0]: nu = z - H x-, S = H P- H^T + R, d2 = nu^T S^-1 nu through the closed-form 2 x 2
+ *   inverse.  The measurement is accepted iff it is usable, det S > 0 and finite, and d2 <= gate (a chi-square quantile, 2 d.o.f.).
+ *   Accepted: K = P- H^T S^-1, x = x- + K nu, P = (I - K H) P- (I - K H)^T + K R K^T (Joseph form), then P = (P + P^T) / 2;
+ *     coast = 0; status HUPR_TRACK_UPDATED.
+ *   Not accepted, coast < max_coast: x = x-, P = P-, coast += 1; status HUPR_TRACK_COASTED_MISSING (not usable) or
+ *     HUPR_TRACK_COASTED_GATED (usable, refused by the gate).
+ *   Not accepted, coast == max_coast (it would coast for the (max_coast + 1)-th consecutive frame): the track ends, and the row
+ *     goes on as one without a live track, in the same frame.
+ * No live track: a usable measurement starts one, x = (z, 0, 0), P = diag-blocks(R, init_speed_std^2 I), live = 1, coast = 0, status
+ *   HUPR_TRACK_STARTED; otherwise the state is all zero and the status HUPR_TRACK_LOST.
+ * Outputs per row: keypoints [rows][2] = (x, y); velocity [rows][2] = (vx, vy) per second; covariance [rows][3] = (P00, P01, P11),
+ *   the position block; forecast [rows][2] = (x + vx horizon_s, y + vy horizon_s), with horizon_s = 0 the keypoints bit for bit;
+ *   status [rows] int.  STARTED: keypoints = z bit for bit, velocity 0, covariance R.  LOST: keypoints = forecast = z, velocity and
+ *   covariance 0.
+ * Parameters: rate_hz, meas_std, gate, init_speed_std > 0 and finite; accel_psd (pixel^2 / s^3), heatmap_gain, horizon_s >= 0 and
+ *   finite; max_coast >= 0; min_score not NaN.  They are launch arguments, i.e. constants of a captured graph.
+ * rows == 0 is a no-op. */
+#define HUPR_TRACK_UPDATED 0
+#define HUPR_TRACK_COASTED_MISSING 1
+#define HUPR_TRACK_COASTED_GATED 2
+#define HUPR_TRACK_STARTED 3
+#define HUPR_TRACK_LOST 4
+size_t hupr_pose_track_state_bytes(long rows);
+int hupr_pose_track_f32(const float* heat, long rows, int H, int W, float ratio, int refine, float* state, float rate_hz,
+                        float accel_psd, float meas_std, float heatmap_gain, float gate, int max_coast, float init_speed_std,
+                        float min_score, float horizon_s, int* idx, float* maxval, float* raw_keypoints, float* keypoints,
+                        float* velocity, float* covariance, float* forecast, int* status, hupr_stream_t stream);
 
 /* tri-/bilinear align_corners=True resampling (models/layers.py:84,89,199,204; gcn_networks.py:49,63) */
 int hupr_interp_linear_fwd_f32(const float* x, float* y, int Bn, int Di, int Hi, int Wi, int Do, int Ho, int Wo,
