@@ -1448,10 +1448,30 @@ GCN_MATH = "f32"
 GCN_PRODUCTS = True        # test aid: False = the generic fp32 engine instead of csrc/gcn_products.hip
 
 
-def _gcn_products_ok(x, weight):
+def _gcn_products_ok(F, ld, weight_shape, dtype):
     """The dedicated PRGCN product kernels apply: fp32 pipe (the default of the head in every mode), 16-wide key-point slots."""
-    return (GCN_PRODUCTS and (GCN_MATH == "f32" or _st.math == "f32") and x.dtype == torch.float32 and x.shape[2] == 16
-            and x.shape[1] % 64 == 0 and tuple(weight.shape) == (x.shape[1], x.shape[1]))
+    return (GCN_PRODUCTS and (GCN_MATH == "f32" or _st.math == "f32") and dtype == torch.float32 and ld == 16
+            and F % 64 == 0 and tuple(weight_shape) == (F, F))
+
+
+def gcn_route(B, F, ld, weight_shape, dtype, backward=False):
+    """Which kernels a PRGCN layer on x (B, F, ld) of ``dtype`` with a weight of ``weight_shape`` runs its products on (host logic
+    only): "sliced" (forward of a single sample with F % 1024 == 0: eight K slices of a batched GEMM, summed by the adjacency kernel),
+    "products" (csrc/gcn_products.hip) or "generic" (the fp32 / bf16 GEMM engine)."""
+    products = _gcn_products_ok(F, ld, weight_shape, dtype)
+    if backward:
+        return "products" if products and B > 1 else "generic"
+    if B == 1 and F % 1024 == 0:
+        return "sliced"
+    return "products" if products else "generic"
+
+
+def head_route(region_switched, is_cuda, dtype, channels, weight_shape, num_keypoints):
+    """Which kernels the 1x1 head runs on (host logic only): "head1x1" (Head1x1Fn, csrc/head.hip) inside a bf16 run whose "head" region
+    is switched to fp32, else "generic" (the generic convolution)."""
+    if region_switched and is_cuda and dtype == torch.float32 and channels == 32 and tuple(weight_shape) == (num_keypoints, 32, 1, 1):
+        return "head1x1"
+    return "generic"
 
 
 @_math_scoped
@@ -1464,12 +1484,13 @@ class GCNLayerFn(torch.autograd.Function):
         B, F, ld = x.shape
         K = bias.shape[1]
         L = rt.lib()
-        if B == 1 and F % 1024 == 0:
+        route = gcn_route(B, F, ld, weight.shape, x.dtype)
+        if route == "sliced":
             # single-sample inference: F / 128 = 8 workgroups would each walk K = F alone (37 us of latency for 34 MFLOP);
             # eight K slices side by side as a batched GEMM; the adjacency kernel sums them
             S = 8
             t = gemm(0, 0, weight, x, F, ld, F // S, F, ld, S, F // S, (F // S) * ld, math=GCN_MATH)
-        elif _gcn_products_ok(x, weight):
+        elif route == "products":
             S = 1
             t = torch.empty_like(x)
             rt.check(L.hupr_gcn_wx_f32(rt.ptr(_c(weight)), rt.ptr(x), rt.ptr(t), B, F, ld, 0, rt.stream()))
@@ -1501,7 +1522,7 @@ class GCNLayerFn(torch.autograd.Function):
         dbias, db_direct = _pgrad(bias) if tuple(bias.shape) == (F, K) and bias.is_contiguous() else (torch.empty((F, K), dtype=torch.float32, device=x.device), False)
         rt.check(L.hupr_gcn_adj_bwd_f32(rt.ptr(_c(dy)), rt.ptr(y), rt.ptr(adj), rt.ptr(dt), rt.ptr(gm), rt.ptr(dbias), B, F, K,
                                         ld, 1 if ctx.relu else 0, rt.stream()))
-        if _gcn_products_ok(x, weight) and B > 1:
+        if gcn_route(B, F, ld, weight.shape, x.dtype, backward=True) == "products":
             # the batch folded into the matrix pipe's column axis (dx) / reduction axis (dW) in place: csrc/gcn_products.hip
             dx = torch.empty_like(x)
             rt.check(L.hupr_gcn_wx_f32(rt.ptr(_c(weight)), rt.ptr(dt), rt.ptr(dx), B, F, ld, 1, rt.stream()))
@@ -1577,7 +1598,7 @@ class Head1x1Fn(torch.autograd.Function):
 def head_conv(x, weight, num_keypoints):
     """1x1 head: the dedicated fp32 kernels inside a bf16 run whose "head" region is switched to fp32 (32 -> 16 channels),
     the generic convolution otherwise (the pure fp32 parity path keeps the arithmetic its golden fixtures were pinned with)."""
-    if _st.region_switched and x.is_cuda and x.dtype == torch.float32 and x.shape[-1] == 32 and tuple(weight.shape) == (num_keypoints, 32, 1, 1):
+    if head_route(_st.region_switched, x.is_cuda, x.dtype, x.shape[-1], weight.shape, num_keypoints) == "head1x1":
         return Head1x1Fn.apply(x, weight, _head_w16_cached(weight))
     return conv(x, head_weight16(weight, num_keypoints), None, None, (0, 0, 0))
 
