@@ -1895,6 +1895,38 @@ def pose_decode(heat, ratio, refine=True, filter_state=None, smoothing=None):
     return idx, mx, raw, kp, vel
 
 
+def pose_decode_integral(heat, ratio, radius, filter_state=None, smoothing=None):
+    """heat (..., H, W) fp32 GPU -> ``pose_decode``'s 5-tuple in one launch (csrc/pose_integral.hip; the rule is stated beside
+    hupr_pose_decode_integral_f32 in include/hupr.h): the raw keypoint is the mass centroid of the weights max(h, 0) over the window
+    of ``radius`` pixels around the arg-max, clipped to the map, times ``ratio``; ``radius`` 0 is the whole map, the centroid the
+    integral coordinate loss trains.  ``idx`` / ``maxval`` are ``argmax_rows``' bits.  ``filter_state`` and ``smoothing`` are
+    ``pose_decode``'s: the same state tensor, the same One-Euro filter.  Device tensors, no sync."""
+    if heat.dim() < 2:
+        raise ValueError("pose_decode_integral needs (..., H, W) heat-maps, got shape %r" % (tuple(heat.shape),))
+    if heat.dtype != torch.float32:
+        raise ValueError("pose_decode_integral needs fp32 heat-maps, got %s" % heat.dtype)
+    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 0 <= radius < 2 ** 31:
+        raise ValueError("pose_decode_integral needs an integer radius >= 0 (0 = the whole map), got %r" % (radius,))
+    if (filter_state is None) != (smoothing is None):
+        raise ValueError("filter_state and smoothing go together")
+    heat = _c(heat)
+    lead, (H, W) = tuple(heat.shape[:-2]), heat.shape[-2:]
+    rows = int(np.prod(lead, dtype=np.int64))
+    idx = torch.empty(lead, dtype=torch.int32, device=heat.device)
+    mx = torch.empty(lead, dtype=torch.float32, device=heat.device)
+    raw = torch.empty(lead + (2,), dtype=torch.float32, device=heat.device)
+    kp = vel = None
+    params = (0.0,) * 5
+    if filter_state is not None:
+        if filter_state.dtype != torch.float32 or filter_state.numel() * 4 != int(rt.lib().hupr_pose_filter_state_bytes(rows)):
+            raise ValueError("filter_state must be the fp32 tensor pose_filter_state(%d, device) returns" % rows)
+        kp, vel = torch.empty_like(raw), torch.empty_like(raw)
+        params = tuple(float(getattr(smoothing, k)) for k in ("rate_hz", "min_cutoff", "beta", "d_cutoff", "min_score"))
+    rt.check(rt.lib().hupr_pose_decode_integral_f32(rt.ptr(heat), rows, H, W, float(ratio), int(radius), rt.ptr(filter_state), *params,
+                                                    rt.ptr(idx), rt.ptr(mx), rt.ptr(raw), rt.ptr(kp), rt.ptr(vel), rt.stream()))
+    return idx, mx, raw, kp, vel
+
+
 TRACK_UPDATED, TRACK_COASTED_MISSING, TRACK_COASTED_GATED, TRACK_STARTED, TRACK_LOST = range(5)      # pose_track's status codes
 _TRACK_PARAMS = ("rate_hz", "accel_psd", "meas_std", "heatmap_gain", "gate", "max_coast", "init_speed_std", "min_score", "horizon_s")
 

@@ -5,7 +5,7 @@ import math
 import torch
 
 from .. import functional as F_
-from .metrics import decode_setting, get_final_preds, get_max_preds
+from .metrics import decode_radius_setting, decode_setting, get_final_preds, get_integral_preds, get_max_preds
 
 PAIR_BCE = True      # test aid: False = one BCE node per head, combined by torch
 
@@ -76,6 +76,7 @@ class LossComputer():
         self.imgSize = self.imgWidth = self.imgHeight = cfg.DATASET.imgSize
         self.lossDecay = cfg.TRAINING.lossDecay
         self.decode = decode_setting(cfg)       # TEST.decode: how the host-decode branch below turns preds2 into pred2d
+        self.decodeRadius = decode_radius_setting(cfg)      # TEST.decodeRadius: the integral decode's window (None for the others)
         self.targets_mode = targets_setting(cfg)    # TRAINING.targets: which joints computeLoss takes and how targets() encodes them
         # TRAINING.ohkm / TRAINING.jointWeights: with either set computeLoss takes the mined loss (k = numKeypoints for weights alone)
         self.ohkm = ohkm_setting(cfg)
@@ -137,8 +138,11 @@ class LossComputer():
             # the reference decodes both arg-max sets every iteration (misc/losses.py:43-44); here the two decodes are
             # kernels on the step's stream and the (B,K) index / maximum tensors stay on the device (no sync, no D2H)
             return loss, loss2, F_.argmax_rows(preds2.detach().reshape(-1, H * W)), F_.argmax_rows(heatmaps.reshape(-1, H * W))
-        final = get_final_preds if self.decode == "subpixel" else get_max_preds
-        pred2d, _ = final(preds2.detach().reshape(-1, K, H, W))
+        if self.decode == "integral":
+            pred2d, _ = get_integral_preds(preds2.detach().reshape(-1, K, H, W), self.decodeRadius)
+        else:
+            final = get_final_preds if self.decode == "subpixel" else get_max_preds
+            pred2d, _ = final(preds2.detach().reshape(-1, K, H, W))
         gt2d, _ = get_max_preds(heatmaps)
         return loss, loss2, pred2d, gt2d
 

@@ -54,6 +54,9 @@ SIGNATURES = {
     # keypoint decode: arg-max + sub-pixel refinement + One-Euro filter (csrc/pose_decode.hip)
     "hupr_pose_filter_state_bytes": (c_size_t, [c_long]),
     "hupr_pose_decode_f32": (c_int, [c_void_p, c_long, c_int, c_int, c_float, c_int, c_void_p] + [c_float] * 5 + [c_void_p] * 6),
+    # integral keypoint decode: arg-max + windowed mass centroid + One-Euro filter (csrc/pose_integral.hip)
+    "hupr_pose_decode_integral_f32": (c_int, [c_void_p, c_long, c_int, c_int, c_float, c_int, c_void_p] + [c_float] * 5 +
+                                      [c_void_p] * 6),
     # keypoint decode + constant-velocity Kalman filter per joint (csrc/pose_track.hip)
     "hupr_pose_track_state_bytes": (c_size_t, [c_long]),
     "hupr_pose_track_f32": (c_int, [c_void_p, c_long, c_int, c_int, c_float, c_int, c_void_p] + [c_float] * 5 + [c_int] +

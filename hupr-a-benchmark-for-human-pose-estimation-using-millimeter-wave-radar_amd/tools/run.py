@@ -110,7 +110,7 @@ class Runner(BaseRunner):
         written to ``<phase>_results.json`` by rank 0 and scored with the OKS evaluator against the ground truth the
         reference uses: the float joints of ``<phase>_gt.json`` (not the integer-truncated ``jointsGroup`` the loss sees by default;
         with ``TRAINING.targets: subpixel`` the loss sees the float joints too, ``loss_labels``).  When ``TRAINING.targets`` or
-        ``TEST.decode`` is ``subpixel``, or ``TRAINING.coordLoss`` or ``TEST.flip`` is set, one more line is printed, the mean per-joint position error in image pixels
+        ``TEST.decode`` is ``subpixel``, ``TEST.decode`` is ``integral``, or ``TRAINING.coordLoss`` or ``TEST.flip`` is set, one more line is printed, the mean per-joint position error in image pixels
         (``mean_position_error``): AP's OKS thresholds are too coarse to show a sub-pixel change.
         ``--keypoints`` prints the per-joint APs (``evaluateEach``) instead of the summary line."""
         self.logger.clear(len(self.testLoader.dataset))
@@ -157,7 +157,8 @@ class Runner(BaseRunner):
             stats = evaluate_keypoints(gts, savePreds)
             print("  ".join("%s: %.3f" % (n, s) for n, s in zip(names, stats)))
             ap = float(stats[0])
-            if "subpixel" in (self.lossComputer.targets_mode, self.lossComputer.decode) or self.lossComputer.coordLoss is not None or self.flip:
+            if ("subpixel" in (self.lossComputer.targets_mode, self.lossComputer.decode) or self.lossComputer.decode == "integral"
+                    or self.lossComputer.coordLoss is not None or self.flip):
                 print("MPJPE: %.3f px (n = %d)" % mean_position_error(gts, savePreds)[::2])
         if self.world > 1:
             box = [ap]

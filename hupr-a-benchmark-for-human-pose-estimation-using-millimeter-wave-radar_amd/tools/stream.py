@@ -20,10 +20,13 @@ refines the peak to sub-pixel position and ``smooth=PoseSmoothing(rate_hz)`` run
 the device; either replaces the two decode launches by one (csrc/pose_decode.hip), inside the captured graph like them.
 ``track=PoseTracking(rate_hz)`` runs a constant-velocity Kalman filter per joint instead (csrc/pose_track.hip, one launch likewise):
 outliers are gated, drop-outs coast on the track's velocity, every joint carries a covariance and a forecast.
+``decode="integral"`` decodes the mass centroid of the window of ``decode_radius`` pixels around the peak (default: the targets' patch
+radius; 0: the whole map) — what the integral coordinate loss trains — in one launch of csrc/pose_integral.hip in place of the two,
+``smooth`` included; it does not combine with ``track``, whose measurement is pinned to the sub-pixel decode.
 
     python -m hupr_amd.tools.stream --config mscsa_prgcn.yaml --dir <logs name> --raw <dir with hori/ and vert/ adc_data.bin>
                                     [--lookahead N] [--math f32|bf16] [--no-graph] [--out poses.json]
-                                    [--decode argmax|subpixel] [--smooth --rate FPS]
+                                    [--decode argmax|subpixel|integral [--decode-radius N]] [--smooth --rate FPS]
                                     [--track --rate FPS [--predict-now] [--accel-psd Q] [--gate D2] [--max-coast N]]
 """
 import argparse
@@ -62,7 +65,8 @@ class StreamEndedError(StreamError):
 
 
 class DecodeError(StreamError):
-    """``decode`` is neither "argmax" nor "subpixel"."""
+    """``decode`` is none of "argmax", "subpixel" and "integral", or ``decode_radius`` is out of range or given without
+    ``decode="integral"``."""
 
 
 class SmoothingError(StreamError):
@@ -70,11 +74,11 @@ class SmoothingError(StreamError):
 
 
 class TrackingError(StreamError):
-    """A ``PoseTracking`` parameter out of range, ``track`` is not a ``PoseTracking``, ``track`` together with ``smooth``, or
-    ``predict_now`` without ``track``."""
+    """A ``PoseTracking`` parameter out of range, ``track`` is not a ``PoseTracking``, ``track`` together with ``smooth`` or with
+    ``decode="integral"``, or ``predict_now`` without ``track``."""
 
 
-DECODES = ("argmax", "subpixel")
+DECODES = ("argmax", "subpixel", "integral")
 WEIGHTS = ("live", "averaged")      # which parameters of model_best.pth: as trained, or their moving average (TRAINING.emaDecay)
 
 
@@ -140,18 +144,34 @@ class PoseTracking:
         return PoseTracking(**dict({k: getattr(self, k) for k in self.__slots__}, horizon_s=horizon_s))
 
 
-def check_decode(decode, smooth):
-    """The session's decode arguments: ``decode`` one of DECODES, ``smooth`` None or a PoseSmoothing."""
-    if decode not in DECODES:
-        raise DecodeError("decode must be 'argmax' or 'subpixel', got %r" % (decode,))
+def check_decode(decode, smooth, decode_radius=None, heatmap_size=None):
+    """The session's decode arguments: ``decode`` one of DECODES, ``smooth`` None or a PoseSmoothing, ``decode_radius`` only with
+    ``decode="integral"`` -> the integral decode's window radius (None for the other decodes): ``decode_radius`` itself, 0 (the whole
+    map) or an integer in [1, heatmap_size - 1], or by default the targets' patch radius at ``heatmap_size``."""
+    if not isinstance(decode, str) or decode not in DECODES:
+        raise DecodeError("decode must be 'argmax', 'subpixel' or 'integral', got %r" % (decode,))
     if smooth is not None and not isinstance(smooth, PoseSmoothing):
         raise SmoothingError("smooth must be a PoseSmoothing or None, got %r" % (smooth,))
+    if decode != "integral":
+        if decode_radius is not None:
+            raise DecodeError("decode_radius needs decode='integral', got decode %r" % (decode,))
+        return None
+    from ..misc.metrics import check_decode_radius, default_decode_radius
+    try:
+        if decode_radius is None:
+            return default_decode_radius(heatmap_size)
+        return check_decode_radius(decode_radius, heatmap_size, "decode_radius")
+    except ValueError as e:
+        raise DecodeError(str(e)) from None
 
 
-def check_track(track, smooth, predict_now):
-    """The session's tracker arguments: ``track`` None or a PoseTracking, never beside ``smooth``; ``predict_now`` only with it."""
+def check_track(track, smooth, predict_now, decode="argmax"):
+    """The session's tracker arguments: ``track`` None or a PoseTracking, never beside ``smooth`` or ``decode="integral"``;
+    ``predict_now`` only with it."""
     if track is not None and not isinstance(track, PoseTracking):
         raise TrackingError("track must be a PoseTracking or None, got %r" % (track,))
+    if track is not None and decode == "integral":
+        raise TrackingError("track and decode='integral' exclude each other: the tracker's measurement is the sub-pixel decode's")
     if track is not None and smooth is not None:
         raise TrackingError("track and smooth exclude each other: a session has one temporal filter")
     if predict_now and track is None:
@@ -285,16 +305,18 @@ class PoseStream:
     ``smooth``: a constant-velocity Kalman filter per joint whose measurement noise is read off the heat-map; the session then emits
     ``TrackedPoseFrame``s (filtered keypoints, velocity, position covariance, forecast, status), and with ``predict_now=True`` the
     forecast horizon is ``lookahead / rate_hz`` — where the joint is at the newest frame, not at the emitted one — whatever the
-    tracker's own ``horizon_s``.  With the defaults the session decodes exactly as before, in the same two launches."""
+    tracker's own ``horizon_s``.  ``decode="integral"`` decodes the mass centroid of the window of ``decode_radius`` heat-map pixels
+    around the peak (None: the targets' patch radius, 6 at 64 and 9 at 128; 0: the whole map), with ``smooth`` in the same launch and
+    never with ``track``.  With the defaults the session decodes exactly as before, in the same two launches."""
 
     def __init__(self, model, cfg, lanes=1, lookahead=None, graph=True, device=None, decode="argmax", smooth=None, track=None,
-                 predict_now=False):
+                 predict_now=False, decode_radius=None):
         D = cfg.DATASET
         self.G = D.numGroupFrames
         self.schedule = StreamSchedule(self.G, lookahead)
         self.lookahead = self.schedule.lookahead
-        check_decode(decode, smooth)
-        check_track(track, smooth, predict_now)
+        self.decode_radius = check_decode(decode, smooth, decode_radius, D.heatmapSize)
+        check_track(track, smooth, predict_now, decode)
         self.decode, self.smooth, self.predict_now = decode, smooth, bool(predict_now)
         self.track = track.with_horizon(self.lookahead / track.rate_hz) if predict_now else track
         if not isinstance(lanes, int) or lanes < 1:
@@ -327,8 +349,8 @@ class PoseStream:
             self._idx = torch.empty((lanes, self.K), dtype=torch.int32, device=dev)
             self._mx = torch.empty((lanes, self.K), dtype=torch.float32, device=dev)
             self._kp = torch.empty((lanes, self.K, 2), dtype=torch.float32, device=dev)
-            # the one-launch decode (csrc/pose_decode.hip) serves everything but the default; with a filter _kp holds the filtered
-            # keypoints, _raw the decoded ones, _vel the velocity, _fstate the filter's state
+            # the one-launch decode (csrc/pose_decode.hip; csrc/pose_integral.hip for "integral") serves everything but the default; with
+            # a filter _kp holds the filtered keypoints, _raw the decoded ones, _vel the velocity, _fstate the filter's state
             self._fused = decode != "argmax" or smooth is not None
             self._raw = self._vel = self._fstate = None
             if smooth is not None:
@@ -392,10 +414,12 @@ class PoseStream:
         if self._fused:
             f = self.smooth
             params = (0.0,) * 5 if f is None else (f.rate_hz, f.min_cutoff, f.beta, f.d_cutoff, f.min_score)
-            rt.check(L.hupr_pose_decode_f32(rt.ptr(F_._c(gcn)), rows, self.H, self.W, self.ratio, int(self.decode == "subpixel"),
-                                            rt.ptr(self._fstate), *params, rt.ptr(self._idx), rt.ptr(self._mx),
-                                            rt.ptr(self._kp if f is None else self._raw), rt.ptr(None if f is None else self._kp),
-                                            rt.ptr(self._vel), s))
+            integral = self.decode == "integral"
+            fn = L.hupr_pose_decode_integral_f32 if integral else L.hupr_pose_decode_f32
+            mode = self.decode_radius if integral else int(self.decode == "subpixel")      # the sixth argument: radius / refine
+            rt.check(fn(rt.ptr(F_._c(gcn)), rows, self.H, self.W, self.ratio, mode, rt.ptr(self._fstate), *params, rt.ptr(self._idx),
+                        rt.ptr(self._mx), rt.ptr(self._kp if f is None else self._raw), rt.ptr(None if f is None else self._kp),
+                        rt.ptr(self._vel), s))
             return heat, gcn
         rt.check(L.hupr_argmax_rows_f32(rt.ptr(F_._c(gcn)), rows, self.H * self.W, rt.ptr(self._idx), rt.ptr(self._mx), s))
         rt.check(L.hupr_stream_keypoints_f32(rt.ptr(self._idx), rt.ptr(self._mx), rt.ptr(self._kp), rows, self.W, self.ratio, s))
@@ -489,7 +513,10 @@ def parse(argv=None):
     p.add_argument("--math", choices=("f32", "bf16"), default=None, help="precision mode (default: the process default)")
     p.add_argument("--no-graph", action="store_true", help="eager launches instead of one hipGraph replay per frame")
     p.add_argument("--out", type=str, default="poses.json")
-    p.add_argument("--decode", choices=DECODES, default="argmax", help="argmax: the reference's decode; subpixel: refined peaks")
+    p.add_argument("--decode", choices=DECODES, default="argmax", help="argmax: the reference's decode; subpixel: refined peaks; "
+                   "integral: the mass centroid of a window around the peak")
+    p.add_argument("--decode-radius", type=int, default=None, help="with --decode integral: the window radius in heat-map pixels "
+                   "(default: the targets' patch radius; 0 = the whole map)")
     p.add_argument("--smooth", action="store_true", help="One-Euro filter over the keypoints (needs --rate); adds the velocity")
     p.add_argument("--rate", type=float, default=None, help="frames per second of the capture (required with --smooth)")
     p.add_argument("--track", action="store_true", help="Kalman filter per joint (needs --rate, excludes --smooth); adds velocity, "
@@ -507,6 +534,12 @@ def parse(argv=None):
         p.error("--track needs --rate (frames per second)")
     if args.track and args.smooth:
         p.error("--track and --smooth exclude each other: a session has one temporal filter")
+    if args.track and args.decode == "integral":
+        p.error("--track and --decode integral exclude each other: the tracker's measurement is the sub-pixel decode's")
+    if args.decode_radius is not None and args.decode != "integral":
+        p.error("--decode-radius needs --decode integral")
+    if args.decode_radius is not None and args.decode_radius < 0:
+        p.error("--decode-radius must be 0 (the whole map) or a positive number of heat-map pixels")
     if not args.track:
         for flag, given in (("--predict-now", args.predict_now), ("--accel-psd", args.accel_psd is not None),
                             ("--gate", args.gate is not None), ("--max-coast", args.max_coast is not None)):
@@ -571,7 +604,7 @@ def main(argv=None):
     n = min(frames[0].shape[0], frames[1].shape[0])
     session = PoseStream(model, cfg, lanes=1, lookahead=args.lookahead, graph=not args.no_graph, device=dev, decode=args.decode,
                          smooth=PoseSmoothing(args.rate) if args.smooth else None, track=tracking_from_args(args),
-                         predict_now=args.predict_now)
+                         predict_now=args.predict_now, decode_radius=args.decode_radius)
     records = []
 
     def record(pf):

@@ -343,6 +343,32 @@ size_t hupr_pose_filter_state_bytes(long rows);
 int hupr_pose_decode_f32(const float* heat, long rows, int H, int W, float ratio, int refine, float* filter_state_or_null,
                          float rate_hz, float min_cutoff, float beta, float d_cutoff, float min_score, int* idx, float* maxval,
                          float* raw_keypoints, float* keypoints_or_null, float* velocity_or_null, hupr_stream_t stream);
+/* Integral keypoint decode in one launch (csrc/pose_integral.hip): arg-max, the mass centroid of a window around it and, with a filter
+ * state, One-Euro smoothing.  The decode of Sun et al., "Integral Human Pose Regression" (ECCV 2018) and Nibali et al. (DSNT), which
+ * hupr_coord_loss_fwd_f32 trains, restricted to a window so that a floor under the map does not pull it to the map centre.  New, no
+ * reference counterpart; one 64-lane wave per row, no scratch, no LDS, no atomics: every output is bit-identical from run to run.
+ * heat : float [rows][H][W].  idx / maxval [rows]: the bits of hupr_argmax_rows_f32 (first maximum wins).
+ * With the peak at (px, py) = (idx % W, idx / W), h the row as H x W and radius r >= 0:
+ *   Window    x in [max(px - r, 0), min(px + r, W - 1)] = [x0, x1], y in [max(py - r, 0), min(py + r, H - 1)] = [y0, y1].  r == 0 means
+ *             the whole map, enumerated as the window [0, W-1] x [0, H-1]; any r >= max(H, W) - 1 clips to that window and gives the
+ *             bits of r == 0.
+ *   Weights   w = fmaxf(h, 0): a negative pixel and a NaN pixel weigh 0 (the weights of hupr_pose_track_f32's covariance window).
+ *   Moments   m = sum w, Mx = sum w (x - px), My = sum w (y - py) over the window, in fp32, in this order: with ww = x1 - x0 + 1 the
+ *             window cell c = 0 .. ww (y1 - y0 + 1) - 1 is the pixel (x0 + c % ww, y0 + c / ww); lane l of the wave takes the cells
+ *             c = l, l + 64, l + 128, ... and adds them in increasing c, starting from 0: m = m + w, Mx = fmaf(w, x - px, Mx),
+ *             My = fmaf(w, y - py, My) (x - px and y - py are exact integers); then the three lane sums go through the wave butterfly,
+ *             v = v + v[lane ^ 32], then ^ 16, 8, 4, 2, 1.
+ *   Offset    (ox, oy) = (Mx / m, My / m) in heat-map pixels.  No clamp: the window bounds each component by r.  (0, 0) where
+ *             maxval <= 0 (the window is then not read), where m is not positive and finite, or where Mx / m or My / m is not finite.
+ * raw_keypoints [rows][2] = ((px + ox) * ratio, (py + oy) * ratio), (0, 0) where maxval <= 0, as in hupr_pose_decode_f32.
+ * filter_state_or_null, rate_hz, min_cutoff, beta, d_cutoff, min_score, keypoints_or_null, velocity_or_null: the One-Euro stage of
+ *   hupr_pose_decode_f32 on this raw keypoint, word for word: the same [rows][8] state of hupr_pose_filter_state_bytes(rows) bytes
+ *   (a session may not mix the two decodes on one state and expect either's track), the same meaning of missing, the same outputs.
+ * Returns -1 (HUPR_ERR_ARG) before any launch for a null required pointer, radius < 0, H or W below 1, rows or H * W beyond 2^31, and
+ * the filter-argument errors of hupr_pose_decode_f32.  rows == 0 is a no-op. */
+int hupr_pose_decode_integral_f32(const float* heat, long rows, int H, int W, float ratio, int radius, float* filter_state_or_null,
+                                  float rate_hz, float min_cutoff, float beta, float d_cutoff, float min_score, int* idx, float* maxval,
+                                  float* raw_keypoints, float* keypoints_or_null, float* velocity_or_null, hupr_stream_t stream);
 /* Keypoint decode with a constant-velocity Kalman filter per row in one launch (csrc/pose_track.hip): arg-max, sub-pixel refinement,
  * a measurement covariance read off the heat-map, predict / gate / update, and a forecast.  One 64-lane wave per row, no scratch, no
  * LDS.  All positions are image pixels, all times seconds; one call is one frame, dt = 1 / rate_hz.
