@@ -3,22 +3,9 @@
 // Networks", DSNT), written relative to the joint and damped by eps so that a nearly empty plane has a bounded gradient.  The rule is
 // stated in full beside hupr_coord_loss_fwd_f32 in include/hupr.h.  No atomics, no workspace and no data-dependent summation order:
 // every output is bit-identical from run to run, and equal planes with equal joints give equal bits.
-#include "hupr_common.h"
+#include "coord_plane.h"
 
 namespace hupr {
-
-// One axis of one joint in heat-map pixels; a NaN where the row is invalid.  snap: the pixel hupr_k_gaussian_targets centres its patch
-// on, (int)(a + 0.5f) with the truncating cast, which is executed only where it is defined (decided in float arithmetic as in
-// target_axis of targets.hip: a NaN fails both comparisons).  Valid iff finite and 0 <= a <= H - 1.
-__device__ __forceinline__ float coord_axis(float joint, float stride, int snap, int H) {
-    float a = joint / stride;
-    if (snap) {
-        const float t = a + 0.5f;
-        if (!(t >= -2147483648.f && t < 2147483648.f)) return NAN;
-        a = (float)(int)t;
-    }
-    return (a >= 0.f && a <= (float)(H - 1)) ? a : NAN;
-}
 
 // One 256-thread workgroup per plane (grid-stride over the 2 B K rows, head-major).  A thread adds its cells' p, p (x - a_x) and
 // p (y - a_y) in index order into three fp32 partials (H * H / 256 terms: 16 at H = 64, 64 at H = 128), then the wave butterfly
@@ -45,51 +32,9 @@ __global__ __launch_bounds__(256) void hupr_k_coord_loss_plane(const float* __re
             continue;
         }
         const float* __restrict__ pp = (r < planes ? p1 : p2) + q * HW;
-        float s = 0.f, nx = 0.f, ny = 0.f;
-        if (VEC) {
-            const int w4 = H >> 2, n4 = H * w4;
-            for (int g = threadIdx.x; g < n4; g += 256) {
-                const float4 v = reinterpret_cast<const float4*>(pp)[g];
-                const int y = g / w4, x = (g - y * w4) << 2;
-                const float dy = (float)y - ay, dx = (float)x - ax;
-                s += v.x;
-                nx = fmaf(v.x, dx, nx);
-                ny = fmaf(v.x, dy, ny);
-                s += v.y;
-                nx = fmaf(v.y, (float)(x + 1) - ax, nx);
-                ny = fmaf(v.y, dy, ny);
-                s += v.z;
-                nx = fmaf(v.z, (float)(x + 2) - ax, nx);
-                ny = fmaf(v.z, dy, ny);
-                s += v.w;
-                nx = fmaf(v.w, (float)(x + 3) - ax, nx);
-                ny = fmaf(v.w, dy, ny);
-            }
-        } else {
-            const int n = H * H;
-            for (int i = threadIdx.x; i < n; i += 256) {
-                const float v = pp[i];
-                const int y = i / H, x = i - y * H;
-                s += v;
-                nx = fmaf(v, (float)x - ax, nx);
-                ny = fmaf(v, (float)y - ay, ny);
-            }
-        }
-        s = wave_sum(s);
-        nx = wave_sum(nx);
-        ny = wave_sum(ny);
-        __syncthreads();        // the previous row's red[] has been read
-        if ((threadIdx.x & 63) == 0) {
-            const int wv = threadIdx.x >> 6;
-            red[0][wv] = s;
-            red[1][wv] = nx;
-            red[2][wv] = ny;
-        }
-        __syncthreads();
+        float S, Nx, Ny;
+        coord_plane_sums<VEC>(pp, ax, ay, H, red, S, Nx, Ny);
         if (threadIdx.x == 0) {
-            const float S = ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3];
-            const float Nx = ((red[1][0] + red[1][1]) + red[1][2]) + red[1][3];
-            const float Ny = ((red[2][0] + red[2][1]) + red[2][2]) + red[2][3];
             const float den = S + eps;
             resid[r * 2 + 0] = Nx / den;
             resid[r * 2 + 1] = Ny / den;
@@ -187,24 +132,9 @@ __global__ __launch_bounds__(256) void hupr_k_coord_loss_bwd(const float* __rest
     }
 }
 
-static inline bool coord_aligned16(const void* a, const void* b) {
-    return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15) == 0;
-}
-
 }  // namespace hupr
 
 using namespace hupr;
-
-// the shape rule shared by both entries; the byte offset of the last cell must fit the kernels' 64-bit index arithmetic
-static int coord_shape(const char* name, long B, int K, int H, float stride) {
-    HUPR_REQUIRE(K >= 1 && K <= 64, "%s: bad shape (K %d must be in [1, 64])", name, K);
-    HUPR_REQUIRE(H >= 1 && H <= 4096, "%s: bad shape (H %d must be in [1, 4096])", name, H);
-    HUPR_REQUIRE(B >= 1, "%s: bad shape (B %ld must be >= 1)", name, B);
-    HUPR_REQUIRE(B <= (INT64_MAX / 8) / K && B * K <= (INT64_MAX / 8) / ((long)H * H), "%s: bad shape (%ld x %d planes of %d x %d cells)",
-                 name, B, K, H, H);
-    HUPR_REQUIRE(stride > 0.f && stride < INFINITY, "%s: bad parameter (stride %g must be positive and finite)", name, stride);
-    return HUPR_OK;
-}
 
 extern "C" int hupr_coord_loss_fwd_f32(const float* p1, const float* p2, const float* joints_xy, long B, int K, int H, float stride,
                                        int snap, const float* joint_w_or_null, float eps, float a0, float a1, float* loss3, float* resid,

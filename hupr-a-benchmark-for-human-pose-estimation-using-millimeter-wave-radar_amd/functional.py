@@ -1810,6 +1810,102 @@ class CoordLossFn(torch.autograd.Function):
         return dp1, dp2, None, None, None, None, None, None, None
 
 
+def default_bones():
+    """The bone table of the data set's skeleton (``datasets.base.SKELETON``, 13 edges over the 14 joints) with zero-based indices."""
+    from .datasets.base import SKELETON
+    return tuple((u - 1, v - 1) for u, v in SKELETON)
+
+
+def bone_table(bones, K):
+    """``bones`` (None = ``default_bones()``, else a sequence of (u, v) pairs of ints) -> a tuple of E pairs, checked as
+    hupr_bone_loss_fwd_f32 checks them: 1 <= E <= 32, indices in [0, K), u != v."""
+    if bones is None:
+        bones = default_bones()
+    try:
+        table = tuple((u, v) for u, v in bones)
+    except (TypeError, ValueError):
+        raise ValueError("BoneLossFn: bones must be None or a sequence of (u, v) pairs, got %r" % (bones,))
+    if not 1 <= len(table) <= 32:
+        raise ValueError("BoneLossFn: 1 to 32 bones, got %d" % len(table))
+    for u, v in table:
+        if not all(isinstance(i, (int, np.integer)) and not isinstance(i, bool) and 0 <= i < K for i in (u, v)) or u == v:
+            raise ValueError("BoneLossFn: a bone joins two different joints of [0, %d), got %r" % (K, (u, v)))
+    return tuple((int(u), int(v)) for u, v in table)
+
+
+@_math_scoped
+class BoneLossFn(torch.autograd.Function):
+    """Bone-vector loss on both heads (csrc/bone_loss.hip; the rule is stated beside hupr_bone_loss_fwd_f32 in include/hupr.h): an
+    L1, in heat-map pixels, on the error of the vector between the mass centroids of the two maps at the ends of every bone.
+    ``BoneLossFn.apply(p1, p2, joints, stride, snap, bones, bone_w, a0, a1, acc)`` -> (bone_loss, b_heads): bone_loss = a0 B_0 +
+    a1 B_1, b_heads the detached (B_0, B_1); two launches forward, one backward.  p1, p2, joints, stride, snap: as in
+    ``CoordLossFn``; ``bones``: None (``default_bones()``, which needs K = 14) or a sequence of 1 to 32 (u, v) pairs of different
+    joints in [0, K); ``bone_w``: None or E fp32 weights on the device; ``acc``: None or 3 fp64 on the device, which accumulate
+    (B_0, B_1, 1) per call.  The damping of the rule is ``BoneLossFn.eps``.  ``BoneLossFn.last_residual`` is the (2, B, E, 2) bone
+    residuals of the latest forward, detached.  No gradient flows to the joints.  Anything else raises: there is no fallback."""
+
+    eps = 1.0
+    last_residual = None
+
+    @staticmethod
+    def forward(ctx, p1, p2, joints, stride, snap, bones, bone_w, a0, a1, acc):
+        for name, x in (("p1", p1), ("p2", p2)):
+            if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float32:
+                raise ValueError("BoneLossFn: %s must be an fp32 GPU tensor, got %s" % (
+                    name, "%s on %s" % (x.dtype, x.device) if isinstance(x, torch.Tensor) else type(x).__name__))
+        if p1.shape != p2.shape or p1.device != p2.device or p1.dim() != 4 or p1.shape[2] != p1.shape[3] or p1.numel() == 0:
+            raise ValueError("BoneLossFn: p1 and p2 must share one shape (B, K, H, H) and one device, got %s, %s" % (
+                tuple(p1.shape), tuple(p2.shape)))
+        B, K, H = p1.shape[0], p1.shape[1], p1.shape[2]
+        if K > 64 or H > 4096:
+            raise ValueError("BoneLossFn: K <= 64 and H <= 4096, got K = %d, H = %d" % (K, H))
+        if not isinstance(joints, torch.Tensor) or joints.device != p1.device or tuple(joints.shape) != (B, K, 2) \
+                or joints.dtype == torch.bool or joints.is_complex():
+            raise ValueError("BoneLossFn: joints must be (%d, %d, 2) of a real dtype on %s, got %s" % (
+                B, K, p1.device, "%s %s on %s" % (tuple(joints.shape), joints.dtype, joints.device)
+                if isinstance(joints, torch.Tensor) else type(joints).__name__))
+        if isinstance(stride, bool) or not isinstance(stride, (int, float)) or not (0 < stride < float("inf")):
+            raise ValueError("BoneLossFn: stride must be a positive finite number, got %r" % (stride,))
+        table = bone_table(bones, K)
+        E = len(table)
+        if bone_w is not None and not (isinstance(bone_w, torch.Tensor) and bone_w.device == p1.device and bone_w.is_contiguous()
+                                       and bone_w.dtype == torch.float32 and tuple(bone_w.shape) == (E,)):
+            raise ValueError("BoneLossFn: bone_w must be None or %d contiguous fp32 weights on %s" % (E, p1.device))
+        if acc is not None and not (isinstance(acc, torch.Tensor) and acc.device == p1.device and acc.is_contiguous()
+                                    and acc.dtype == torch.float64 and tuple(acc.shape) == (3,)):
+            raise ValueError("BoneLossFn: acc must be None or 3 contiguous fp64 on %s" % (p1.device,))
+        p1, p2, joints = _c(p1), _c(p2), _c(joints.to(torch.float32))
+        out = torch.empty(3, dtype=torch.float32, device=p1.device)
+        resid = torch.empty((2, B, K, 2), dtype=torch.float32, device=p1.device)
+        inv_den = torch.empty((2, B, K), dtype=torch.float32, device=p1.device)
+        bone_resid = torch.empty((2, B, E, 2), dtype=torch.float32, device=p1.device)
+        gcoef = torch.empty((2, B, K, 2), dtype=torch.float32, device=p1.device)
+        host = (ctypes.c_int * (2 * E))(*[i for uv in table for i in uv])
+        rt.check(rt.lib().hupr_bone_loss_fwd_f32(rt.ptr(p1), rt.ptr(p2), rt.ptr(joints), B, K, H, float(stride), int(bool(snap)), host, E,
+                                                 rt.ptr(bone_w), float(BoneLossFn.eps), float(a0), float(a1), rt.ptr(out), rt.ptr(resid),
+                                                 rt.ptr(inv_den), rt.ptr(bone_resid), rt.ptr(gcoef), rt.ptr(acc), rt.stream()))
+        ctx.save_for_backward(resid, inv_den, gcoef, joints)
+        ctx.args = (B, K, E, H, float(stride), int(bool(snap)), float(a0), float(a1))
+        ctx.set_materialize_grads(False)
+        BoneLossFn.last_residual = bone_resid
+        b_heads = out[1:]
+        ctx.mark_non_differentiable(b_heads)
+        return out[0], b_heads
+
+    @staticmethod
+    def backward(ctx, g, _g_heads):
+        resid, inv_den, gcoef, joints = ctx.saved_tensors
+        B, K, E, H, stride, snap, a0, a1 = ctx.args
+        if g is None:
+            g = torch.zeros(1, dtype=torch.float32, device=resid.device)
+        dp1 = torch.empty((B, K, H, H), dtype=torch.float32, device=resid.device)
+        dp2 = torch.empty_like(dp1)
+        g = _c(g.reshape(1).to(torch.float32))
+        rt.check(rt.lib().hupr_bone_loss_bwd_f32(rt.ptr(resid), rt.ptr(inv_den), rt.ptr(gcoef), rt.ptr(joints), rt.ptr(g), B, K, E, H,
+                                                 stride, snap, a0, a1, rt.ptr(dp1), rt.ptr(dp2), rt.stream()))
+        return dp1, dp2, None, None, None, None, None, None, None, None
+
+
 _PATCH_CACHE = {}
 
 

@@ -2,6 +2,7 @@
 
 import math
 
+import numpy as np
 import torch
 
 from .. import functional as F_
@@ -65,6 +66,25 @@ def coord_loss_setting(cfg):
     raise ValueError("TRAINING.coordLoss must be -1 (off) or a finite weight > 0, got %r" % (v,))
 
 
+def bone_loss_setting(cfg):
+    """``TRAINING.boneLoss`` (not a key of the reference's YAML) -> None (absent or -1: off) or the weight mu, a finite number > 0,
+    of the bone-vector loss that computeLoss adds to the heat-map loss (``functional.BoneLossFn``).  Anything else (0, a negative,
+    nan, inf, a bool, a string, a list) raises here, where the config is read."""
+    v = getattr(getattr(cfg, "TRAINING", None), "boneLoss", -1)
+    if isinstance(v, (int, float)) and not isinstance(v, bool):
+        if v == -1:
+            return None
+        if math.isfinite(v) and v > 0:
+            return float(v)
+    raise ValueError("TRAINING.boneLoss must be -1 (off) or a finite weight > 0, got %r" % (v,))
+
+
+def bone_weights(joint_weights, bones):
+    """Per-bone weights from per-joint ones: w_e = sqrt(w_u w_v), taken in fp64 and stored as fp32, so a joint of weight zero
+    silences its bones and equal joint weights carry over unchanged."""
+    return [float(np.float32(math.sqrt(float(joint_weights[u]) * float(joint_weights[v])))) for u, v in bones]
+
+
 class LossComputer():
     def __init__(self, cfg, device):
         self.device = device
@@ -94,6 +114,18 @@ class LossComputer():
         self.coord_residual = None      # the last coordinate loss's (2, B, K, 2) residuals in heat-map pixels, on the device
         if self.coordLoss is not None:
             self.computeLoss = self._computeLossWithCoord       # without the key computeLoss stays the method below, untouched
+        # TRAINING.boneLoss: computeLoss adds mu times the bone-vector loss of both heads (csrc/bone_loss.hip) over the data set's
+        # skeleton, on top of whatever the keys above made of it; the accumulator {sum B_0, sum B_1, steps} lives on the device
+        self.boneLoss = bone_loss_setting(cfg)
+        self.bone_acc = self.bones = self._bone_w = None
+        self.bone_residual = None       # the last bone loss's (2, B, E, 2) bone residuals in heat-map pixels, on the device
+        if self.boneLoss is not None:
+            self.bones = F_.bone_table(None, self.numKeypoints)
+            self.bone_acc = torch.zeros(3, dtype=torch.float64, device=device)
+            if self.jointWeights is not None:
+                self._bone_w = torch.tensor(bone_weights(self.jointWeights, self.bones), dtype=torch.float32, device=device)
+            self._computeLossBeforeBone = self.computeLoss      # the method below, or the one with the coordinate term
+            self.computeLoss = self._computeLossWithBone
         self.alpha = 0.0
         self.beta = 1.0
 
@@ -160,3 +192,17 @@ class LossComputer():
                                         self.coord_acc if torch.is_grad_enabled() else None)
         self.coord_residual = F_.CoordLossFn.last_residual
         return loss + coord, loss2, pred2d, gt2d
+
+    def _computeLossWithBone(self, preds, gt, decode=True):
+        """computeLoss with ``TRAINING.boneLoss`` set: the same tuple, ``loss`` being the loss of the other keys plus mu times the
+        bone-vector term of both heads on every valid bone, whatever the mining keeps; ``loss2`` stays the second head's BCE.  The
+        head weights are those the BCE pair just got; with ``TRAINING.jointWeights`` a bone weighs sqrt(w_u w_v).  The accumulator
+        moves only where gradients are recorded."""
+        loss, loss2, pred2d, gt2d = self._computeLossBeforeBone(preds, gt, decode)
+        K, H, W = self.numKeypoints, self.height, self.width
+        w = (self.alpha, self.beta) if self.lossDecay != -1 else (1.0, 1.0)
+        bone, _ = F_.BoneLossFn.apply(preds[0].reshape(-1, K, H, W), preds[1].reshape(-1, K, H, W), gt.to(self.device),
+                                      self.imgSize / self.heatmapSize, self.targets_mode == "integer", self.bones, self._bone_w,
+                                      self.boneLoss * w[0], self.boneLoss * w[1], self.bone_acc if torch.is_grad_enabled() else None)
+        self.bone_residual = F_.BoneLossFn.last_residual
+        return loss + bone, loss2, pred2d, gt2d

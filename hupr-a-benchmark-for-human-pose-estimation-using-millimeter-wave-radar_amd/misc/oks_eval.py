@@ -196,3 +196,33 @@ def mean_position_error(gts, dts):
         return float("nan"), np.full(len(SIGMAS), np.nan), 0
     dist = np.stack(dist)
     return float(dist.mean()), dist.mean(axis=0), len(dist)
+
+
+def mean_bone_error(gts, dts, bones=None):
+    """Mean error of the bones' lengths in image pixels: over the matched images and the bones (u, v) of ``bones``, the mean of
+    | ||p_v - p_u|| - ||g_v - g_u|| |, p the detection's joints and g its ground truth's.  ``bones``: zero-based joint pairs; None =
+    the data set's skeleton (``datasets.base.SKELETON``, which is one-based, shifted to zero).  Records and matching as in
+    ``mean_position_error``.  A pose displaced as a whole has no bone error; a limb of the wrong length has.
+    -> (mean over all matched bones, per-bone means ndarray (E,), number of matched images); (nan, nan's, 0) without a match."""
+    if bones is None:
+        from ..datasets.base import SKELETON
+        bones = [(u - 1, v - 1) for u, v in SKELETON]
+    u, v = np.asarray(bones, dtype=np.int64).reshape(-1, 2).T
+    g_by = {}
+    for g in gts:
+        kp = np.asarray(g["keypoints"], dtype=np.float64)
+        xy = kp.reshape(-1, 3)[:, :2] if "area" in g else kp.reshape(-1, 2)
+        g_by.setdefault(int(g["image_id"]), xy)
+    err, seen = [], set()
+    for d in dts:
+        iid = int(d["image_id"])
+        if iid not in g_by or iid in seen:
+            continue
+        seen.add(iid)
+        xy = np.asarray(d["keypoints"], dtype=np.float64).reshape(-1, 3)[:, :2]
+        length = lambda q: np.sqrt(((q[v] - q[u]) ** 2).sum(axis=1))
+        err.append(np.abs(length(xy) - length(g_by[iid])))
+    if not err:
+        return float("nan"), np.full(len(u), np.nan), 0
+    err = np.stack(err)
+    return float(err.mean()), err.mean(axis=0), len(err)

@@ -171,6 +171,10 @@ SIGNATURES = {
     "hupr_coord_loss_fwd_f32": (c_int, [c_void_p] * 3 + [c_long, c_int, c_int, c_float, c_int, c_void_p, c_float, c_float, c_float]
                                 + [c_void_p] * 5),
     "hupr_coord_loss_bwd_f32": (c_int, [c_void_p] * 4 + [c_long, c_int, c_int, c_float, c_int, c_float, c_float] + [c_void_p] * 3),
+    # the bone-vector loss on both heads (csrc/bone_loss.hip); the bone table is host memory
+    "hupr_bone_loss_fwd_f32": (c_int, [c_void_p] * 3 + [c_long, c_int, c_int, c_float, c_int, ctypes.POINTER(c_int), c_int, c_void_p, c_float,
+                                                         c_float, c_float] + [c_void_p] * 7),
+    "hupr_bone_loss_bwd_f32": (c_int, [c_void_p] * 5 + [c_long, c_int, c_int, c_int, c_float, c_int, c_float, c_float] + [c_void_p] * 3),
     "hupr_gaussian_targets_f32": (c_int, [c_void_p] * 3 + [c_int, c_int, c_int, c_float, c_void_p]),
     "hupr_argmax_rows_f32": (c_int, [c_void_p, c_long, c_int, c_void_p, c_void_p, c_void_p]),
     # sub-pixel Gaussian targets (csrc/targets.hip)

@@ -380,7 +380,11 @@ class GradientBuckets:
             with torch.cuda.stream(self.comm_stream):
                 self.comm_stream.wait_event(ev)
                 for s in F_.side_streams_in_use(self.device):      # gradients of the side-stream branch (host-ordered earlier)
-                    self.comm_stream.wait_stream(s)
+                    # torch hands out streams from a pool of 32 per device in turn, so after 32 more torch.cuda.Stream() calls the
+                    # communication stream can BE the side stream.  A stream is ordered after itself; waiting for its own event
+                    # while it is a forked stream of a graph capture makes the end of that capture crash, so it is not asked to
+                    if s.cuda_stream != self.comm_stream.cuda_stream:
+                        self.comm_stream.wait_stream(s)
                 if self._accum_live:                               # earlier micro-batches of this optimiser step
                     b.flat_grad.add_(b.accum)
                 if self._timing is not None:

@@ -183,9 +183,9 @@ class TrainEngine:
         With ``TRAINING.targets: subpixel`` the joints must be a floating tensor: the static buffer keeps their dtype (an integer
         buffer would truncate every later batch), and a conversion to fp32 is a device kernel inside the captured region.
         The gradient guard (``TRAINING.gradClip``), the weight average (``TRAINING.emaDecay``), the mined loss with its counters
-        (``TRAINING.ohkm``, ``TRAINING.jointWeights``) and the coordinate loss with its accumulator (``TRAINING.coordLoss``) are
-        device-side and replay with the step; so is the augmentation (``TRAINING.aug*``): its plan is drawn by a launch from a counter in
-        device memory, so every replay draws a fresh plan.
+        (``TRAINING.ohkm``, ``TRAINING.jointWeights``) and the coordinate and bone-vector losses with their accumulators
+        (``TRAINING.coordLoss``, ``TRAINING.boneLoss``) are device-side and replay with the step; so is the augmentation
+        (``TRAINING.aug*``): its plan is drawn by a launch from a counter in device memory, so every replay draws a fresh plan.
         The ``warmup`` eager steps are real optimisation steps."""
         self._refuse_while_swapped("capture")
         tr = self.buckets.transport
@@ -270,6 +270,20 @@ class TrainEngine:
         replay it is the captured step's buffer)}; None otherwise.  The state lives on the device and replays with a captured step.
         Synchronises the device: per epoch, not per step."""
         return self.augment.stats() if self.augment is not None else None
+
+    def bone_stats(self):
+        """With ``TRAINING.boneLoss`` set: {"weight": mu, "sum": (sum of B_0, sum of B_1) over the training losses so far — B_h the
+        bone-vector loss of the first head and of the PRGCN head in heat-map pixels, before mu and the head weights —, "steps": how
+        many losses those sums hold, "residual": the last loss's (2, B, E, 2) ndarray of bone-vector errors (None before the first;
+        between ``capture()`` and the first replay it is the captured step's buffer, which no step has filled yet)}; None
+        otherwise.  As ``coord_stats``: the accumulator lives on the device, replays with a captured step and is not part of a
+        checkpoint.  Synchronises the device: per epoch, not per step."""
+        lc = self.lossComputer
+        if lc.boneLoss is None:
+            return None
+        acc = lc.bone_acc.cpu().numpy()
+        return {"weight": lc.boneLoss, "sum": (float(acc[0]), float(acc[1])), "steps": int(round(acc[2])),
+                "residual": lc.bone_residual.cpu().numpy() if lc.bone_residual is not None else None}
 
     # -- averaged weights (TRAINING.emaDecay) -----------------------------------------------------------------------------------
     def ema_stats(self):

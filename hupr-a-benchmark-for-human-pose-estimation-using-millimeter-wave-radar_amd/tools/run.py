@@ -16,7 +16,7 @@ import torch.utils.data as data
 from ..datasets import getDataset
 from ..datasets.dataset import HuPRRawADC, SequenceGroupedSampler
 from ..misc.losses import TARGETS
-from ..misc.oks_eval import evaluate_keypoints, mean_position_error
+from ..misc.oks_eval import evaluate_keypoints, mean_bone_error, mean_position_error
 from ..misc.plot import plotHumanPose
 from .augment import flip_setting
 from .base import BaseRunner
@@ -111,7 +111,8 @@ class Runner(BaseRunner):
         reference uses: the float joints of ``<phase>_gt.json`` (not the integer-truncated ``jointsGroup`` the loss sees by default;
         with ``TRAINING.targets: subpixel`` the loss sees the float joints too, ``loss_labels``).  When ``TRAINING.targets`` or
         ``TEST.decode`` is ``subpixel``, ``TEST.decode`` is ``integral``, or ``TRAINING.coordLoss`` or ``TEST.flip`` is set, one more line is printed, the mean per-joint position error in image pixels
-        (``mean_position_error``): AP's OKS thresholds are too coarse to show a sub-pixel change.
+        (``mean_position_error``): AP's OKS thresholds are too coarse to show a sub-pixel change.  ``TRAINING.boneLoss`` prints that
+        line and one more, the mean error of the bones' lengths in image pixels (``mean_bone_error``).
         ``--keypoints`` prints the per-joint APs (``evaluateEach``) instead of the summary line."""
         self.logger.clear(len(self.testLoader.dataset))
         savePreds, gts = [], []
@@ -158,8 +159,10 @@ class Runner(BaseRunner):
             print("  ".join("%s: %.3f" % (n, s) for n, s in zip(names, stats)))
             ap = float(stats[0])
             if ("subpixel" in (self.lossComputer.targets_mode, self.lossComputer.decode) or self.lossComputer.decode == "integral"
-                    or self.lossComputer.coordLoss is not None or self.flip):
+                    or self.lossComputer.coordLoss is not None or self.lossComputer.boneLoss is not None or self.flip):
                 print("MPJPE: %.3f px (n = %d)" % mean_position_error(gts, savePreds)[::2])
+            if self.lossComputer.boneLoss is not None:
+                print("Bone error: %.3f px (n = %d)" % mean_bone_error(gts, savePreds)[::2])
         if self.world > 1:
             box = [ap]
             dist.broadcast_object_list(box, src=0)
@@ -176,6 +179,7 @@ class Runner(BaseRunner):
             guard0 = self.engine.guard_stats()
             mined0 = self.engine.mining_stats()
             coord0 = self.engine.coord_stats()
+            bone0 = self.engine.bone_stats()
             aug0 = self.engine.augment_stats()
             self.logger.clear(len(self.trainLoader.dataset))
             if hasattr(self.trainLoader.sampler, "set_epoch"):
@@ -212,6 +216,13 @@ class Runner(BaseRunner):
                 print("==========>Coordinate loss in epoch %d: first head %.4f  PRGCN head %.4f heat-map px (weight %g, %d steps)" % (
                     epoch, (coord["sum"][0] - coord0["sum"][0]) / max(n, 1), (coord["sum"][1] - coord0["sum"][1]) / max(n, 1),
                     coord["weight"], n))
+            if bone0 is not None and self.rank == 0:
+                # TRAINING.boneLoss: this epoch's mean of B_h, the weighted per-axis mean error of each head's bone vectors
+                bone = self.engine.bone_stats()
+                n = bone["steps"] - bone0["steps"]
+                print("==========>Bone loss in epoch %d: first head %.4f  PRGCN head %.4f heat-map px (weight %g, %d steps)" % (
+                    epoch, (bone["sum"][0] - bone0["sum"][0]) / max(n, 1), (bone["sum"][1] - bone0["sum"][1]) / max(n, 1),
+                    bone["weight"], n))
             if aug0 is not None and self.rank == 0:
                 # TRAINING.aug*: what this epoch's plans drew (this rank's; the other ranks draw their own)
                 st = self.engine.augment_stats()

@@ -628,6 +628,46 @@ int hupr_coord_loss_fwd_f32(const float* p1, const float* p2, const float* joint
                             double* acc_or_null, hupr_stream_t stream);
 int hupr_coord_loss_bwd_f32(const float* resid, const float* scale, const float* joints_xy, const float* grad_loss, long B, int K, int H,
                             float stride, int snap, float a0, float a1, float* dp1, float* dp2, hupr_stream_t stream);
+/* Bone-vector loss on both heads (Sun et al., "Compositional Human Pose Regression", ICCV 2017), csrc/bone_loss.hip: an L1 on the
+ * error of the vector between the mass centroids of the two planes at the ends of every bone of a skeleton table, in heat-map pixels.
+ * New, no reference counterpart.  Two launches forward, one backward, no workspace, no atomics, no scratch: every output is
+ * bit-identical from run to run, and equal planes with equal joints give equal bits.  p1, p2, joints_xy, stride, snap, eps: as in
+ * hupr_coord_loss_fwd_f32, with its Position and Validity; a joint is valid iff both axes are valid.
+ *   Residual     per (h, b, j): S = sum p, N = sum p (x - a_x, y - a_y), den = S + eps, r = N / den: hupr_coord_loss_fwd_f32's
+ *                residual by the same arithmetic in the same summation order (one body, csrc/coord_plane.h); for equal inputs and
+ *                eps the bits equal that entry's resid.  inv_den = 1 / den.  An invalid joint gives r = 0 and inv_den = 0, and its
+ *                plane is not read.  A NaN cell in a valid plane gives a NaN r and inv_den; it is not masked.
+ *   Bones        bones_host: a HOST table of 2 E ints, bone e = (u_e, v_e); 1 <= E <= 32, every index in [0, K), u_e != v_e.  It is
+ *                checked on the host and copied into the kernel's arguments.  A bone is valid iff both its joints are valid.
+ *   Bone error   d[h,b,e] = r[h,b,v_e] - r[h,b,u_e], two fp32 subtractions; exactly 0 for an invalid bone.  Up to the eps damping
+ *                this is (c_v - c_u) - (a_v - a_u), the error of the predicted bone vector: a pose whose every joint is displaced by
+ *                the same offset costs nothing.
+ *   Head loss    B_h = (1 / (2 B E)) sum_b sum_e w_e (|d_x| + |d_y|), w = bone_w_or_null (E floats on the device) or all ones when
+ *                it is null: a fixed denominator, invalid bones count as zeros; summed in fp64 in an order fixed by (B, E).
+ *   Coefficient  gcoef[h,b,j] = sum_{e: v_e = j} w_e sgn(d_e) - sum_{e: u_e = j} w_e sgn(d_e) per axis, accumulated in fp32 in bone-
+ *                index order over the valid bones; sgn(0) = 0 and a NaN d stays a NaN: nothing is masked, so a NaN cell reaches both
+ *                of the bone's joints.  A weight of zero is plain arithmetic, not a mask.
+ *   Outputs      loss3 = {a0 B_0 + a1 B_1, B_0, B_1}, the two products and the sum rounded separately as in
+ *                hupr_coord_loss_fwd_f32; resid (2, B, K, 2); inv_den (2, B, K); bone_resid (2, B, E, 2) receives d; gcoef
+ *                (2, B, K, 2).
+ *   Accumulator  with acc_or_null non-null (3 doubles): acc[0] += B_0, acc[1] += B_1, acc[2] += 1.  Plain adds by one workgroup;
+ *                the caller zeroes the array once.
+ *   Backward     dp_h[b,j,y,x] = f (gcoef_x ((x - a_x) - r_x) + gcoef_y ((y - a_y) - r_y)), f = (g a_h) inv_den[h,b,j] / (2 B E).
+ *                It reads resid, inv_den, gcoef, the joints and g, never the maps: a store-only kernel.  Every cell of dp1 and dp2 is
+ *                written; a plane whose f is zero, or whose two coefficients are both zero, is written as zeros; a NaN factor or
+ *                coefficient is not zero and fills its plane.  No gradient flows to the joints.
+ * Launches: the plane pass of hupr_coord_loss_fwd_f32 (one 256-thread workgroup per plane; 16-byte loads and stores where
+ * H % 4 == 0 and the maps are 16-byte aligned, 4-byte ones otherwise), then one workgroup that writes bone_resid, gcoef and loss3 and
+ * moves acc; each gcoef thread recomputes the d of its incident bones from resid, which gives the same bits.
+ * Both return -1 (HUPR_ERR_ARG) before any launch for a null pointer (the two _or_null ones excepted), B < 1, K outside [1, 64],
+ * H outside [1, 4096], B * K * H * H beyond the 64-bit index arithmetic, stride not finite or not positive, E outside [1, 32], and the
+ * forward for eps not finite or not positive and for a bone with an index outside [0, K) or with u == v. */
+int hupr_bone_loss_fwd_f32(const float* p1, const float* p2, const float* joints_xy, long B, int K, int H, float stride, int snap,
+                           const int* bones_host, int E, const float* bone_w_or_null, float eps, float a0, float a1, float* loss3,
+                           float* resid, float* inv_den, float* bone_resid, float* gcoef, double* acc_or_null, hupr_stream_t stream);
+int hupr_bone_loss_bwd_f32(const float* resid, const float* inv_den, const float* gcoef, const float* joints_xy, const float* grad_loss,
+                           long B, int K, int E, int H, float stride, int snap, float a0, float a1, float* dp1, float* dp2,
+                           hupr_stream_t stream);
 int hupr_gaussian_targets_f32(const long long* joints, const float* patch, float* t, int BK, int H, int rad,
                               float stride, hupr_stream_t stream);
 int hupr_argmax_rows_f32(const float* p, long rows, int n, int* idx, float* maxval, hupr_stream_t stream);
