@@ -493,8 +493,42 @@ __device__ __forceinline__ AngleOut angle_cell(const v2f* __restrict__ cell, con
 // workgroup give the mean and the unbiased variance of all sixteen planes.
 // 8 workgroups per CU (<= 64 registers per lane): the loader grids — 8 planes x 256 sensor-frames = 2 048 workgroups — are then ONE
 // round of the 256 CUs instead of 1.14 (70 registers: 7 per CU, a second round of 256 workgroups at one per CU)
-template <int MODE>
-__global__ __launch_bounds__(256) void hupr_k_angle(const float2* __restrict__ rd, void* __restrict__ out_) {
+//
+// TDM (opt-in, hupr_fft_chain_tdm; include/hupr.h "Doppler phase compensation"): the three transmitters fire one after another, so a
+// mover's phase has turned by 2 pi d k / 192 between the loop's start and slot k of its chirp.  The staging loop multiplies the
+// range-Doppler value of (v, i, range) by kTdmFactor[k(v)][i] = exp(-2 pi j (i - 8) k / 192); everything behind it — the closed-form
+// Normalize sums, the pruned DFT, all four output modes — then sees compensated values.  A wave stages whole antennas (v = t >> 6),
+// so k and the factor are uniform over a wave; a factor that is exactly (1, 0) (k = 0 or i = 8) is not multiplied at all, which
+// keeps those values' bits whatever they hold (signed zeros of the exact zero-Doppler mode included).  `swapped`: one byte per
+// `frames_per_flag` sensor-frames, read at launch time (a replayed graph follows the table's current content) — the ADC mirror of
+// tools/augment.py exchanged transmitters 0 and 2, and with them their slots.
+struct TdmSwapTable {               // sensor-frame sf is swapped when swapped != null, sf / frames_per_flag < n_swapped and that byte != 0
+    const unsigned char* swapped;
+    int n_swapped, frames_per_flag;
+};
+__device__ __forceinline__ TdmSwapTable tdm_swap_table(TdmSwapTable t) { return t; }      // the one element of the kernel's pack
+// The 48 factors: fp32 roundings of the fp64 cosine and sine, row k, column i (tests/test_tdm_cpu.py recomputes them).
+__constant__ float2 kTdmFactor[3 * 16] = {
+    // k = 0
+    {1.f, 0.f}, {1.f, 0.f}, {1.f, 0.f}, {1.f, 0.f}, {1.f, 0.f}, {1.f, 0.f}, {1.f, 0.f}, {1.f, 0.f},
+    {1.f, 0.f}, {1.f, 0.f}, {1.f, 0.f}, {1.f, 0.f}, {1.f, 0.f}, {1.f, 0.f}, {1.f, 0.f}, {1.f, 0.f},
+    // k = 1
+    {0.965925813f, 0.258819044f}, {0.973876953f, 0.227076262f}, {0.980785251f, 0.195090324f}, {0.986643314f, 0.162895471f},
+    {0.991444886f, 0.130526185f}, {0.99518472f, 0.0980171412f}, {0.997858942f, 0.0654031262f}, {0.999464571f, 0.0327190831f},
+    {1.f, 0.f}, {0.999464571f, -0.0327190831f}, {0.997858942f, -0.0654031262f}, {0.99518472f, -0.0980171412f},
+    {0.991444886f, -0.130526185f}, {0.986643314f, -0.162895471f}, {0.980785251f, -0.195090324f}, {0.973876953f, -0.227076262f},
+    // k = 2
+    {0.866025388f, 0.5f}, {0.896872759f, 0.442288697f}, {0.923879504f, 0.382683426f}, {0.94693011f, 0.321439475f},
+    {0.965925813f, 0.258819044f}, {0.980785251f, 0.195090324f}, {0.991444886f, 0.130526185f}, {0.997858942f, 0.0654031262f},
+    {1.f, 0.f}, {0.997858942f, -0.0654031262f}, {0.991444886f, -0.130526185f}, {0.980785251f, -0.195090324f},
+    {0.965925813f, -0.258819044f}, {0.94693011f, -0.321439475f}, {0.923879504f, -0.382683426f}, {0.896872759f, -0.442288697f},
+};
+
+// TDM = false is the kernel every parity path launches, (rd, out) its whole argument list; the compensated form carries the swap
+// table behind them: hupr_k_angle<MODE, true, TdmSwapTable>(rd, out, table).
+template <int MODE, bool TDM = false, typename... SwapTable>
+__global__ __launch_bounds__(256) void hupr_k_angle(const float2* __restrict__ rd, void* __restrict__ out_, SwapTable... swap_table) {
+    static_assert(sizeof...(SwapTable) == (TDM ? 1 : 0), "hupr_k_angle: one TdmSwapTable, with TDM only");
     constexpr bool LOADER = MODE == 1 || MODE == 3;
     __shared__ v2f cells[kRange * kVant];      // RD for this (sf, i): 64 range bins x 12 antennas
     __shared__ v2f tw64[64];
@@ -507,9 +541,25 @@ __global__ __launch_bounds__(256) void hupr_k_angle(const float2* __restrict__ r
     const int i = LOADER ? pl + 4 : pl;         // loader keeps Doppler indices 4..11 (dataset.py:145)
 
     // RD[sf][antenna][doppler][range] -> cells[range][antenna]: twelve 512-byte runs
-    for (int t = tid; t < kRange * kVant; t += 256) {
-        const int v = t >> 6, r = t & 63;
-        cells[r * kVant + v] = reinterpret_cast<const v2f*>(rd)[(((size_t)sf * kVant + v) * kDop + i) * kRange + r];
+    if constexpr (TDM) {
+        const TdmSwapTable tb = tdm_swap_table(swap_table...);
+        const int g = sf / tb.frames_per_flag;
+        const bool sw = tb.swapped != nullptr && g < tb.n_swapped && tb.swapped[g] != 0;
+        for (int t = tid; t < kRange * kVant; t += 256) {
+            const int v = t >> 6, r = t & 63;
+            const int k = v >= 8 ? 1 : ((v < 4) != sw ? 0 : 2);      // slot of antenna v's transmitter (TX0, TX2 exchanged when swapped)
+            v2f x = reinterpret_cast<const v2f*>(rd)[(((size_t)sf * kVant + v) * kDop + i) * kRange + r];
+            if (k != 0 && i != 8) {
+                const float2 w = kTdmFactor[k * 16 + i];
+                x = pk_cmul_v(x, (v2f){w.x, w.y});
+            }
+            cells[r * kVant + v] = x;
+        }
+    } else {
+        for (int t = tid; t < kRange * kVant; t += 256) {
+            const int v = t >> 6, r = t & 63;
+            cells[r * kVant + v] = reinterpret_cast<const v2f*>(rd)[(((size_t)sf * kVant + v) * kDop + i) * kRange + r];
+        }
     }
     if (tid < 64) tw64[tid] = reinterpret_cast<const v2f*>(kTw256)[4 * tid];
     __syncthreads();
@@ -742,7 +792,7 @@ extern "C" size_t hupr_fft_chain_ws_bytes(int n_sf) {
 // bit 1 = the three antennas of a receiver back to back on one XCD (measured neutral, off).
 
 static int fft_chain_common(const int16_t* adc_iq, int n_sf, void* out, void* ws, size_t ws_bytes,
-                            hupr_stream_t stream, bool loader, int flags = 0, bool means = false) {
+                            hupr_stream_t stream, bool loader, int flags = 0, bool means = false, const TdmSwapTable* tdm = nullptr) {
     HUPR_REQUIRE((flags & ~(HUPR_FFT_HANN_RANGE | HUPR_FFT_HANN_DOPPLER | HUPR_FFT_MAGNITUDE | HUPR_FFT_ZERO_DOPPLER_EXACT |
                             HUPR_FFT_RANGE_FIRST)) == 0, "hupr_fft_chain: flags=0x%x", flags);
     HUPR_REQUIRE(!((flags & HUPR_FFT_ZERO_DOPPLER_EXACT) && (flags & HUPR_FFT_RANGE_FIRST)),
@@ -784,6 +834,17 @@ static int fft_chain_common(const int16_t* adc_iq, int n_sf, void* out, void* ws
 #undef HUPR_DR
     }
     HUPR_LAUNCH_OK("hupr_k_range_doppler");
+    if (tdm) {
+#define HUPR_ANGLE_TDM(M_, P_) \
+    HUPR_LAUNCH((hupr_k_angle<M_, true, TdmSwapTable>), dim3(n_sf * P_), dim3(256), 0, s, rd, out, *tdm)
+        if (loader && means) HUPR_ANGLE_TDM(3, 8);
+        else if (loader) HUPR_ANGLE_TDM(1, 8);
+        else if (flags & HUPR_FFT_MAGNITUDE) HUPR_ANGLE_TDM(2, 16);
+        else HUPR_ANGLE_TDM(0, 16);
+#undef HUPR_ANGLE_TDM
+        HUPR_LAUNCH_OK("hupr_k_angle<TDM>");
+        return HUPR_OK;
+    }
     if (loader && means)
         HUPR_LAUNCH(hupr_k_angle<3>, dim3(n_sf * 8), dim3(256), 0, s, rd, out);
     else if (loader)
@@ -815,6 +876,17 @@ extern "C" int hupr_fft_chain_opts(const int16_t* adc_iq, int n_sf, void* out, i
                                    hupr_stream_t stream) {
     HUPR_REQUIRE(loader >= 0 && loader <= 2, "hupr_fft_chain_opts: loader=%d", loader);
     return fft_chain_common(adc_iq, n_sf, out, ws, ws_bytes, stream, loader != 0, flags, loader == 2);
+}
+
+extern "C" int hupr_fft_chain_tdm(const int16_t* adc_iq, int n_sf, void* out, int flags, int loader,
+                                  const unsigned char* tx_swapped_or_null, int n_swapped, int frames_per_flag, void* ws, size_t ws_bytes,
+                                  hupr_stream_t stream) {
+    HUPR_REQUIRE(loader >= 0 && loader <= 2, "hupr_fft_chain_tdm: loader=%d", loader);
+    HUPR_REQUIRE(frames_per_flag >= 1, "hupr_fft_chain_tdm: frames_per_flag=%d", frames_per_flag);
+    HUPR_REQUIRE(n_swapped >= 0, "hupr_fft_chain_tdm: n_swapped=%d", n_swapped);
+    HUPR_REQUIRE(!(tx_swapped_or_null && n_swapped == 0), "hupr_fft_chain_tdm: a swap table with n_swapped=0");
+    const TdmSwapTable tdm = {tx_swapped_or_null, n_swapped, frames_per_flag};
+    return fft_chain_common(adc_iq, n_sf, out, ws, ws_bytes, stream, loader != 0, flags, loader == 2, &tdm);
 }
 
 extern "C" int hupr_loader_normalize_c64(const void* cube_c64, int n_sf, float* out, hupr_stream_t stream) {

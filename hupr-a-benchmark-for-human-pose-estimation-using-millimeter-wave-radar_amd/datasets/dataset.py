@@ -26,6 +26,7 @@ import torch.utils.data as data
 from .. import synth
 from ..misc.oks_eval import evaluate_keypoints
 from ..preprocessing.process_iwr1843 import dca1000_frames, loader_normalize
+from ..tools.augment import TDM_NEEDS_RANGE_DOPPLER, tdm_setting
 from .base import generateGTAnnot
 
 
@@ -57,14 +58,15 @@ class SequenceFFTCache:
     the two (G, 8, 2, 64, 64, 8) fp32 network inputs of sample ``index`` (position inside the sequence), with the
     reference's edge clamping (``window_indices``).  Memory: 2.1 MB per cached sensor-frame (600 frames x 2 = 2.5 GB)."""
 
-    def __init__(self, adc_hori, adc_vert, num_group_frames):
+    def __init__(self, adc_hori, adc_vert, num_group_frames, tdm_compensation=False):
         from ..preprocessing.process_iwr1843 import fft_chain_loader
         if adc_hori.shape != adc_vert.shape:
             raise ValueError("hori / vert sequences must have the same number of frames")
         self.duration = adc_hori.shape[0]
         self.G = num_group_frames
-        self.hori = fft_chain_loader(adc_hori)          # (duration, 8, 2, 64, 64, 8)
-        self.vert = fft_chain_loader(adc_vert)
+        kw = {"tdm_compensation": True} if tdm_compensation else {}      # DATASET.tdmCompensation (tools/augment.py: tdm_setting)
+        self.hori = fft_chain_loader(adc_hori, **kw)    # (duration, 8, 2, 64, 64, 8)
+        self.vert = fft_chain_loader(adc_vert, **kw)
 
     def window(self, index):
         idx = torch.tensor(window_indices(index, self.duration, self.G), device=self.hori.device)
@@ -173,6 +175,8 @@ class HuPR3D_horivert(_AnnotatedHuPR):
     """Real-data reader (reference layout).  Returns network-ready tensors on ``device``."""
 
     def __init__(self, phase, cfg, args, random=True, device="cuda"):
+        if tdm_setting(cfg):
+            raise RuntimeError(TDM_NEEDS_RANGE_DOPPLER)
         super().__init__(phase, cfg, args, random)
         self.device = device
         self.VRDAEPaths_hori = [os.path.join(self.dirRoot, "single_%d/hori/%09d.npy" % (it["seq"], it["frame"])) for it in self.items]
@@ -200,6 +204,7 @@ class HuPRRawADC(_AnnotatedHuPR):
         super().__init__(phase, cfg, args, random)
         self.device = device
         self.rawRoot = getattr(cfg.DATASET, "rawDir", None) or self.dirRoot
+        self.tdm = tdm_setting(cfg)
         self.cache_sequences = cache_sequences
         self._cache = OrderedDict()
         self._seq_start = {}
@@ -214,7 +219,7 @@ class HuPRRawADC(_AnnotatedHuPR):
                 path = os.path.join(self.rawRoot, "single_%d" % seq, sensor, "adc_data.bin")
                 raw = torch.from_numpy(np.fromfile(path, dtype=np.int16)).to(self.device)
                 streams.append(dca1000_frames(raw))            # (frames, 4, 192, 256, 2) int16
-            c = SequenceFFTCache(streams[0], streams[1], self.G)
+            c = SequenceFFTCache(streams[0], streams[1], self.G, tdm_compensation=self.tdm)
             self._cache[seq] = c
             while len(self._cache) > self.cache_sequences:
                 self._cache.popitem(last=False)

@@ -56,11 +56,59 @@ def _flags(window, magnitude, zero_doppler=None):
     return table[window] | (MAGNITUDE if magnitude else 0) | ZERO_DOPPLER_MODES[zd]
 
 
-def fft_chain(adc_iq, ws=None, window=None, magnitude=False, zero_doppler=None):
+# Doppler phase compensation for the TDM-MIMO virtual array (include/hupr.h, hupr_fft_chain_tdm).  Slot of the transmitter behind
+# virtual antenna v in the chain's workspace order: TX0 fires first (v = 0..3), TX1 — the elevated row, v = 8..11 — second, TX2
+# (v = 4..7) third; the ADC mirror of tools/augment.py exchanges TX0 and TX2 and with them their slots ("swapped").
+TDM_SLOTS = (0, 0, 0, 0, 2, 2, 2, 2, 1, 1, 1, 1)
+TDM_SLOTS_SWAPPED = (2, 2, 2, 2, 0, 0, 0, 0, 1, 1, 1, 1)
+
+
+def tdm_phase_table(swapped=False):
+    """The compensation factors ``exp(-2 pi j d k(v) / 192)`` as a complex128 ``(12 virtual antennas, 16 kept Doppler indices)``
+    array in fp64: ``d = i - 8`` the signed Doppler bin, ``k(v)`` the slot of the antenna's transmitter (``TDM_SLOTS``, or
+    ``TDM_SLOTS_SWAPPED`` for a mirrored sensor-frame).  A factor with ``d == 0`` or ``k == 0`` is exactly 1.  The device multiplies by
+    the fp32 roundings of these cosines and sines (csrc/fft_chain.hip, ``kTdmFactor``).  A Doppler bin aliased past +-32 gets the
+    wrong sign, as in every TDM-MIMO pipeline: the compensation knows the bin, not the velocity."""
+    k = np.asarray(TDM_SLOTS_SWAPPED if swapped else TDM_SLOTS, dtype=np.int64)[:, None]
+    d = np.arange(16, dtype=np.int64)[None, :] - 8
+    ang = 2.0 * np.pi * (d * k).astype(np.float64) / 192.0
+    return np.cos(ang) - 1j * np.sin(ang)
+
+
+def _tdm_table(tx_swapped, frames_per_flag, n):
+    """-> (pointer or None, n_swapped, frames_per_flag) of hupr_fft_chain_tdm for ``n`` sensor-frames."""
+    if not isinstance(frames_per_flag, int) or isinstance(frames_per_flag, bool) or frames_per_flag < 1:
+        raise ValueError("frames_per_flag must be a positive int, got %r" % (frames_per_flag,))
+    if tx_swapped is None:
+        return None, 0, frames_per_flag
+    if tx_swapped.dtype != torch.uint8 or tx_swapped.dim() != 1 or tx_swapped.numel() * frames_per_flag < n or tx_swapped.numel() == 0:
+        raise ValueError("tx_swapped must be a uint8 (ceil(n / frames_per_flag),) device tensor, got %s %r for %d frames, %d per flag"
+                         % (tx_swapped.dtype, tuple(tx_swapped.shape), n, frames_per_flag))
+    return rt.ptr(tx_swapped), tx_swapped.numel(), frames_per_flag
+
+
+def _launch_tdm(adc_iq, n, out, flags, loader, tx_swapped, frames_per_flag, ws, nbytes):
+    tbl, n_swapped, fpf = _tdm_table(tx_swapped, frames_per_flag, n)
+    rt.check(rt.lib().hupr_fft_chain_tdm(rt.ptr(adc_iq), n, rt.ptr(out), flags, loader, tbl, n_swapped, fpf, rt.ptr(ws), nbytes,
+                                         rt.stream()))
+
+
+def _refuse_swap_without_tdm(tdm_compensation, tx_swapped):
+    if tx_swapped is not None and not tdm_compensation:
+        raise ValueError("tx_swapped only means something with tdm_compensation=True")
+
+
+def fft_chain(adc_iq, ws=None, window=None, magnitude=False, zero_doppler=None, tdm_compensation=False, tx_swapped=None,
+              frames_per_flag=1):
     """adc_iq: int16 GPU tensor (n,4,192,256,2) -> complex64 GPU tensor (n,16,64,64,8).
     Opt-in (defaults = the reference: no window, complex output): ``window="hann"`` applies np.hanning windows over the
-    range samples and the chirp loops, ``magnitude=True`` returns |X| as fp32.  ``zero_doppler``: see ZERO_DOPPLER_MODES."""
+    range samples and the chirp loops, ``magnitude=True`` returns |X| as fp32.  ``zero_doppler``: see ZERO_DOPPLER_MODES.
+    ``tdm_compensation=True`` multiplies the range-Doppler map by ``tdm_phase_table`` in front of the angle transform
+    (hupr_fft_chain_tdm); ``tx_swapped``: uint8 device tensor, one flag per ``frames_per_flag`` sensor-frames, non-zero = that
+    group's transmitters 0 and 2 were exchanged (``tools.augment.adc_mirror``); None = none.  Reference-trained weights expect the
+    default, off."""
     _check_adc(adc_iq)
+    _refuse_swap_without_tdm(tdm_compensation, tx_swapped)
     n = adc_iq.shape[0]
     flags = _flags(window, magnitude, zero_doppler)
     out = torch.empty((n, 16, 64, 64, 8), dtype=torch.float32 if magnitude else torch.complex64, device=adc_iq.device)
@@ -68,18 +116,22 @@ def fft_chain(adc_iq, ws=None, window=None, magnitude=False, zero_doppler=None):
         ws, nbytes = _workspace(n, adc_iq.device)
     else:
         nbytes = ws.numel() * ws.element_size()
-    if flags == 0:
+    if tdm_compensation:
+        _launch_tdm(adc_iq, n, out, flags, 0, tx_swapped, frames_per_flag, ws, nbytes)
+    elif flags == 0:
         rt.check(rt.lib().hupr_fft_chain_c64(rt.ptr(adc_iq), n, rt.ptr(out), rt.ptr(ws), nbytes, rt.stream()))
     else:
         rt.check(rt.lib().hupr_fft_chain_opts(rt.ptr(adc_iq), n, rt.ptr(out), flags, 0, rt.ptr(ws), nbytes, rt.stream()))
     return out
 
 
-def fft_chain_loader(adc_iq, ws=None, out=None, window=None, zero_doppler=None):
+def fft_chain_loader(adc_iq, ws=None, out=None, window=None, zero_doppler=None, tdm_compensation=False, tx_swapped=None,
+                     frames_per_flag=1):
     """adc_iq: int16 GPU tensor (n,4,192,256,2) -> fp32 GPU tensor (n, 8, 2, 64, 64, 8):
-    Doppler bins 4..11, re/im split, per-elevation Normalize (datasets glue fused in).  ``window`` / ``zero_doppler``: see
-    fft_chain."""
+    Doppler bins 4..11, re/im split, per-elevation Normalize (datasets glue fused in).  ``window`` / ``zero_doppler`` /
+    ``tdm_compensation`` / ``tx_swapped`` / ``frames_per_flag``: see fft_chain (the statistics are those of the compensated values)."""
     _check_adc(adc_iq)
+    _refuse_swap_without_tdm(tdm_compensation, tx_swapped)
     n = adc_iq.shape[0]
     if out is None:
         out = torch.empty((n, 8, 2, 64, 64, 8), dtype=torch.float32, device=adc_iq.device)
@@ -88,18 +140,22 @@ def fft_chain_loader(adc_iq, ws=None, out=None, window=None, zero_doppler=None):
     else:
         nbytes = ws.numel() * ws.element_size()
     flags = _flags(window, False, zero_doppler)
-    if flags == 0:
+    if tdm_compensation:
+        _launch_tdm(adc_iq, n, out, flags, 1, tx_swapped, frames_per_flag, ws, nbytes)
+    elif flags == 0:
         rt.check(rt.lib().hupr_fft_chain_loader_f32(rt.ptr(adc_iq), n, rt.ptr(out), rt.ptr(ws), nbytes, rt.stream()))
     else:
         rt.check(rt.lib().hupr_fft_chain_opts(rt.ptr(adc_iq), n, rt.ptr(out), flags, 1, rt.ptr(ws), nbytes, rt.stream()))
     return out
 
 
-def fft_chain_loader_means(adc_iq, ws=None, zero_doppler=None):
+def fft_chain_loader_means(adc_iq, ws=None, zero_doppler=None, tdm_compensation=False, tx_swapped=None, frames_per_flag=1):
     """adc_iq: int16 GPU tensor (n,4,192,256,2) -> fp32 GPU tensor (n, 16, 64, 64): the loader tensor of ``fft_chain_loader``
     averaged over its elevation axis, plane index 2 f + c — what ``HuPRNet.forward`` computes first (models/networks.py:26-27).
-    The fused training loader hands these planes to the model instead of the 8x larger (n,8,2,64,64,8) tensor."""
+    The fused training loader hands these planes to the model instead of the 8x larger (n,8,2,64,64,8) tensor.
+    ``tdm_compensation`` / ``tx_swapped`` / ``frames_per_flag``: see fft_chain."""
     _check_adc(adc_iq)
+    _refuse_swap_without_tdm(tdm_compensation, tx_swapped)
     n = adc_iq.shape[0]
     out = torch.empty((n, 16, 64, 64), dtype=torch.float32, device=adc_iq.device)
     if ws is None:
@@ -107,7 +163,9 @@ def fft_chain_loader_means(adc_iq, ws=None, zero_doppler=None):
     else:
         nbytes = ws.numel() * ws.element_size()
     flags = _flags(None, False, zero_doppler)
-    if flags == 0:
+    if tdm_compensation:
+        _launch_tdm(adc_iq, n, out, flags, 2, tx_swapped, frames_per_flag, ws, nbytes)
+    elif flags == 0:
         rt.check(rt.lib().hupr_fft_chain_loader_means_f32(rt.ptr(adc_iq), n, rt.ptr(out), rt.ptr(ws), nbytes, rt.stream()))
     else:
         rt.check(rt.lib().hupr_fft_chain_opts(rt.ptr(adc_iq), n, rt.ptr(out), flags, 2, rt.ptr(ws), nbytes, rt.stream()))
@@ -173,12 +231,13 @@ class RadarObject:
         """``<dirName>/<idxFrame:09d>.npy`` (reference :180-182)."""
         np.save(os.path.join(dirName, "%09d.npy" % idxFrame), matrix)
 
-    def processRadarDataHoriVert(self, frames_per_call=64):
+    def processRadarDataHoriVert(self, frames_per_call=64, tdm_compensation=False):
         """The reference's offline driver (:184-196): every sequence's two captures -> one complex128 ``(16,64,64,8)`` cube per
         frame and sensor under ``<saveDir>/{hori,vert}/%09d.npy``.  Here a capture goes to the GPU once, is de-interleaved there
         and transformed ``frames_per_call`` frames at a time (the reference parses 115 200 chirps and runs ~200 000 tiny FFT calls
         per frame in Python).  Training does not need these files: ``datasets.HuPRRawADC`` feeds the network straight from
-        the captures."""
+        the captures.  ``tdm_compensation=True`` writes Doppler-compensated cubes (see ``fft_chain``); a dataset that reads them runs with
+        ``DATASET.tdmCompensation`` off, since the cubes already are."""
         for names, save_dir in zip(self.radarDataFileNameGroup, self.saveDirNameGroup):
             for sensor, name in zip(("hori", "vert"), names):
                 out_dir = os.path.join(save_dir, sensor)
@@ -187,14 +246,15 @@ class RadarObject:
                 frames = dca1000_frames(torch.from_numpy(raw).to(self.device))
                 n = min(frames.shape[0], self.numFrame)
                 for f0 in range(0, n, frames_per_call):
-                    cubes = fft_chain(frames[f0:min(n, f0 + frames_per_call)]).cpu().numpy().astype(np.complex128)
+                    cubes = fft_chain(frames[f0:min(n, f0 + frames_per_call)], tdm_compensation=tdm_compensation).cpu().numpy().astype(np.complex128)
                     for k, cube in enumerate(cubes):
                         self.saveRadarData(cube, out_dir, f0 + k)
                 print("%s, finished %d frames" % (name, n))
 
-    def generateHeatmap(self, frame, window=None, magnitude=False):
+    def generateHeatmap(self, frame, window=None, magnitude=False, tdm_compensation=False):
         """frame: complex ndarray (4,192,256) -> complex128 ndarray (16,64,64,8) (float64 with ``magnitude``).
-        ``window`` / ``magnitude`` are opt-in extras (see ``fft_chain``); the defaults are the reference's arithmetic."""
+        ``window`` / ``magnitude`` / ``tdm_compensation`` are opt-in extras (see ``fft_chain``); the defaults are the reference's
+        arithmetic."""
         frame = np.asarray(frame)
         if frame.shape != (self.numRX, self.numChirp, self.numADCSamples):
             raise ValueError("frame must be (4,192,256), got %r" % (frame.shape,))
@@ -202,5 +262,5 @@ class RadarObject:
         if not np.all(np.abs(iq) <= 32767) or not np.array_equal(iq, np.rint(iq)):
             raise ValueError("generateHeatmap expects integer-valued 16-bit ADC samples")
         dev = torch.from_numpy(iq.astype(np.int16)[None]).to(self.device)
-        out = fft_chain(dev, window=window, magnitude=magnitude)
+        out = fft_chain(dev, window=window, magnitude=magnitude, tdm_compensation=tdm_compensation)
         return out[0].cpu().numpy().astype(np.float64 if magnitude else np.complex128)

@@ -92,14 +92,8 @@ def adc_cube_complex(iq):
     return iq[..., 0].astype(np.float64) + 1j * iq[..., 1].astype(np.float64)
 
 
-def point_target_cube(targets, noise=0.0, seed=0):
-    """Known-answer scene: sum of complex exponentials over (sample, chirp, virtual antenna).
-
-    ``targets`` = list of dict(range_bin, doppler_bin, az_bin, el_bin, amp).  Phase
-    progressions follow the reference's demux: chirp c = 3*cc + tx; tx0 -> az
-    antennas 0..3, tx2 -> az antennas 4..7, tx1 -> elevation row (az offset 2).
-    Returns int16 I/Q ``(1, 4, 192, 256, 2)``.
-    """
+def point_target_scene(targets, noise=0.0, seed=0, tdm=False):
+    """The scene of ``point_target_cube`` before it is rounded to int16: complex128 ``(4, 192, 256)``."""
     s = np.arange(NUM_SAMPLE)[None, None, :]
     cc = np.arange(64)[None, :, None]
     rx = np.arange(NUM_RX)[:, None, None]
@@ -115,10 +109,27 @@ def point_target_cube(targets, noise=0.0, seed=0):
                 ph = np.exp(2j * np.pi * fa * (rx + 4))
             else:
                 ph = np.exp(2j * np.pi * (fa * (rx + 2) + fe))
+            if tdm:
+                ph = ph * np.exp(2j * np.pi * fd * tx / 3.0)
             out[:, tx::3, :] += base * ph
     if noise > 0:
         out += noise * (normal(out.shape, "ptn_r", seed, dtype=np.float64)
                         + 1j * normal(out.shape, "ptn_i", seed, dtype=np.float64))
+    return out
+
+
+def point_target_cube(targets, noise=0.0, seed=0, tdm=False):
+    """Known-answer scene: sum of complex exponentials over (sample, chirp, virtual antenna).
+
+    ``targets`` = list of dict(range_bin, doppler_bin, az_bin, el_bin, amp).  Phase
+    progressions follow the reference's demux: chirp c = 3*cc + tx; tx0 -> az
+    antennas 0..3, tx2 -> az antennas 4..7, tx1 -> elevation row (az offset 2).
+    ``tdm=False`` is the idealised scene: the three transmitters of a chirp loop share one Doppler phase ``2 pi fd cc``.  ``tdm=True``
+    is the physical one: transmitter ``tx`` fires ``tx`` chirp periods into the loop, so its Doppler phase is
+    ``2 pi fd (cc + tx / 3)``.
+    Returns int16 I/Q ``(1, 4, 192, 256, 2)``.
+    """
+    out = point_target_scene(targets, noise, seed, tdm)
     iq = np.stack([np.clip(np.rint(out.real), -32768, 32767),
                    np.clip(np.rint(out.imag), -32768, 32767)], axis=-1).astype(np.int16)
     return iq[None]

@@ -7,6 +7,8 @@ Settings (none of them a key of the reference's YAML; each absent or ``-1`` = of
   ``TRAINING.augMaskRange``  int in [1, rangeSize / 2]: per sample one band of up to that many range bins is zeroed in both maps
   ``TRAINING.augMaskAngle``  int in [1, azimuthSize / 2]: per sample and map one band of up to that many azimuth bins is zeroed
   ``TEST.flip``              bool: evaluate with the flip test (``TrainEngine.infer_from_adc(..., flip=True)``)
+  ``DATASET.tdmCompensation`` bool (absent = false): Doppler phase compensation of the TDM-MIMO virtual array in the FFT chain
+                             (``preprocessing.tdm_phase_table``; read here because it meets the mirror, below)
 
 What "mirror" means for this radar.  Reversing the azimuth axis of the network input is wrong: the FFT chain's azimuth index is
 ``a -> (31 - a) mod 64`` in frequency, so a mirrored target lands on ``(62 - a) mod 64``, and a scene mirrored about the array centre
@@ -17,8 +19,10 @@ mirror needs raw ADC cubes; stored, already normalised cubes can take the noise 
 
 Two approximations.  The vertical sensor's cube is left as it is: the mirrored scene would reflect that array's two-row axis, which
 is not symmetric (8 antennas in one row, 4 in the other), and the network only ever sees the mean over that axis.  Swapping the two
-transmitters also swaps their time slots: a target in Doppler bin ``d`` keeps a residual phase of the order ``2 pi d / 96`` between
-the two antenna halves (the reference compensates no TDM phase either).
+transmitters also swaps their time slots: with ``DATASET.tdmCompensation`` off (the default; the reference compensates no TDM phase
+either) a target in Doppler bin ``d`` keeps a residual phase of the order ``2 pi d / 96`` between the two antenna halves.  With the key
+on the residual vanishes: the engine hands the plan's mirror flags to the chain, which compensates a mirrored frame with the slots of
+transmitters 0 and 2 exchanged, and the mirror identity (index map times ramp) holds exactly on the compensated cube.
 
 The labels are mirrored about the centre of the heat-map grid, ``x' = stride (H - 1) - x`` (252 - x), with ``L_*`` and ``R_*`` joints
 exchanged: the decode maps heat-map pixel ``m`` to image ``4 m``, so only this axis makes the mirrored target the mirror
@@ -101,6 +105,19 @@ def flip_setting(cfg):
     if isinstance(v, bool):
         return v
     raise ValueError("TEST.flip must be true or false, got %r" % (v,))
+
+
+TDM_NEEDS_RANGE_DOPPLER = ("DATASET.tdmCompensation is set, but this dataset reads stored cubes: the compensation acts on the range-Doppler map, "
+                           "which a stored cube no longer has.  Cubes written with processRadarDataHoriVert(tdm_compensation=True) are already "
+                           "compensated and are used with the key off")
+
+
+def tdm_setting(cfg):
+    """``DATASET.tdmCompensation`` -> bool (absent: False).  Anything but a bool raises."""
+    v = getattr(getattr(cfg, "DATASET", None), "tdmCompensation", False)
+    if isinstance(v, bool):
+        return v
+    raise ValueError("DATASET.tdmCompensation must be true or false, got %r" % (v,))
 
 
 def augment_settings(cfg):

@@ -18,6 +18,28 @@ import torch
 from ..misc.logger import Logger
 
 
+def preprocess_sidecar(cfg):
+    """What ``preprocess.json`` records beside the checkpoints of a run the GPU FFT loader fed: the zero-Doppler convention, and
+    ``"fft_tdm_compensation": true`` only when ``DATASET.tdmCompensation`` is on (a run without the key writes the file it always
+    wrote)."""
+    from ..preprocessing import process_iwr1843 as _pre
+    from .augment import tdm_setting
+    side = {"fft_zero_doppler": _pre.ZERO_DOPPLER}
+    if tdm_setting(cfg):
+        side["fft_tdm_compensation"] = True
+    return side
+
+
+def tdm_mismatch_warning(side, tdm_now):
+    """-> the warning line when the weights beside sidecar dict ``side`` were trained under the other ``DATASET.tdmCompensation``
+    setting than this process runs, else None.  A sidecar without the key means off."""
+    trained = bool(side.get("fft_tdm_compensation", False))
+    if trained == bool(tdm_now):
+        return None
+    return ("==========>WARNING: these weights were trained with DATASET.tdmCompensation %s, this process runs it %s"
+            % (("on", "off") if trained else ("off", "on")))
+
+
 class BaseRunner():
     def __init__(self, args, cfg):
         self.device = "cuda" if torch.cuda.is_available() and args.gpuIDs else "cpu"
@@ -108,9 +130,8 @@ class BaseRunner():
         # Written only when the GPU FFT loader actually fed this run (raw-capture dataset): a run on stored .npy cubes never touched
         # the chain, and a sidecar there would claim a convention nobody used.
         if getattr(self, "uses_gpu_fft_loader", False):
-            from ..preprocessing import process_iwr1843 as _pre
             with open(os.path.join(self.dir, "preprocess.json"), "w") as fp:
-                json.dump({"fft_zero_doppler": _pre.ZERO_DOPPLER}, fp)
+                json.dump(preprocess_sidecar(self.cfg), fp)
         if epoch % 5 == 0:
             torch.save(group, os.path.join(self.dir, "checkpoint_%d.pth" % epoch))
 
@@ -135,10 +156,15 @@ class BaseRunner():
         side = os.path.join(self.dir, "preprocess.json")
         if os.path.exists(side):
             from ..preprocessing import process_iwr1843 as _pre
+            from .augment import tdm_setting
             with open(side) as fp:
-                trained = json.load(fp).get("fft_zero_doppler")
+                recorded = json.load(fp)
+            trained = recorded.get("fft_zero_doppler")
             if trained and trained != _pre.ZERO_DOPPLER:
                 print("==========>WARNING: these weights were trained with HUPR_FFT_ZERO_DOPPLER=%s, this process runs %s" % (trained, _pre.ZERO_DOPPLER))
+            warn = tdm_mismatch_warning(recorded, tdm_setting(self.cfg))
+            if warn:
+                print(warn)
         elif getattr(self, "uses_gpu_fft_loader", False):
             from ..preprocessing import process_iwr1843 as _pre
             print("==========>NOTE: no preprocess.json beside these weights: the zero-Doppler convention they were trained with is unknown "

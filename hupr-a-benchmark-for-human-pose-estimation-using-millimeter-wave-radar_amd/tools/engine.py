@@ -20,6 +20,9 @@ from .optim import make_optimizer
 class TrainEngine:
     def __init__(self, cfg, device="cuda", lr=None, seed=0, bucket_bytes=48 << 20):
         self.cfg = cfg
+        # DATASET.tdmCompensation: the FFT chain compensates the Doppler phase between the transmitters' slots (preprocessing,
+        # hupr_fft_chain_tdm); off = today's launches.  A mirrored horizontal cube is compensated with the slots of TX0 and TX2 exchanged
+        self.tdm = aug.tdm_setting(cfg)
         self.device = torch.device(device)
         torch.manual_seed(seed)
         self.model = HuPRNet(cfg).to(self.device)
@@ -51,6 +54,7 @@ class TrainEngine:
         self.augment = aug.Augmenter(cfg, settings, self.device, seed=seed, rank=dist.get_rank() if dist.is_initialized() else 0) \
             if settings is not None else None
         self._mirror_pairs = None
+        self._all_swapped = None      # the flip test's swap flags under DATASET.tdmCompensation: every frame of the second pass
         self.fuse_elevation_mean = os.environ.get("HUPR_NO_FUSED_MEAN", "0") != "1"
         self._fft_ws = None
         self._seed = None
@@ -70,13 +74,21 @@ class TrainEngine:
         self.buckets.close()
 
     # -- data -------------------------------------------------------------------------------------
-    def preprocess(self, adc_hori, adc_vert):
+    def preprocess(self, adc_hori, adc_vert, hori_swapped=None):
         """int16 ADC cubes (B*G, 4, 192, 256, 2) per sensor -> the two network inputs.  Default (``fuse_elevation_mean``): the
         loader tensor already averaged over its elevation axis, (B, G, 16, R, A) planes — 1/8 of the bytes written by the FFT
         chain and read back by the MNet front end, bit-identical results; ``HUPR_NO_FUSED_MEAN=1`` keeps the reference-shaped
-        (B,G,F,2,R,A,E) hand-over."""
+        (B,G,F,2,R,A,E) hand-over.  With ``DATASET.tdmCompensation`` both chains compensate the TDM Doppler phase; ``hori_swapped``:
+        (B,) uint8 on the device, the samples whose horizontal cube was mirrored (the vertical cube never is)."""
         n = adc_hori.shape[0]
         B = n // self.G
+        if self.tdm:
+            hkw = dict(tdm_compensation=True, tx_swapped=hori_swapped, frames_per_flag=self.G)
+            if self.fuse_elevation_mean:
+                return (fft_chain_loader_means(adc_hori, **hkw).view(B, self.G, 16, 64, 64),
+                        fft_chain_loader_means(adc_vert, tdm_compensation=True).view(B, self.G, 16, 64, 64))
+            return (fft_chain_loader(adc_hori, **hkw).view(B, self.G, 8, 2, 64, 64, 8),
+                    fft_chain_loader(adc_vert, tdm_compensation=True).view(B, self.G, 8, 2, 64, 64, 8))
         if self.fuse_elevation_mean:
             return (fft_chain_loader_means(adc_hori).view(B, self.G, 16, 64, 64),
                     fft_chain_loader_means(adc_vert).view(B, self.G, 16, 64, 64))
@@ -91,7 +103,7 @@ class TrainEngine:
         by the labels."""
         a = self.augment
         a.plan(adc_hori.shape[0] // self.G)
-        hori, vert = self.preprocess(a.adc(adc_hori), adc_vert)
+        hori, vert = self.preprocess(a.adc(adc_hori), adc_vert, hori_swapped=a.flags if self.tdm and a.mirrors else None)
         return a.apply(hori, 0), a.apply(vert, 1), a.labels(joints)
 
     # -- steps ------------------------------------------------------------------------------------
@@ -351,7 +363,13 @@ class TrainEngine:
             self._mirror_pairs = aug.mirror_pairs(self.cfg.DATASET.idxToJoints)
         adc_m = aug.adc_mirror(adc_hori)
         B = adc_m.shape[0] // self.G
-        hori_m = fft_chain_loader_means(adc_m).view(B, self.G, 16, 64, 64) if self.fuse_elevation_mean else \
-            fft_chain_loader(adc_m).view(B, self.G, 8, 2, 64, 64, 8)
+        if self.tdm:                             # every frame of the second pass is mirrored: all flags set
+            if self._all_swapped is None or self._all_swapped.numel() != B:
+                self._all_swapped = torch.ones(B, dtype=torch.uint8, device=adc_m.device)
+            kw = dict(tdm_compensation=True, tx_swapped=self._all_swapped, frames_per_flag=self.G)
+        else:
+            kw = {}
+        hori_m = fft_chain_loader_means(adc_m, **kw).view(B, self.G, 16, 64, 64) if self.fuse_elevation_mean else \
+            fft_chain_loader(adc_m, **kw).view(B, self.G, 8, 2, 64, 64, 8)
         preds_m = self.infer(hori_m, vert)
         return tuple(aug.flip_merge(p, pm, self._mirror_pairs) for p, pm in zip(preds, preds_m))

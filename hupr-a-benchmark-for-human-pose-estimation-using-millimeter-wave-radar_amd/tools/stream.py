@@ -307,10 +307,12 @@ class PoseStream:
     forecast horizon is ``lookahead / rate_hz`` — where the joint is at the newest frame, not at the emitted one — whatever the
     tracker's own ``horizon_s``.  ``decode="integral"`` decodes the mass centroid of the window of ``decode_radius`` heat-map pixels
     around the peak (None: the targets' patch radius, 6 at 64 and 9 at 128; 0: the whole map), with ``smooth`` in the same launch and
-    never with ``track``.  With the defaults the session decodes exactly as before, in the same two launches."""
+    never with ``track``.  With the defaults the session decodes exactly as before, in the same two launches.
+    ``tdm_compensation=True``: the FFT chain of every push compensates the TDM Doppler phase (``hupr_fft_chain_tdm`` with no swap
+    table, inside the same graph replay) — for weights trained with ``DATASET.tdmCompensation``."""
 
     def __init__(self, model, cfg, lanes=1, lookahead=None, graph=True, device=None, decode="argmax", smooth=None, track=None,
-                 predict_now=False, decode_radius=None):
+                 predict_now=False, decode_radius=None, tdm_compensation=False):
         D = cfg.DATASET
         self.G = D.numGroupFrames
         self.schedule = StreamSchedule(self.G, lookahead)
@@ -318,6 +320,9 @@ class PoseStream:
         self.decode_radius = check_decode(decode, smooth, decode_radius, D.heatmapSize)
         check_track(track, smooth, predict_now, decode)
         self.decode, self.smooth, self.predict_now = decode, smooth, bool(predict_now)
+        if not isinstance(tdm_compensation, bool):
+            raise StreamError("tdm_compensation must be True or False, got %r" % (tdm_compensation,))
+        self.tdm_compensation = tdm_compensation
         self.track = track.with_horizon(self.lookahead / track.rate_hz) if predict_now else track
         if not isinstance(lanes, int) or lanes < 1:
             raise StreamError("lanes must be a positive integer, got %r" % (lanes,))
@@ -385,7 +390,10 @@ class PoseStream:
         L, s = rt.lib(), rt.stream()
         if not flush:
             flags = pre._flags(None, False, None)
-            if flags == 0:
+            if self.tdm_compensation:
+                rt.check(L.hupr_fft_chain_tdm(rt.ptr(self._adc), 2 * self.lanes, rt.ptr(self._staging), flags, 2, None, 0, 1,
+                                              rt.ptr(self._ws), self._ws_bytes, s))
+            elif flags == 0:
                 rt.check(L.hupr_fft_chain_loader_means_f32(rt.ptr(self._adc), 2 * self.lanes, rt.ptr(self._staging), rt.ptr(self._ws),
                                                            self._ws_bytes, s))
             else:
@@ -525,6 +533,8 @@ def parse(argv=None):
     p.add_argument("--accel-psd", type=float, default=None, help="with --track: white-acceleration power, pixel^2 / s^3 (default 200)")
     p.add_argument("--gate", type=float, default=None, help="with --track: largest accepted squared Mahalanobis distance (default 13.816)")
     p.add_argument("--max-coast", type=int, default=None, help="with --track: frames a track survives without a measurement (default 5)")
+    p.add_argument("--tdm-compensation", action="store_true", help="compensate the TDM Doppler phase in the FFT chain (weights trained "
+                   "with DATASET.tdmCompensation)")
     p.add_argument("--weights", choices=WEIGHTS, default="live", help="live: model_state_dict as trained; averaged: ema_state_dict "
                    "(a run with TRAINING.emaDecay)")
     args = p.parse_args(argv)
@@ -556,10 +566,11 @@ def tracking_from_args(args):
     return PoseTracking(args.rate, **kw)
 
 
-def load_model_best(model, log_dir, device, weights="live"):
+def load_model_best(model, log_dir, device, weights="live", tdm_compensation=False):
     """``model_best.pth`` of ``log_dir`` into ``model``, the way Runner.loadModelWeight reads it for evaluation.  ``weights``:
     ``"live"`` = ``model_state_dict``, the parameters as trained; ``"averaged"`` = ``ema_state_dict``, their moving average, which
-    only a run with ``TRAINING.emaDecay`` saved."""
+    only a run with ``TRAINING.emaDecay`` saved.  ``tdm_compensation``: what the session will run, compared with what
+    ``preprocess.json`` says the weights were trained with."""
     if weights not in WEIGHTS:
         raise ValueError("weights must be one of %s, got %r" % (", ".join(WEIGHTS), weights))
     from ..preprocessing import process_iwr1843 as pre
@@ -577,10 +588,15 @@ def load_model_best(model, log_dir, device, weights="live"):
         model.load_state_dict(ck["model_state_dict"])
     side = os.path.join(log_dir, "preprocess.json")
     if os.path.exists(side):
+        from .base import tdm_mismatch_warning
         with open(side) as fp:
-            trained = json.load(fp).get("fft_zero_doppler")
+            recorded = json.load(fp)
+        trained = recorded.get("fft_zero_doppler")
         if trained and trained != pre.ZERO_DOPPLER:
             print("==========>WARNING: these weights were trained with HUPR_FFT_ZERO_DOPPLER=%s, this process runs %s" % (trained, pre.ZERO_DOPPLER))
+        warn = tdm_mismatch_warning(recorded, tdm_compensation)
+        if warn:
+            print(warn)
     print("==========>Load the model weight from %s, saved at epoch %d" % (log_dir, ck["epoch"]))
 
 
@@ -594,7 +610,7 @@ def main(argv=None):
     dev = torch.device("cuda", torch.cuda.current_device())
     cfg = load_config(args.config, "./config" if os.path.isdir("./config") else None)
     model = HuPRNet(cfg).to(dev).eval()
-    load_model_best(model, os.path.join("./logs", args.dir), dev, weights=args.weights)
+    load_model_best(model, os.path.join("./logs", args.dir), dev, weights=args.weights, tdm_compensation=args.tdm_compensation)
     if args.math is not None:
         model.math_mode = args.math
     frames = []
@@ -604,7 +620,7 @@ def main(argv=None):
     n = min(frames[0].shape[0], frames[1].shape[0])
     session = PoseStream(model, cfg, lanes=1, lookahead=args.lookahead, graph=not args.no_graph, device=dev, decode=args.decode,
                          smooth=PoseSmoothing(args.rate) if args.smooth else None, track=tracking_from_args(args),
-                         predict_now=args.predict_now, decode_radius=args.decode_radius)
+                         predict_now=args.predict_now, decode_radius=args.decode_radius, tdm_compensation=args.tdm_compensation)
     records = []
 
     def record(pf):

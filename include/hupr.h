@@ -93,6 +93,35 @@ int hupr_fft_chain_loader_means_f32(const int16_t* adc_iq, int n_sf, float* mean
 int hupr_fft_chain_opts(const int16_t* adc_iq, int n_sf, void* out, int flags, int loader, void* ws, size_t ws_bytes,
                         hupr_stream_t stream);
 
+/* (a1, opt-in) Doppler phase compensation for the TDM-MIMO virtual array.  The reference has none (process_iwr1843.py:113-120
+ *      demultiplexes the three transmitters and goes on as if they had fired together); this is the Doppler compensation step of
+ *      a TDM-MIMO pipeline (TI mmWave SDK, AoA DPU, "Doppler compensation").  OFF on every parity path.
+ *
+ *      Virtual antenna v in the chain's workspace order:
+ *
+ *        v      transmitter             slot k
+ *        0..3   TX0                     0
+ *        4..7   TX2                     2
+ *        8..11  TX1, the elevated row   1
+ *
+ *      - The kept Doppler index i = 0..15 has the signed bin d = i - 8.
+ *      - The range-Doppler value of (v, i, range) is multiplied by exp(-2 pi j d k(v) / 192) before the pruned angle DFT and
+ *        before the loader statistics.
+ *      - For a sensor-frame marked swapped, k is 2 for v in 0..3 and 0 for v in 4..7.  k stays 1 for the elevated row.
+ *      - The 48 factors are the fp32 roundings of the fp64 cosine and sine.  A factor with d == 0 or k == 0 is exactly (1, 0).
+ *      - Doppler index 8 and the k = 0 rows must therefore keep today's bits.  This holds under all three zero-Doppler
+ *        conventions: the dither, ZERO_DOPPLER_EXACT and RANGE_FIRST.
+ *
+ *      flags, loader, the buffers, the workspace and the error rules are those of hupr_fft_chain_opts.  Sensor-frame sf is swapped
+ *      when tx_swapped_or_null is non-null, sf / frames_per_flag < n_swapped and that byte is non-zero (the ADC mirror of
+ *      hupr_adc_mirror_i16 exchanges TX0 and TX2, and with them their slots).  The table is device memory, read by the kernel at
+ *      launch time: a step replayed from a hipGraph follows the table's current content.  HUPR_ERR_ARG before any launch for
+ *      frames_per_flag < 1, n_swapped < 0, or a non-null table with n_swapped == 0.
+ *      A Doppler bin aliased past +-32 is compensated with the wrong sign, as in every such pipeline. */
+int hupr_fft_chain_tdm(const int16_t* adc_iq, int n_sf, void* out, int flags, int loader,
+                       const unsigned char* tx_swapped_or_null, int n_swapped, int frames_per_flag,
+                       void* ws, size_t ws_bytes, hupr_stream_t stream);
+
 /* (a2) loader glue alone on a precomputed cube (the .npy hand-off of the reference):
  * cube_c64 : float2 [n_sf][16][64][64][8]  ->  out float [n_sf][8][2][64][64][8]            */
 int hupr_loader_normalize_c64(const void* cube_c64, int n_sf, float* out, hupr_stream_t stream);
