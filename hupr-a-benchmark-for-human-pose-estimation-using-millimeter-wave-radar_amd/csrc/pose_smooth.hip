@@ -1,0 +1,186 @@
+// Fixed-interval Rauch-Tung-Striebel smoother (Rauch, Tung & Striebel 1965) over a recorded run of the Kalman tracker of
+// csrc/pose_track.hip: the backward pass over the states the filter left behind, frame T-1 down to frame 0.
+//   * one thread per row, sequential in the frame: a latency-bound recurrence of T dependent steps; the rows axis exists so that many
+//     sequences (sequences x joints) share one launch
+//   * the successor's smoothed state (4 + 10 values) stays in registers; the filter's state of a frame is read as four float4
+//   * no LDS, no atomics, no scratch: every output is bit-identical from run to run and independent of the other rows
+// The rule is stated in full beside hupr_pose_smooth_rts_f32 in include/hupr.h.
+#include "hupr_common.h"
+#include "pose_refine.h"
+
+namespace hupr {
+
+constexpr int kStateFloats = 16;      // the tracker's state of one row (csrc/pose_track.hip)
+constexpr int kStarted = 3, kLost = 4;                                          // HUPR_TRACK_STARTED, HUPR_TRACK_LOST
+constexpr int kSmoothed = 0, kEnd = 1, kPassthrough = 2, kDegenerate = 3;       // HUPR_SMOOTH_*
+
+// the upper triangle of a symmetric 4 x 4 matrix row by row, as the tracker's state keeps it
+__host__ __device__ constexpr int tri(int i, int j) { return i <= j ? i * (9 - i) / 2 + (j - i) : j * (9 - j) / 2 + (i - j); }
+
+// One backward step.  x, p: the filter's state of frame k; xs, ps: the smoothed state of frame k + 1 on entry, of frame k on return.
+// false (xs, ps untouched) where a Cholesky pivot is not positive and finite or a result is not finite.
+__device__ __forceinline__ bool rts_step(const float (&x)[4], const float (&p)[10], float (&xs)[4], float (&ps)[10], float dt, float q11,
+                                         float q12, float q22) {
+    // ---- predict, with the tracker's own expressions: xp = F x, Pp = F P F^T + Q ------------------------------------------------------
+    float xp[4] = {x[0] + dt * x[2], x[1] + dt * x[3], x[2], x[3]};
+    float pp[10];
+    pp[tri(0, 0)] = p[tri(0, 0)] + (dt * (2.f * p[tri(0, 2)]) + dt * dt * p[tri(2, 2)] + q11);
+    pp[tri(0, 1)] = p[tri(0, 1)] + (dt * (p[tri(0, 3)] + p[tri(1, 2)]) + dt * dt * p[tri(2, 3)]);
+    pp[tri(1, 1)] = p[tri(1, 1)] + (dt * (2.f * p[tri(1, 3)]) + dt * dt * p[tri(3, 3)] + q11);
+    pp[tri(0, 2)] = p[tri(0, 2)] + (dt * p[tri(2, 2)] + q12);
+    pp[tri(0, 3)] = p[tri(0, 3)] + dt * p[tri(2, 3)];
+    pp[tri(1, 2)] = p[tri(1, 2)] + dt * p[tri(2, 3)];
+    pp[tri(1, 3)] = p[tri(1, 3)] + (dt * p[tri(3, 3)] + q12);
+    pp[tri(2, 2)] = p[tri(2, 2)] + q22;
+    pp[tri(2, 3)] = p[tri(2, 3)];
+    pp[tri(3, 3)] = p[tri(3, 3)] + q22;
+
+    // ---- Cholesky Pp = L L^T, column by column; l[tri(i, j)] = L[i][j] for i >= j ------------------------------------------------------
+    float l[10], inv[4];
+    bool ok = true;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        float d = pp[tri(j, j)];
+#pragma unroll
+        for (int m = 0; m < j; ++m) d -= l[tri(j, m)] * l[tri(j, m)];
+        ok = ok && d > 0.f && finitef(d);
+        const float root = sqrtf(d);
+        l[tri(j, j)] = root;
+        inv[j] = 1.f / root;
+#pragma unroll
+        for (int i = j + 1; i < 4; ++i) {
+            float v = pp[tri(i, j)];
+#pragma unroll
+            for (int m = 0; m < j; ++m) v -= l[tri(i, m)] * l[tri(j, m)];
+            l[tri(i, j)] = v * inv[j];
+        }
+    }
+
+    // ---- C = P F^T Pp^-1: row i of C solves L L^T c = (P F^T)[i][:]^T, forward then backward ---------------------------------------------
+    float c[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const float a[4] = {p[tri(i, 0)] + dt * p[tri(i, 2)], p[tri(i, 1)] + dt * p[tri(i, 3)], p[tri(i, 2)], p[tri(i, 3)]};
+        float y[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float v = a[j];
+#pragma unroll
+            for (int m = 0; m < j; ++m) v -= l[tri(j, m)] * y[m];
+            y[j] = v * inv[j];
+        }
+#pragma unroll
+        for (int j = 3; j >= 0; --j) {
+            float v = y[j];
+#pragma unroll
+            for (int m = j + 1; m < 4; ++m) v -= l[tri(m, j)] * c[i][m];
+            c[i][j] = v * inv[j];
+        }
+    }
+
+    // ---- xs = x + C (xs' - xp);  Ps = P + C (Ps' - Pp) C^T, symmetrised ---------------------------------------------------------------------
+    float dx[4], d[10];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) dx[j] = xs[j] - xp[j];
+#pragma unroll
+    for (int j = 0; j < 10; ++j) d[j] = ps[j] - pp[j];
+    float nx[4], m[4][4], n[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        nx[i] = x[i] + (c[i][0] * dx[0] + c[i][1] * dx[1] + c[i][2] * dx[2] + c[i][3] * dx[3]);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            m[i][j] = c[i][0] * d[tri(0, j)] + c[i][1] * d[tri(1, j)] + c[i][2] * d[tri(2, j)] + c[i][3] * d[tri(3, j)];
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            n[i][j] = p[tri(i, j)] + (m[i][0] * c[j][0] + m[i][1] * c[j][1] + m[i][2] * c[j][2] + m[i][3] * c[j][3]);
+    float np[10];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = i; j < 4; ++j) np[tri(i, j)] = i == j ? n[i][i] : 0.5f * (n[i][j] + n[j][i]);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) ok = ok && finitef(nx[j]);
+#pragma unroll
+    for (int j = 0; j < 10; ++j) ok = ok && finitef(np[j]);
+    if (ok) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) xs[j] = nx[j];
+#pragma unroll
+        for (int j = 0; j < 10; ++j) ps[j] = np[j];
+    }
+    return ok;
+}
+
+// One thread = one row, frames T-1 .. 0.  Nothing is shared between threads.
+__global__ __launch_bounds__(64) void hupr_k_pose_smooth_rts(const float* __restrict__ states, const int* __restrict__ status,
+                                                             const float* __restrict__ keypoints, long T, long rows, float rate,
+                                                             float accel_psd, float* __restrict__ smoothed,
+                                                             float* __restrict__ velocity, float* __restrict__ covariance,
+                                                             int* __restrict__ flag) {
+    const long r = (long)blockIdx.x * 64 + threadIdx.x;
+    if (r >= rows) return;
+    const float dt = 1.f / rate;
+    const float q11 = accel_psd * dt * dt * dt * (1.f / 3.f), q12 = accel_psd * dt * dt * 0.5f, q22 = accel_psd * dt;
+    float xs[4] = {0.f, 0.f, 0.f, 0.f};
+    float ps[10] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    bool chained = false;                      // frame k + 1 exists and continues the track of frame k
+    for (long k = T - 1; k >= 0; --k) {
+        const long e = k * rows + r;
+        const int code = status[e];
+        int fl;
+        if (code == kLost) {
+            *reinterpret_cast<float2*>(smoothed + e * 2) = *reinterpret_cast<const float2*>(keypoints + e * 2);
+            *reinterpret_cast<float2*>(velocity + e * 2) = make_float2(0.f, 0.f);
+            covariance[e * 3 + 0] = 0.f;
+            covariance[e * 3 + 1] = 0.f;
+            covariance[e * 3 + 2] = 0.f;
+            fl = kPassthrough;
+        } else {
+            const float4* s = reinterpret_cast<const float4*>(states + e * kStateFloats);
+            const float4 s0 = s[0], s1 = s[1], s2 = s[2], s3 = s[3];
+            const float x[4] = {s0.x, s0.y, s0.z, s0.w};
+            const float p[10] = {s1.x, s1.y, s1.z, s1.w, s2.x, s2.y, s2.z, s2.w, s3.x, s3.y};
+            fl = kEnd;
+            if (chained) fl = rts_step(x, p, xs, ps, dt, q11, q12, q22) ? kSmoothed : kDegenerate;
+            if (fl != kSmoothed) {             // the end of a segment and a degenerate frame: the filter's own state, and the chain goes on from it
+#pragma unroll
+                for (int j = 0; j < 4; ++j) xs[j] = x[j];
+#pragma unroll
+                for (int j = 0; j < 10; ++j) ps[j] = p[j];
+            }
+            *reinterpret_cast<float2*>(smoothed + e * 2) = make_float2(xs[0], xs[1]);
+            *reinterpret_cast<float2*>(velocity + e * 2) = make_float2(xs[2], xs[3]);
+            covariance[e * 3 + 0] = ps[tri(0, 0)];
+            covariance[e * 3 + 1] = ps[tri(0, 1)];
+            covariance[e * 3 + 2] = ps[tri(1, 1)];
+        }
+        flag[e] = fl;
+        chained = code != kLost && code != kStarted;
+    }
+}
+
+}  // namespace hupr
+
+using namespace hupr;
+
+extern "C" int hupr_pose_smooth_rts_f32(const float* states, const int* status, const float* keypoints, long T, long rows,
+                                        float rate_hz, float accel_psd, float* smoothed, float* velocity, float* covariance, int* flag,
+                                        hupr_stream_t stream) {
+    HUPR_REQUIRE(T >= 1 && rows >= 0, "hupr_pose_smooth_rts_f32: bad shape (T %ld, rows %ld)", T, rows);
+    if (rows == 0) return HUPR_OK;
+    HUPR_REQUIRE(states && status && keypoints && smoothed && velocity && covariance && flag, "hupr_pose_smooth_rts_f32: null pointer");
+    HUPR_REQUIRE(T < (1L << 31) && rows < (1L << 31) && T * rows < (1L << 31),
+                 "hupr_pose_smooth_rts_f32: T * rows beyond 2^31 (T %ld, rows %ld)", T, rows);
+    HUPR_REQUIRE(((uintptr_t)states & 15) == 0, "hupr_pose_smooth_rts_f32: the states must be 16-byte aligned");
+    HUPR_REQUIRE(rate_hz > 0.f && rate_hz < INFINITY && accel_psd >= 0.f && accel_psd < INFINITY,
+                 "hupr_pose_smooth_rts_f32: bad tracker parameter (rate_hz %g must be positive, accel_psd %g non-negative, both finite)",
+                 rate_hz, accel_psd);
+    HUPR_LAUNCH(hupr_k_pose_smooth_rts, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, as_stream(stream), states, status, keypoints, T,
+                rows, rate_hz, accel_psd, smoothed, velocity, covariance, flag);
+    HUPR_LAUNCH_OK("hupr_k_pose_smooth_rts");
+    return HUPR_OK;
+}

@@ -2065,3 +2065,41 @@ def pose_track(heat, ratio, refine=True, track_state=None, tracking=None):
                                           rt.ptr(idx), rt.ptr(mx), rt.ptr(raw), rt.ptr(kp), rt.ptr(vel), rt.ptr(cov), rt.ptr(fc),
                                           rt.ptr(status), rt.stream()))
     return idx, mx, raw, kp, vel, cov, fc, status
+
+
+SMOOTH_SMOOTHED, SMOOTH_END, SMOOTH_PASSTHROUGH, SMOOTH_DEGENERATE = range(4)                   # pose_smooth_rts's flags
+
+
+def pose_smooth_rts(states, status, keypoints, tracking):
+    """Rauch-Tung-Striebel smoothing of a recorded ``pose_track`` run in one launch (csrc/pose_smooth.hip; the rule is stated beside
+    hupr_pose_smooth_rts_f32 in include/hupr.h).  ``states`` (T, ..., 16) fp32: entry k is a copy of the ``track_state`` right after
+    the ``pose_track`` call of frame k; ``status`` int32 (T, ...) and ``keypoints`` (T, ..., 2) that call's status and filtered
+    keypoints; ``tracking`` the parameters of the run (``rate_hz`` and ``accel_psd`` are read) -> (smoothed keypoints (T, ..., 2),
+    velocity (T, ..., 2), position covariance (T, ..., 3) = (Pxx, Pxy, Pyy), flag int32 (T, ...), one of the SMOOTH_* codes).  Device
+    tensors, no sync."""
+    for name, t, dtype in (("states", states, torch.float32), ("status", status, torch.int32), ("keypoints", keypoints, torch.float32)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype:
+            raise ValueError("pose_smooth_rts needs %s as a %s tensor, got %s" % (name, dtype, getattr(t, "dtype", type(t).__name__)))
+    if tracking is None:
+        raise ValueError("pose_smooth_rts needs the tracking parameters of the filter run")
+    if status.dim() < 1 or status.shape[0] < 1:
+        raise ValueError("pose_smooth_rts needs (T, ...) histories with T >= 1, got status of shape %r" % (tuple(status.shape),))
+    lead = tuple(status.shape)
+    if tuple(states.shape) != lead + (16,) or tuple(keypoints.shape) != lead + (2,):
+        raise ValueError("pose_smooth_rts needs states %r and keypoints %r beside status %r, got %r and %r"
+                         % (lead + (16,), lead + (2,), lead, tuple(states.shape), tuple(keypoints.shape)))
+    if not (states.device == status.device == keypoints.device):
+        raise ValueError("states, status and keypoints are on %s, %s and %s" % (states.device, status.device, keypoints.device))
+    if not states.is_cuda:
+        raise ValueError("pose_smooth_rts needs GPU tensors (no CPU fallback), got %s" % states.device)
+    states, status, keypoints = _c(states), _c(status), _c(keypoints)
+    T = lead[0]
+    rows = int(np.prod(lead[1:], dtype=np.int64))
+    dev = states.device
+    smoothed, vel = (torch.empty(lead + (2,), dtype=torch.float32, device=dev) for _ in range(2))
+    cov = torch.empty(lead + (3,), dtype=torch.float32, device=dev)
+    flag = torch.empty(lead, dtype=torch.int32, device=dev)
+    rt.check(rt.lib().hupr_pose_smooth_rts_f32(rt.ptr(states), rt.ptr(status), rt.ptr(keypoints), T, rows, float(tracking.rate_hz),
+                                               float(tracking.accel_psd), rt.ptr(smoothed), rt.ptr(vel), rt.ptr(cov), rt.ptr(flag),
+                                               rt.stream()))
+    return smoothed, vel, cov, flag

@@ -61,6 +61,8 @@ SIGNATURES = {
     "hupr_pose_track_state_bytes": (c_size_t, [c_long]),
     "hupr_pose_track_f32": (c_int, [c_void_p, c_long, c_int, c_int, c_float, c_int, c_void_p] + [c_float] * 5 + [c_int] +
                             [c_float] * 3 + [c_void_p] * 9),
+    # Rauch-Tung-Striebel smoother over a recorded run of the tracker (csrc/pose_smooth.hip)
+    "hupr_pose_smooth_rts_f32": (c_int, [c_void_p] * 3 + [c_long, c_long, c_float, c_float] + [c_void_p] * 5),
     "hupr_fft_chain_opts": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "hupr_fft_chain_tdm": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "hupr_loader_normalize_c64": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),

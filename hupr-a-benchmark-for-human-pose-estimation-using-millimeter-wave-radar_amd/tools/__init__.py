@@ -3,6 +3,7 @@ from .optim import FusedAdam, FusedSGD  # noqa: F401
 _STREAM = ("PoseStream", "PoseFrame", "StreamSchedule", "stream_window_sources", "StreamError", "LookaheadError",
            "FrameShapeError", "FrameDtypeError", "StreamEndedError", "PoseSmoothing", "DecodeError", "SmoothingError",
            "PoseTracking", "TrackedPoseFrame", "TrackingError")
+_SMOOTH = ("SequenceSmoother", "SmoothedSequence", "TrackHistory", "jitter")
 
 
 def __getattr__(name):          # lazy: Runner pulls in datasets/models
@@ -12,4 +13,7 @@ def __getattr__(name):          # lazy: Runner pulls in datasets/models
     if name in _STREAM:         # the live-stream session (tools/stream.py)
         from . import stream
         return getattr(stream, name)
+    if name in _SMOOTH:         # offline smoothing of tracked sequences (tools/smooth.py)
+        from . import smooth
+        return getattr(smooth, name)
     raise AttributeError(name)

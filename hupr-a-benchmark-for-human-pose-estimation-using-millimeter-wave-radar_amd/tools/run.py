@@ -21,6 +21,7 @@ from ..misc.plot import plotHumanPose
 from .augment import flip_setting
 from .base import BaseRunner
 from .engine import TrainEngine
+from .smooth import SequenceSmoother, SequenceWalker, jitter, temporal_setting
 
 
 def _collate(batch):
@@ -62,6 +63,10 @@ class Runner(BaseRunner):
             raise RuntimeError("the HIP runner needs a GPU (no CPU fallback)")
         self.rank = dist.get_rank() if dist.is_initialized() else 0
         self.world = dist.get_world_size() if dist.is_initialized() else 1
+        self.temporal = temporal_setting(cfg)   # TEST.temporal: eval() walks the test set through the Kalman tracker (tools/smooth.py)
+        if self.temporal is not None and self.world > 1:
+            raise RuntimeError("TEST.temporal: %s needs a single process: the evaluation is sharded over the %d ranks sample by sample, "
+                               "which would split every sequence" % (self.temporal.mode, self.world))
         if not args.eval:
             self.trainSet = getDataset("train", cfg, args)
             if isinstance(self.trainSet, HuPRRawADC):
@@ -113,9 +118,19 @@ class Runner(BaseRunner):
         ``TEST.decode`` is ``subpixel``, ``TEST.decode`` is ``integral``, or ``TRAINING.coordLoss`` or ``TEST.flip`` is set, one more line is printed, the mean per-joint position error in image pixels
         (``mean_position_error``): AP's OKS thresholds are too coarse to show a sub-pixel change.  ``TRAINING.boneLoss`` prints that
         line and one more, the mean error of the bones' lengths in image pixels (``mean_bone_error``).
-        ``--keypoints`` prints the per-joint APs (``evaluateEach``) instead of the summary line."""
+        ``--keypoints`` prints the per-joint APs (``evaluateEach``) instead of the summary line.
+        ``TEST.temporal: track`` or ``rts`` (``temporal_setting``): the test set is walked in loader order as sequences (sequence and
+        frame from ``imageId``; a new sequence or a frame that is not its predecessor + 1 zeroes the tracker state), every sample's
+        second-head maps go through ``SequenceSmoother.track`` one frame per call, and the keypoints written and scored are the
+        Kalman-filtered ones (``track``) or the Rauch-Tung-Striebel smoothed ones (``rts``).  After the AP line come an ``MPJPE``
+        line for the raw, the filtered and (``rts``) the smoothed keypoints and a ``Jitter`` line (``tools.smooth.jitter``) for each
+        of them and for the ground truth."""
         self.logger.clear(len(self.testLoader.dataset))
         savePreds, gts = [], []
+        temporal = self.temporal
+        if temporal is not None:
+            smoother = SequenceSmoother(temporal.tracking, self.numKeypoints, self.engine.device)
+            walker, boxes, ids = SequenceWalker(), [], []
         for batch in self.testLoader:
             keypoints = batch["jointsGroup"]
             if self.flip:
@@ -131,11 +146,27 @@ class Runner(BaseRunner):
             self.logger.display(loss, loss2, keypoints.size(0), epoch)
             if visualization:                       # --visDir given: one skeleton overlay per sample (run.py:50-52)
                 plotHumanPose(pred2d * self.imgHeatmapRatio, self.cfg, self.visDir, batch["imageId"], None)
-            self.saveKeypoints(savePreds, pred2d * self.imgHeatmapRatio, batch["bbox"], batch["imageId"])
+            if temporal is None:
+                self.saveKeypoints(savePreds, pred2d * self.imgHeatmapRatio, batch["bbox"], batch["imageId"])
+            else:
+                maps = preds[1].detach().reshape(-1, self.numKeypoints, self.height, self.width)
+                for j in range(keypoints.size(0)):
+                    if walker.step(batch["imageId"][j]):
+                        smoother.new_sequence()
+                    smoother.track(maps[j], self.imgHeatmapRatio, refine=self.lossComputer.decode == "subpixel")
+                    boxes.append(batch["bbox"][j])
+                    ids.append(batch["imageId"][j])
             gt_joints = batch["jointsFloat"] if "jointsFloat" in batch else keypoints
             for j in range(keypoints.size(0)):
                 gts.append({"image_id": int(batch["imageId"][j]), "keypoints": gt_joints[j].numpy().astype(np.float64),
                             "bbox": batch["bbox"][j].numpy().astype(np.float64)})
+        if temporal is not None:
+            seq = (smoother.smooth() if temporal.mode == "rts" else smoother.history.record()).cpu()
+            tracks = {"raw": seq.raw.numpy(), "filtered": seq.filtered.numpy()}
+            if temporal.mode == "rts":
+                tracks["smoothed"] = seq.keypoints.numpy()
+            self.saveKeypoints(savePreds, tracks["smoothed" if temporal.mode == "rts" else "filtered"], boxes, ids)
+            visited = np.stack([g["keypoints"] for g in gts])
         if self.world > 1:
             parts = [None] * self.world
             dist.all_gather_object(parts, (savePreds, gts))
@@ -163,6 +194,11 @@ class Runner(BaseRunner):
                 print("MPJPE: %.3f px (n = %d)" % mean_position_error(gts, savePreds)[::2])
             if self.lossComputer.boneLoss is not None:
                 print("Bone error: %.3f px (n = %d)" % mean_bone_error(gts, savePreds)[::2])
+            if temporal is not None:
+                for name, kp in tracks.items():
+                    print("MPJPE %s: %.3f px (n = %d)" % ((name,) + mean_position_error(gts, self.saveKeypoints([], kp, boxes, ids))[::2]))
+                for name, kp in list(tracks.items()) + [("truth", visited)]:
+                    print("Jitter %s: %.3f px" % (name, jitter([kp[a:b] for a, b in walker.segments()])))
         if self.world > 1:
             box = [ap]
             dist.broadcast_object_list(box, src=0)

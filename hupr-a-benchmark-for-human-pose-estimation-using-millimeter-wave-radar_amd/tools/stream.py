@@ -27,7 +27,10 @@ radius; 0: the whole map) — what the integral coordinate loss trains — in on
     python -m hupr_amd.tools.stream --config mscsa_prgcn.yaml --dir <logs name> --raw <dir with hori/ and vert/ adc_data.bin>
                                     [--lookahead N] [--math f32|bf16] [--no-graph] [--out poses.json]
                                     [--decode argmax|subpixel|integral [--decode-radius N]] [--smooth --rate FPS]
-                                    [--track --rate FPS [--predict-now] [--accel-psd Q] [--gate D2] [--max-coast N]]
+                                    [--track --rate FPS [--predict-now] [--accel-psd Q] [--gate D2] [--max-coast N] [--rts]]
+
+``--rts`` (with ``--track``): the capture is a finished file, so after the flush the recorded tracker states go through the
+Rauch-Tung-Striebel smoother (tools/smooth.py, csrc/pose_smooth.hip) and every record gains the smoothed pose.
 """
 import argparse
 import json
@@ -309,10 +312,14 @@ class PoseStream:
     around the peak (None: the targets' patch radius, 6 at 64 and 9 at 128; 0: the whole map), with ``smooth`` in the same launch and
     never with ``track``.  With the defaults the session decodes exactly as before, in the same two launches.
     ``tdm_compensation=True``: the FFT chain of every push compensates the TDM Doppler phase (``hupr_fft_chain_tdm`` with no swap
-    table, inside the same graph replay) — for weights trained with ``DATASET.tdmCompensation``."""
+    table, inside the same graph replay) — for weights trained with ``DATASET.tdmCompensation``.
+    ``history=True`` (needs ``track``): after every push or flush that emits a pose the tracker's state and outputs are copied into a
+    history on the device (tools/smooth.py: TrackHistory) — eager device-to-device copies on the session's stream, behind the graph
+    replay and not inside it — and ``smoothed()`` returns the Rauch-Tung-Striebel smoothed poses emitted since the last ``reset()``
+    in one launch of csrc/pose_smooth.hip.  The default adds nothing."""
 
     def __init__(self, model, cfg, lanes=1, lookahead=None, graph=True, device=None, decode="argmax", smooth=None, track=None,
-                 predict_now=False, decode_radius=None, tdm_compensation=False):
+                 predict_now=False, decode_radius=None, tdm_compensation=False, history=False):
         D = cfg.DATASET
         self.G = D.numGroupFrames
         self.schedule = StreamSchedule(self.G, lookahead)
@@ -323,6 +330,10 @@ class PoseStream:
         if not isinstance(tdm_compensation, bool):
             raise StreamError("tdm_compensation must be True or False, got %r" % (tdm_compensation,))
         self.tdm_compensation = tdm_compensation
+        if not isinstance(history, bool):
+            raise StreamError("history must be True or False, got %r" % (history,))
+        if history and track is None:
+            raise TrackingError("history needs track: it records the tracker's states for smoothed()")
         self.track = track.with_horizon(self.lookahead / track.rate_hz) if predict_now else track
         if not isinstance(lanes, int) or lanes < 1:
             raise StreamError("lanes must be a positive integer, got %r" % (lanes,))
@@ -369,6 +380,10 @@ class PoseStream:
                 self._cov = torch.empty((lanes, self.K, 3), dtype=torch.float32, device=dev)
                 self._status = torch.empty((lanes, self.K), dtype=torch.int32, device=dev)
                 self._tstate = F_.pose_track_state(lanes * self.K, dev)
+            self._history = None
+            if history:
+                from .smooth import TrackHistory
+                self._history = TrackHistory((lanes, self.K), dev)
             self._done = torch.cuda.Event()
         self._graphs = {}              # "host" / "device" input -> (CUDAGraph, (heatmap, gcn_heatmap))
         self._eager_emits = 0
@@ -450,6 +465,8 @@ class PoseStream:
             self._busy = False
 
     def _frame(self, center, out):
+        if self._history is not None:                          # the emitted pose into the history: eager copies behind the launches
+            self._history.append(self._tstate, self._status, self._kp, self._raw, self._mx)
         if self.track is not None:
             return TrackedPoseFrame(center, self._kp, self._mx, self._idx, out[0], out[1], self._raw, self._vel, self._cov, self._fc,
                                     self._status)
@@ -488,8 +505,8 @@ class PoseStream:
             if host:
                 self._done.record()
                 self._busy = True
-        due = self.schedule.push()
-        return None if due is None else self._frame(due[0], out)
+            due = self.schedule.push()
+            return None if due is None else self._frame(due[0], out)
 
     def flush(self):
         frames = []
@@ -509,6 +526,17 @@ class PoseStream:
             if self._tstate is not None:
                 self._tstate.zero_()                           # likewise: the next usable measurement of a joint starts its track
         self.schedule.reset()
+        if self._history is not None:
+            self._history.clear()
+
+    def smoothed(self):
+        """The poses emitted since the last ``reset()``, smoothed backwards over the tracker's recorded states -> a
+        ``SmoothedSequence`` of (T, lanes, K, ...) device tensors, T = the number of poses emitted (tools/smooth.py).  One launch,
+        no sync; needs ``history=True`` and at least one emitted pose."""
+        if self._history is None:
+            raise TrackingError("smoothed() needs a session built with track=... and history=True")
+        with torch.cuda.device(self.device):
+            return self._history.smooth(self.track)
 
 
 # ---- command ---------------------------------------------------------------------------------------------------------------------
@@ -533,6 +561,8 @@ def parse(argv=None):
     p.add_argument("--accel-psd", type=float, default=None, help="with --track: white-acceleration power, pixel^2 / s^3 (default 200)")
     p.add_argument("--gate", type=float, default=None, help="with --track: largest accepted squared Mahalanobis distance (default 13.816)")
     p.add_argument("--max-coast", type=int, default=None, help="with --track: frames a track survives without a measurement (default 5)")
+    p.add_argument("--rts", action="store_true", help="with --track: after the flush, smooth the whole recording backwards (Rauch-Tung-"
+                   "Striebel); every record gains smoothed, smoothed_velocity, smoothed_covariance and smoothed_flag")
     p.add_argument("--tdm-compensation", action="store_true", help="compensate the TDM Doppler phase in the FFT chain (weights trained "
                    "with DATASET.tdmCompensation)")
     p.add_argument("--weights", choices=WEIGHTS, default="live", help="live: model_state_dict as trained; averaged: ema_state_dict "
@@ -552,7 +582,7 @@ def parse(argv=None):
         p.error("--decode-radius must be 0 (the whole map) or a positive number of heat-map pixels")
     if not args.track:
         for flag, given in (("--predict-now", args.predict_now), ("--accel-psd", args.accel_psd is not None),
-                            ("--gate", args.gate is not None), ("--max-coast", args.max_coast is not None)):
+                            ("--gate", args.gate is not None), ("--max-coast", args.max_coast is not None), ("--rts", args.rts)):
             if given:
                 p.error("%s needs --track" % flag)
     return args
@@ -564,6 +594,19 @@ def tracking_from_args(args):
         return None
     kw = {k: getattr(args, k) for k in ("accel_psd", "gate", "max_coast") if getattr(args, k) is not None}
     return PoseTracking(args.rate, **kw)
+
+
+def add_smoothed(records, seq, lane=0):
+    """--rts: the smoothed pose of ``lane`` of a SmoothedSequence into the records of the same frames, in place."""
+    seq = seq.cpu()
+    if len(seq) != len(records):
+        raise ValueError("%d smoothed frames for %d records" % (len(seq), len(records)))
+    for k, rec in enumerate(records):
+        rec["smoothed"] = [[float(x), float(y)] for x, y in seq.keypoints[k, lane].numpy()]
+        rec["smoothed_velocity"] = [[float(vx), float(vy)] for vx, vy in seq.velocity[k, lane].numpy()]
+        rec["smoothed_covariance"] = [[float(v) for v in c] for c in seq.covariance[k, lane].numpy()]
+        rec["smoothed_flag"] = [int(c) for c in seq.flag[k, lane].numpy()]
+    return records
 
 
 def load_model_best(model, log_dir, device, weights="live", tdm_compensation=False):
@@ -620,7 +663,8 @@ def main(argv=None):
     n = min(frames[0].shape[0], frames[1].shape[0])
     session = PoseStream(model, cfg, lanes=1, lookahead=args.lookahead, graph=not args.no_graph, device=dev, decode=args.decode,
                          smooth=PoseSmoothing(args.rate) if args.smooth else None, track=tracking_from_args(args),
-                         predict_now=args.predict_now, decode_radius=args.decode_radius, tdm_compensation=args.tdm_compensation)
+                         predict_now=args.predict_now, decode_radius=args.decode_radius, tdm_compensation=args.tdm_compensation,
+                         history=args.rts)
     records = []
 
     def record(pf):
@@ -639,6 +683,8 @@ def main(argv=None):
             record(pf)
     for pf in session.flush():
         record(pf)
+    if args.rts and records:
+        add_smoothed(records, session.smoothed())
     with open(args.out, "w") as fp:
         json.dump(records, fp)
     print("%d frames -> %s" % (len(records), args.out))

@@ -444,6 +444,41 @@ int hupr_pose_track_f32(const float* heat, long rows, int H, int W, float ratio,
                         float accel_psd, float meas_std, float heatmap_gain, float gate, int max_coast, float init_speed_std,
                         float min_score, float horizon_s, int* idx, float* maxval, float* raw_keypoints, float* keypoints,
                         float* velocity, float* covariance, float* forecast, int* status, hupr_stream_t stream);
+/* Fixed-interval Rauch-Tung-Striebel smoother over a recorded run of hupr_pose_track_f32 in one launch (csrc/pose_smooth.hip; Rauch,
+ * Tung & Striebel 1965): the backward pass over the states the filter left behind, so that the answer for frame k uses the frames
+ * after it too.  New, no reference counterpart.  One thread per row, sequential in the frame: a latency-bound recurrence of T
+ * dependent steps, the rows axis being there so that many sequences (sequences x joints) share one launch.  No LDS, no atomics, no
+ * scratch: every output is bit-identical from run to run and independent of the other rows.
+ * states    : float [T][rows][16].  Entry k is a copy of the tracker's state tensor right after the hupr_pose_track_f32 launch of
+ *             frame k, in that entry's layout (x, y, vx, vy, the upper triangle of P row by row, live, coast).  16-byte aligned.
+ * status    : int [T][rows], keypoints : float [T][rows][2]: the tracker's status and filtered keypoints of every frame.
+ * rate_hz, accel_psd : those of the filter run; F and Q below are hupr_pose_track_f32's, dt = 1 / rate_hz.
+ * Per row, for k = T-1 down to 0, with x_k, P_k the state of entry k and xs, Ps the smoothed state:
+ *   status[k] == HUPR_TRACK_LOST: smoothed = keypoints[k] bit for bit, velocity and covariance 0, flag HUPR_SMOOTH_PASSTHROUGH; frame
+ *     k-1 has no successor.
+ *   Otherwise, and k == T-1 or status[k+1] is HUPR_TRACK_STARTED or HUPR_TRACK_LOST: the end of a track segment.  xs_k = x_k,
+ *     Ps_k = P_k bit for bit, flag HUPR_SMOOTH_END.  (A caller separates two recordings by zeroing the tracker state between them: the
+ *     next status is then STARTED or LOST, and the chain breaks by itself.)
+ *   Otherwise, in this order:
+ *     xp = F x_k, Pp = F P_k F^T + Q;
+ *     Cholesky Pp = L L^T;
+ *     C = P_k F^T Pp^-1, every row by a forward and a backward triangular solve with L;
+ *     xs_k = x_k + C (xs_{k+1} - xp);
+ *     Ps_k = P_k + C (Ps_{k+1} - Pp) C^T, then (Ps_k + Ps_k^T) / 2;
+ *     flag HUPR_SMOOTH_SMOOTHED.
+ *     If a pivot of the Cholesky factorisation is not positive and finite, or an entry of xs_k or Ps_k is not finite: xs_k = x_k,
+ *     Ps_k = P_k, flag HUPR_SMOOTH_DEGENERATE, and the chain goes on from those values.  (P_k = 0 alone is not degenerate while
+ *     accel_psd > 0: Pp = Q is then positive definite, C = 0 and the frame keeps x_k, P_k as SMOOTHED.)
+ * Outputs: smoothed [T][rows][2] = (xs[0], xs[1]); velocity [T][rows][2] = (xs[2], xs[3]) per second; covariance [T][rows][3] =
+ *   (Ps00, Ps01, Ps11), the position block; flag [T][rows] int.
+ * Returns -1 (HUPR_ERR_ARG) before any launch for a null pointer, T < 1, rows < 0, T * rows beyond 2^31, states not 16-byte aligned,
+ * rate_hz not positive and finite, accel_psd negative or not finite.  rows == 0 with T >= 1 is a no-op. */
+#define HUPR_SMOOTH_SMOOTHED 0
+#define HUPR_SMOOTH_END 1
+#define HUPR_SMOOTH_PASSTHROUGH 2
+#define HUPR_SMOOTH_DEGENERATE 3
+int hupr_pose_smooth_rts_f32(const float* states, const int* status, const float* keypoints, long T, long rows, float rate_hz,
+                             float accel_psd, float* smoothed, float* velocity, float* covariance, int* flag, hupr_stream_t stream);
 
 /* tri-/bilinear align_corners=True resampling (models/layers.py:84,89,199,204; gcn_networks.py:49,63) */
 int hupr_interp_linear_fwd_f32(const float* x, float* y, int Bn, int Di, int Hi, int Wi, int Do, int Ho, int Wo,
