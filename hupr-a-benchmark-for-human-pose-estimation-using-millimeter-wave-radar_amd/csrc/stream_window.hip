@@ -6,18 +6,11 @@
 //     number and one captured graph serves every frame), the reset, and the arg-max -> image-pixel keypoint decode
 //     [misc/metrics.py:10-38 times imgSize / heatmapSize, tools/run.py:47-53]
 #include "hupr_common.h"
+#include "stream_state.h"      // StreamState: the device-resident session state
 
 namespace hupr {
 
 constexpr int kSNF = 32;      // MNet filters (spatial.hip kNF)
-
-// Device-resident session state: frames = sensor-frames pushed so far (= the number of the next frame), emitted = poses emitted so
-// far (= the number of the next centre frame once the stream runs; the flush centres count on from it).
-struct StreamState {
-    int frames;
-    int emitted;
-    int pad[2];
-};
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 

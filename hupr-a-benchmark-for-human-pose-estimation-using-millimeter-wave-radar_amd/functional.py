@@ -2103,3 +2103,82 @@ def pose_smooth_rts(states, status, keypoints, tracking):
                                                float(tracking.accel_psd), rt.ptr(smoothed), rt.ptr(vel), rt.ptr(cov), rt.ptr(flag),
                                                rt.stream()))
     return smoothed, vel, cov, flag
+
+
+# ---- scene occupancy: CA-CFAR detection on the mean planes, presence gate (csrc/cfar.hip) -----------------------------------------------
+CFAR_SUMMARY = ("count", "peak_snr", "peak_f", "peak_r", "peak_a", "centroid_r", "centroid_a", "doppler")
+
+
+class CfarResult:
+    """What ``cfar_ra`` returns.  ``summary`` (..., 8) fp32, the fields of ``CFAR_SUMMARY`` (also as attributes: ``result.count`` is
+    ``summary[..., 0]``); ``mask`` uint8 and ``snr`` fp32, (..., 8, 64, 64) each, None unless asked for; ``pfa``, ``guard``, ``train``
+    the settings of the run.  Device tensors."""
+    __slots__ = ("summary", "mask", "snr", "pfa", "guard", "train")
+
+    def __init__(self, summary, mask, snr, pfa, guard, train):
+        self.summary, self.mask, self.snr, self.pfa, self.guard, self.train = summary, mask, snr, pfa, guard, train
+
+    def __getattr__(self, name):
+        if name in CFAR_SUMMARY:
+            return self.summary[..., CFAR_SUMMARY.index(name)]
+        raise AttributeError(name)
+
+
+_CFAR_TABLES = {}
+
+
+def cfar_table(pfa, guard, train, device):
+    """The fp32 device copy of ``preprocessing.cfar_alpha_table(pfa, guard, train)``, uploaded once per setting and device."""
+    from .preprocessing.cfar import cfar_alpha_table, check_cfar
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    key = check_cfar(pfa, guard, train) + (device,)
+    if key not in _CFAR_TABLES:
+        _CFAR_TABLES[key] = torch.from_numpy(cfar_alpha_table(*key[:3]).astype(np.float32)).to(device)
+    return _CFAR_TABLES[key]
+
+
+def cfar_ra(planes, pfa=1e-5, guard=2, train=4, want_mask=True, want_snr=False):
+    """CA-CFAR detection on the (range, azimuth) maps of the seven moving Doppler slots of ``planes`` (..., 16, 64, 64) fp32 GPU, the
+    elevation-mean planes of ``preprocessing.fft_chain_loader_means`` -> ``CfarResult`` in one launch (csrc/cfar.hip; the rule is
+    stated beside hupr_cfar_ra_f32 in include/hupr.h).  Device tensors, no sync."""
+    from .preprocessing.cfar import check_cfar
+    pfa, guard, train = check_cfar(pfa, guard, train)
+    if not isinstance(planes, torch.Tensor) or planes.dtype != torch.float32 or planes.dim() < 3 or tuple(planes.shape[-3:]) != (16, 64, 64):
+        raise ValueError("cfar_ra needs fp32 planes (..., 16, 64, 64), got %s %r" % (getattr(planes, "dtype", type(planes).__name__),
+                                                                                   tuple(getattr(planes, "shape", ()))))
+    if not planes.is_cuda:
+        raise rt.HuprError("cfar_ra needs GPU planes (no CPU fallback), got %s" % planes.device)
+    planes = _c(planes)
+    lead = tuple(planes.shape[:-3])
+    n = int(np.prod(lead, dtype=np.int64))
+    dev = planes.device
+    with torch.cuda.device(dev):
+        table = cfar_table(pfa, guard, train, dev)
+        summary = torch.empty(lead + (8,), dtype=torch.float32, device=dev)
+        mask = torch.empty(lead + (8, 64, 64), dtype=torch.uint8, device=dev) if want_mask else None
+        snr = torch.empty(lead + (8, 64, 64), dtype=torch.float32, device=dev) if want_snr else None
+        rt.check(rt.lib().hupr_cfar_ra_f32(rt.ptr(planes), n, guard, train, rt.ptr(table), table.numel(), rt.ptr(mask), rt.ptr(snr),
+                                           rt.ptr(summary), rt.stream()))
+    return CfarResult(summary, mask, snr, pfa, guard, train)
+
+
+def presence_state(lanes, device):
+    """A zeroed presence-gate state: int32 (lanes, 4) = (present, hits, misses, frames)."""
+    return torch.zeros((lanes, 4), dtype=torch.int32, device=device)
+
+
+def presence_update(summary, gate_state, min_cells=3, confirm=2, hold=20):
+    """One frame of the presence gate (hupr_presence_update in include/hupr.h): ``summary`` (lanes, 8) fp32 of ``cfar_ra``,
+    ``gate_state`` (``presence_state``, advanced in place) -> present int32 (lanes,).  Device tensors, no sync."""
+    if summary.dtype != torch.float32 or summary.dim() != 2 or summary.shape[1] != 8:
+        raise ValueError("presence_update needs the (lanes, 8) fp32 summary of cfar_ra, got %s %r" % (summary.dtype, tuple(summary.shape)))
+    lanes = summary.shape[0]
+    if gate_state.dtype != torch.int32 or tuple(gate_state.shape) != (lanes, 4) or gate_state.device != summary.device:
+        raise ValueError("gate_state must be the int32 tensor presence_state(%d, device) returns" % lanes)
+    present = torch.empty(lanes, dtype=torch.int32, device=summary.device)
+    with torch.cuda.device(summary.device):
+        rt.check(rt.lib().hupr_presence_update(rt.ptr(_c(summary)), lanes, int(min_cells), int(confirm), int(hold), rt.ptr(gate_state),
+                                               rt.ptr(present), rt.stream()))
+    return present

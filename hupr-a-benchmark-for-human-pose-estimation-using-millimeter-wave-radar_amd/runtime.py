@@ -63,6 +63,12 @@ SIGNATURES = {
                             [c_float] * 3 + [c_void_p] * 9),
     # Rauch-Tung-Striebel smoother over a recorded run of the tracker (csrc/pose_smooth.hip)
     "hupr_pose_smooth_rts_f32": (c_int, [c_void_p] * 3 + [c_long, c_long, c_float, c_float] + [c_void_p] * 5),
+    # scene occupancy: CA-CFAR detection on the mean planes and the presence gate (csrc/cfar.hip); the table of the first two is host memory
+    "hupr_cfar_table_len": (c_int, [c_int, c_int]),
+    "hupr_cfar_alpha_table_f32": (c_int, [ctypes.c_double, c_int, c_int, ctypes.POINTER(c_float), c_int]),
+    "hupr_cfar_ra_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int] + [c_void_p] * 4),
+    "hupr_cfar_ra_stream_f32": (c_int, [c_void_p, c_void_p] + [c_int] * 6 + [c_void_p, c_int] + [c_void_p] * 4),
+    "hupr_presence_update": (c_int, [c_void_p] + [c_int] * 4 + [c_void_p] * 3),
     "hupr_fft_chain_opts": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "hupr_fft_chain_tdm": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "hupr_loader_normalize_c64": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),

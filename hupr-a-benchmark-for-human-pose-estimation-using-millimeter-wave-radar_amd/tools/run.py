@@ -22,6 +22,7 @@ from .augment import flip_setting
 from .base import BaseRunner
 from .engine import TrainEngine
 from .smooth import SequenceSmoother, SequenceWalker, jitter, temporal_setting
+from .stream import presence_setting
 
 
 def _collate(batch):
@@ -67,6 +68,10 @@ class Runner(BaseRunner):
         if self.temporal is not None and self.world > 1:
             raise RuntimeError("TEST.temporal: %s needs a single process: the evaluation is sharded over the %d ranks sample by sample, "
                                "which would split every sequence" % (self.temporal.mode, self.world))
+        self.presence = presence_setting(cfg)   # TEST.presence: eval() runs the CA-CFAR detector and the presence gate (csrc/cfar.hip)
+        if self.presence is not None and self.world > 1:
+            raise RuntimeError("TEST.presence needs a single process: the evaluation is sharded over the %d ranks sample by sample, "
+                               "which would split every sequence" % self.world)
         if not args.eval:
             self.trainSet = getDataset("train", cfg, args)
             if isinstance(self.trainSet, HuPRRawADC):
@@ -110,6 +115,13 @@ class Runner(BaseRunner):
             return self.engine.preprocess(*self._adc(batch))
         return batch["VRDAEmap_hori"].float().to(dev), batch["VRDAEmap_vert"].float().to(dev)
 
+    def _centre_planes(self, hori):
+        """The horizontal network input of a batch, (B, G, 16, R, A) mean planes or the (B, G, F, 2, R, A, E) cube (averaged over its
+        elevation axis here, as HuPRNet.forward does first) -> the (B, 16, R, A) mean planes of window position G / 2, the labelled frame."""
+        if hori.dim() == 7:
+            hori = hori.mean(dim=-1).reshape(hori.shape[0], hori.shape[1], 16, hori.shape[4], hori.shape[5])
+        return hori[:, hori.shape[1] // 2].contiguous()
+
     def eval(self, visualization=True, epoch=-1):
         """-> AP (reference tools/run.py:35-63).  Predictions are decoded from the GCN head, scaled to image pixels,
         written to ``<phase>_results.json`` by rank 0 and scored with the OKS evaluator against the ground truth the
@@ -124,15 +136,26 @@ class Runner(BaseRunner):
         second-head maps go through ``SequenceSmoother.track`` one frame per call, and the keypoints written and scored are the
         Kalman-filtered ones (``track``) or the Rauch-Tung-Striebel smoothed ones (``rts``).  After the AP line come an ``MPJPE``
         line for the raw, the filtered and (``rts``) the smoothed keypoints and a ``Jitter`` line (``tools.smooth.jitter``) for each
-        of them and for the ground truth."""
+        of them and for the ground truth.
+        ``TEST.presence`` (``tools.stream.presence_setting``): the test set is walked as sequences in the same way, the CA-CFAR
+        detector (``functional.cfar_ra``) runs on the horizontal mean planes of every sample's labelled frame (window position G / 2)
+        and the presence gate across each sequence, and one more line is printed: ``Presence: <share> of <n> labelled frames present,
+        median <m> detections``.  Every labelled frame has a person in it, so the share's complement is the gate's miss rate.  Raw
+        ADC batches and stored cubes both work.  Keypoints and AP are what they are without the key."""
         self.logger.clear(len(self.testLoader.dataset))
         savePreds, gts = [], []
         temporal = self.temporal
         if temporal is not None:
             smoother = SequenceSmoother(temporal.tracking, self.numKeypoints, self.engine.device)
             walker, boxes, ids = SequenceWalker(), [], []
+        gate = self.presence
+        if gate is not None:
+            from .. import functional as F_
+            gate_state = F_.presence_state(1, self.engine.device)
+            gate_walker, gate_present, gate_counts = SequenceWalker(), [], []
         for batch in self.testLoader:
             keypoints = batch["jointsGroup"]
+            hori = None
             if self.flip:
                 # TEST.flip: the mirror of this radar is a permutation of the raw cube (tools/augment.py), so stored cubes cannot take it
                 if "adc_hori" not in batch:
@@ -141,6 +164,15 @@ class Runner(BaseRunner):
             else:
                 hori, vert = self._inputs(batch)
                 preds = self.engine.infer(hori, vert)
+            if gate is not None:
+                if hori is None:                    # the flip test ran from the raw cubes
+                    hori = self._inputs(batch)[0]
+                occ = F_.cfar_ra(self._centre_planes(hori), gate.pfa, gate.guard, gate.train, want_mask=False).summary
+                for j in range(keypoints.size(0)):
+                    if gate_walker.step(batch["imageId"][j]):
+                        gate_state.zero_()
+                    gate_present.append(F_.presence_update(occ[j:j + 1], gate_state, gate.min_cells, gate.confirm, gate.hold))
+                gate_counts.append(occ[:, 0])
             with torch.no_grad():
                 loss, loss2, pred2d, _ = self.lossComputer.computeLoss(preds, loss_labels(batch, self.lossComputer.targets_mode))
             self.logger.display(loss, loss2, keypoints.size(0), epoch)
@@ -199,6 +231,12 @@ class Runner(BaseRunner):
                     print("MPJPE %s: %.3f px (n = %d)" % ((name,) + mean_position_error(gts, self.saveKeypoints([], kp, boxes, ids))[::2]))
                 for name, kp in list(tracks.items()) + [("truth", visited)]:
                     print("Jitter %s: %.3f px" % (name, jitter([kp[a:b] for a, b in walker.segments()])))
+            if gate is not None:
+                present = torch.cat(gate_present).cpu().numpy() if gate_present else np.zeros(0, np.int32)
+                counts = torch.cat(gate_counts).cpu().numpy() if gate_counts else np.zeros(0, np.float32)
+                print("Presence: %.3f of %d labelled frames present, median %g detections" % (
+                    float(present.mean()) if present.size else float("nan"), present.size,
+                    float(np.median(counts)) if counts.size else float("nan")))
         if self.world > 1:
             box = [ap]
             dist.broadcast_object_list(box, src=0)

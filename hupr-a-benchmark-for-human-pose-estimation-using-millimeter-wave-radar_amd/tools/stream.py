@@ -28,6 +28,11 @@ radius; 0: the whole map) — what the integral coordinate loss trains — in on
                                     [--lookahead N] [--math f32|bf16] [--no-graph] [--out poses.json]
                                     [--decode argmax|subpixel|integral [--decode-radius N]] [--smooth --rate FPS]
                                     [--track --rate FPS [--predict-now] [--accel-psd Q] [--gate D2] [--max-coast N] [--rts]]
+                                    [--presence [--pfa X] [--cfar-guard N] [--cfar-train N] [--min-cells N] [--confirm N] [--hold N]]
+
+``presence=PresenceGate(...)`` / ``--presence``: scene occupancy.  A CA-CFAR detector on the centre frame's horizontal mean planes and a
+presence gate over its detections (csrc/cfar.hip) tell whether a mover stands in front of the radar; every emitted frame and every
+record gains ``present`` and ``occupancy``.  It reports only, the pose is what it is without it.
 
 ``--rts`` (with ``--track``): the capture is a finished file, so after the flush the recorded tracker states go through the
 Rauch-Tung-Striebel smoother (tools/smooth.py, csrc/pose_smooth.hip) and every record gains the smoothed pose.
@@ -79,6 +84,10 @@ class SmoothingError(StreamError):
 class TrackingError(StreamError):
     """A ``PoseTracking`` parameter out of range, ``track`` is not a ``PoseTracking``, ``track`` together with ``smooth`` or with
     ``decode="integral"``, or ``predict_now`` without ``track``."""
+
+
+class PresenceError(StreamError):
+    """A ``PresenceGate`` parameter out of range, or ``presence`` is not a ``PresenceGate``."""
 
 
 DECODES = ("argmax", "subpixel", "integral")
@@ -145,6 +154,72 @@ class PoseTracking:
     def with_horizon(self, horizon_s):
         """A copy that forecasts ``horizon_s`` seconds ahead."""
         return PoseTracking(**dict({k: getattr(self, k) for k in self.__slots__}, horizon_s=horizon_s))
+
+
+class PresenceGate:
+    """Scene-occupancy settings of a session (frozen; the rule is stated beside hupr_cfar_ra_f32 in include/hupr.h).  The CA-CFAR
+    detector on the centre frame's horizontal mean planes: ``pfa`` the design false-alarm probability per cell, ``guard`` and ``train``
+    the half-widths of the guard area and of the training area beyond it (``guard + train <= 8``).  The gate over its detections: a
+    frame is a hit when it holds at least ``min_cells`` detections; an absent lane becomes present after ``confirm`` consecutive
+    hits, a present lane absent after more than ``hold`` consecutive misses — a person who stands still vanishes under clutter
+    removal, and ``hold`` bridges the pause.  The six defaults are guesses: nobody has run this on a real capture."""
+    __slots__ = ("pfa", "guard", "train", "min_cells", "confirm", "hold")
+
+    def __init__(self, pfa=1e-5, guard=2, train=4, min_cells=3, confirm=2, hold=20):
+        from ..preprocessing.cfar import check_cfar
+        try:
+            pfa, guard, train = check_cfar(pfa, guard, train)
+        except ValueError as e:
+            raise PresenceError("PresenceGate: %s" % e) from None
+        for k, v, lo in (("min_cells", min_cells, 1), ("confirm", confirm, 1), ("hold", hold, 0)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v < 2 ** 31:
+                raise PresenceError("PresenceGate.%s must be an integer >= %d, got %r" % (k, lo, v))
+        for k, v in (("pfa", pfa), ("guard", guard), ("train", train), ("min_cells", int(min_cells)), ("confirm", int(confirm)),
+                     ("hold", int(hold))):
+            object.__setattr__(self, k, v)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("PresenceGate is frozen")
+
+    def __delattr__(self, name):
+        raise AttributeError("PresenceGate is frozen")
+
+    def __eq__(self, other):
+        return isinstance(other, PresenceGate) and all(getattr(self, k) == getattr(other, k) for k in self.__slots__)
+
+    def __hash__(self):
+        return hash(tuple(getattr(self, k) for k in self.__slots__))
+
+    def __repr__(self):
+        return "PresenceGate(%s)" % ", ".join("%s=%r" % (k, getattr(self, k)) for k in self.__slots__)
+
+
+def check_presence(presence):
+    """The session's ``presence`` argument: None or a PresenceGate."""
+    if presence is not None and not isinstance(presence, PresenceGate):
+        raise PresenceError("presence must be a PresenceGate or None, got %r" % (presence,))
+    return presence
+
+
+def presence_setting(cfg):
+    """``TEST.presence`` (no key of the reference's YAML) -> None with the key absent or ``false``, ``PresenceGate()`` with ``true``, a
+    PresenceGate of the given values with a mapping of its six names.  Anything else raises here, where the config is read."""
+    v = getattr(getattr(cfg, "TEST", None), "presence", None)
+    if v is None or v is False:
+        return None
+    if v is True:
+        return PresenceGate()
+    if not isinstance(v, dict):                         # config_tree.obj: a YAML mapping as attributes
+        if not hasattr(v, "__dict__") or isinstance(v, type):
+            raise ValueError("TEST.presence must be true, false or a mapping of PresenceGate arguments, got %r" % (v,))
+        v = vars(v)
+    for k in v:
+        if k not in PresenceGate.__slots__:
+            raise ValueError("TEST.presence.%s is no PresenceGate argument (%s)" % (k, ", ".join(PresenceGate.__slots__)))
+    try:
+        return PresenceGate(**dict(v))
+    except PresenceError as e:
+        raise ValueError("TEST.presence: %s" % e) from None
 
 
 def check_decode(decode, smooth, decode_radius=None, heatmap_size=None):
@@ -251,22 +326,33 @@ class StreamSchedule:
         return out
 
 
-class PoseFrame:
+class _OccupancyFields:
+    """The two fields a session with ``presence`` adds to every frame it emits (a base class of their own, so that ``PoseFrame.__slots__``
+    and ``TrackedPoseFrame.__slots__`` list what they always listed)."""
+    __slots__ = ("present", "occupancy")
+
+
+class PoseFrame(_OccupancyFields):
     """One emitted pose.  ``frame``: its number in the stream; ``keypoints`` (lanes, K, 2) fp32 image pixels (x, y) — the One-Euro
     filtered ones when the session smooths; ``scores`` (lanes, K) the GCN head's maxima; ``indices`` (lanes, K) int32 arg-max
     positions; ``heatmap`` (lanes, K, 1, H, W) and ``gcn_heatmap`` (lanes, 1, K, H, W); ``raw_keypoints`` the decoded keypoints in
     front of the filter (``keypoints`` itself without one); ``velocity`` (lanes, K, 2) image pixels per second, None without a
-    filter.  Device tensors owned by the session, valid until its next push / flush / reset."""
+    filter; ``present`` (lanes,) int32, the presence gate's verdict on this frame, and ``occupancy`` (lanes, 8) fp32, the detector's
+    summary of it (``functional.CFAR_SUMMARY``), both None in a session without ``presence``.  Device tensors owned by the session,
+    valid until its next push / flush / reset."""
     __slots__ = ("frame", "keypoints", "scores", "indices", "heatmap", "gcn_heatmap", "raw_keypoints", "velocity")
 
-    def __init__(self, frame, keypoints, scores, indices, heatmap, gcn_heatmap, raw_keypoints=None, velocity=None):
+    def __init__(self, frame, keypoints, scores, indices, heatmap, gcn_heatmap, raw_keypoints=None, velocity=None, present=None,
+                 occupancy=None):
         self.frame, self.keypoints, self.scores, self.indices = frame, keypoints, scores, indices
         self.heatmap, self.gcn_heatmap = heatmap, gcn_heatmap
         self.raw_keypoints = keypoints if raw_keypoints is None else raw_keypoints
         self.velocity = velocity
+        self.present, self.occupancy = present, occupancy
 
     def _map(self, fn):
-        return PoseFrame(self.frame, *[None if getattr(self, k) is None else fn(getattr(self, k)) for k in self.__slots__[1:]])
+        return PoseFrame(self.frame, *[None if getattr(self, k) is None else fn(getattr(self, k))
+                                       for k in PoseFrame.__slots__[1:] + _OccupancyFields.__slots__])
 
     def clone(self):
         return self._map(torch.clone)
@@ -283,13 +369,14 @@ class TrackedPoseFrame(PoseFrame):
     __slots__ = ("covariance", "forecast", "status")
     STATUS = ("UPDATED", "COASTED_MISSING", "COASTED_GATED", "STARTED", "LOST")
 
-    def __init__(self, frame, keypoints, scores, indices, heatmap, gcn_heatmap, raw_keypoints, velocity, covariance, forecast, status):
-        super().__init__(frame, keypoints, scores, indices, heatmap, gcn_heatmap, raw_keypoints, velocity)
+    def __init__(self, frame, keypoints, scores, indices, heatmap, gcn_heatmap, raw_keypoints, velocity, covariance, forecast, status,
+                 present=None, occupancy=None):
+        super().__init__(frame, keypoints, scores, indices, heatmap, gcn_heatmap, raw_keypoints, velocity, present, occupancy)
         self.covariance, self.forecast, self.status = covariance, forecast, status
 
     def _map(self, fn):
         return TrackedPoseFrame(self.frame, *[None if getattr(self, k) is None else fn(getattr(self, k))
-                                              for k in PoseFrame.__slots__[1:] + self.__slots__])
+                                              for k in PoseFrame.__slots__[1:] + self.__slots__ + _OccupancyFields.__slots__])
 
 
 class PoseStream:
@@ -316,10 +403,15 @@ class PoseStream:
     ``history=True`` (needs ``track``): after every push or flush that emits a pose the tracker's state and outputs are copied into a
     history on the device (tools/smooth.py: TrackHistory) — eager device-to-device copies on the session's stream, behind the graph
     replay and not inside it — and ``smoothed()`` returns the Rauch-Tung-Striebel smoothed poses emitted since the last ``reset()``
-    in one launch of csrc/pose_smooth.hip.  The default adds nothing."""
+    in one launch of csrc/pose_smooth.hip.  The default adds nothing.
+    ``presence=PresenceGate(...)``: scene occupancy.  Behind the window MNet of every push or flush that emits a pose, a CA-CFAR
+    detector runs on the centre frame's horizontal mean planes, read from the ring, and a presence gate runs over its detections
+    (csrc/cfar.hip: two launches, inside the graph replay); the emitted frame gains ``present`` and ``occupancy``, and ``reset()``
+    clears the gate.  The gate reports only: keypoints, scores and the tracker's input are what they are without it, bit for bit.
+    (Feeding absence to the tracker as a missing measurement is left to a later change.)  It composes with every other setting."""
 
     def __init__(self, model, cfg, lanes=1, lookahead=None, graph=True, device=None, decode="argmax", smooth=None, track=None,
-                 predict_now=False, decode_radius=None, tdm_compensation=False, history=False):
+                 predict_now=False, decode_radius=None, tdm_compensation=False, history=False, presence=None):
         D = cfg.DATASET
         self.G = D.numGroupFrames
         self.schedule = StreamSchedule(self.G, lookahead)
@@ -335,6 +427,7 @@ class PoseStream:
         if history and track is None:
             raise TrackingError("history needs track: it records the tracker's states for smoothed()")
         self.track = track.with_horizon(self.lookahead / track.rate_hz) if predict_now else track
+        self.presence = check_presence(presence)
         if not isinstance(lanes, int) or lanes < 1:
             raise StreamError("lanes must be a positive integer, got %r" % (lanes,))
         self.device = torch.device(device) if device is not None else next(model.parameters()).device
@@ -384,6 +477,13 @@ class PoseStream:
             if history:
                 from .smooth import TrackHistory
                 self._history = TrackHistory((lanes, self.K), dev)
+            # scene occupancy (csrc/cfar.hip): the threshold table, the detector's summary, the gate's state and verdict
+            self._alpha = self._occ = self._gstate = self._present = None
+            if presence is not None:
+                self._alpha = F_.cfar_table(presence.pfa, presence.guard, presence.train, dev)
+                self._occ = torch.zeros((lanes, 8), dtype=torch.float32, device=dev)
+                self._gstate = F_.presence_state(lanes, dev)
+                self._present = torch.zeros(lanes, dtype=torch.int32, device=dev)
             self._done = torch.cuda.Event()
         self._graphs = {}              # "host" / "device" input -> (CUDAGraph, (heatmap, gcn_heatmap))
         self._eager_emits = 0
@@ -399,8 +499,9 @@ class PoseStream:
         return self.schedule.frames_emitted
 
     # -- launches -------------------------------------------------------------------------------------------------------------
-    def _front(self, flush):
-        """FFT chain to means on the 2 x lanes new sensor-frames (not for a flush), the window MNet, the state advance."""
+    def _front(self, flush, emit=True):
+        """FFT chain to means on the 2 x lanes new sensor-frames (not for a flush), the window MNet, with ``presence`` the detector
+        and the gate on the centre frame (only where a pose is due: ``emit``), the state advance."""
         from ..preprocessing import process_iwr1843 as pre
         L, s = rt.lib(), rt.stream()
         if not flush:
@@ -419,6 +520,13 @@ class PoseStream:
         rt.check(fn(None if flush else rt.ptr(self._staging), rt.ptr(self._ring), rt.ptr(self._state), self.lookahead, int(flush),
                     rt.ptr(ra.weight), rt.ptr(ra.bias), rt.ptr(re.weight), rt.ptr(re.bias), rt.ptr(self._maps[0]),
                     rt.ptr(self._maps[1]), self.lanes, self.G, self.pixels, s))
+        g = self.presence
+        if g is not None and emit:                 # the centre frame is in the ring by now, and the counters still name it
+            rt.check(L.hupr_cfar_ra_stream_f32(rt.ptr(self._ring), rt.ptr(self._state), self.lookahead, int(flush), self.lanes, self.G,
+                                               g.guard, g.train, rt.ptr(self._alpha), self._alpha.numel(), None, None,
+                                               rt.ptr(self._occ), s))
+            rt.check(L.hupr_presence_update(rt.ptr(self._occ), self.lanes, g.min_cells, g.confirm, g.hold, rt.ptr(self._gstate),
+                                            rt.ptr(self._present), s))
         rt.check(L.hupr_stream_advance(rt.ptr(self._state), self.lookahead, int(flush), s))
 
     def _back(self):
@@ -469,8 +577,8 @@ class PoseStream:
             self._history.append(self._tstate, self._status, self._kp, self._raw, self._mx)
         if self.track is not None:
             return TrackedPoseFrame(center, self._kp, self._mx, self._idx, out[0], out[1], self._raw, self._vel, self._cov, self._fc,
-                                    self._status)
-        return PoseFrame(center, self._kp, self._mx, self._idx, out[0], out[1], self._raw, self._vel)
+                                    self._status, self._present, self._occ)
+        return PoseFrame(center, self._kp, self._mx, self._idx, out[0], out[1], self._raw, self._vel, self._present, self._occ)
 
     # -- public ---------------------------------------------------------------------------------------------------------------
     def push(self, adc_hori, adc_vert):
@@ -497,7 +605,7 @@ class PoseStream:
             else:
                 if host:
                     self._adc.copy_(self._pinned, non_blocking=True)
-                self._front(False)
+                self._front(False, emit)
                 out = None
                 if emit:
                     out = self._back()
@@ -525,6 +633,8 @@ class PoseStream:
                 self._fstate.zero_()                           # "never seen": the next valid sample of a joint starts its filter
             if self._tstate is not None:
                 self._tstate.zero_()                           # likewise: the next usable measurement of a joint starts its track
+            if self._gstate is not None:
+                self._gstate.zero_()                           # absent, no hits, no misses
         self.schedule.reset()
         if self._history is not None:
             self._history.clear()
@@ -565,6 +675,14 @@ def parse(argv=None):
                    "Striebel); every record gains smoothed, smoothed_velocity, smoothed_covariance and smoothed_flag")
     p.add_argument("--tdm-compensation", action="store_true", help="compensate the TDM Doppler phase in the FFT chain (weights trained "
                    "with DATASET.tdmCompensation)")
+    p.add_argument("--presence", action="store_true", help="scene occupancy: CA-CFAR detection on the centre frame and a presence gate; "
+                   "every record gains present and occupancy")
+    p.add_argument("--pfa", type=float, default=None, help="with --presence: design false-alarm probability per cell (default 1e-5)")
+    p.add_argument("--cfar-guard", type=int, default=None, help="with --presence: half-width of the guard area (default 2)")
+    p.add_argument("--cfar-train", type=int, default=None, help="with --presence: half-width of the training area beyond it (default 4)")
+    p.add_argument("--min-cells", type=int, default=None, help="with --presence: detections that make a frame a hit (default 3)")
+    p.add_argument("--confirm", type=int, default=None, help="with --presence: consecutive hits until present (default 2)")
+    p.add_argument("--hold", type=int, default=None, help="with --presence: consecutive misses that are bridged (default 20)")
     p.add_argument("--weights", choices=WEIGHTS, default="live", help="live: model_state_dict as trained; averaged: ema_state_dict "
                    "(a run with TRAINING.emaDecay)")
     args = p.parse_args(argv)
@@ -585,7 +703,28 @@ def parse(argv=None):
                             ("--gate", args.gate is not None), ("--max-coast", args.max_coast is not None), ("--rts", args.rts)):
             if given:
                 p.error("%s needs --track" % flag)
+    if not args.presence:
+        for flag, dest in PRESENCE_FLAGS:
+            if getattr(args, dest) is not None:
+                p.error("%s needs --presence" % flag)
+    else:
+        try:
+            presence_from_args(args)
+        except PresenceError as e:
+            p.error(str(e))
     return args
+
+
+PRESENCE_FLAGS = (("--pfa", "pfa"), ("--cfar-guard", "cfar_guard"), ("--cfar-train", "cfar_train"), ("--min-cells", "min_cells"),
+                  ("--confirm", "confirm"), ("--hold", "hold"))
+
+
+def presence_from_args(args):
+    """The PresenceGate of a parsed command line (None without --presence)."""
+    if not args.presence:
+        return None
+    names = {"cfar_guard": "guard", "cfar_train": "train"}
+    return PresenceGate(**{names.get(dest, dest): getattr(args, dest) for _, dest in PRESENCE_FLAGS if getattr(args, dest) is not None})
 
 
 def tracking_from_args(args):
@@ -664,7 +803,7 @@ def main(argv=None):
     session = PoseStream(model, cfg, lanes=1, lookahead=args.lookahead, graph=not args.no_graph, device=dev, decode=args.decode,
                          smooth=PoseSmoothing(args.rate) if args.smooth else None, track=tracking_from_args(args),
                          predict_now=args.predict_now, decode_radius=args.decode_radius, tdm_compensation=args.tdm_compensation,
-                         history=args.rts)
+                         history=args.rts, presence=presence_from_args(args))
     records = []
 
     def record(pf):
@@ -676,6 +815,9 @@ def main(argv=None):
             records[-1]["covariance"] = [[float(v) for v in c] for c in pf.covariance.cpu().numpy()[0]]
             records[-1]["forecast"] = [[float(x), float(y)] for x, y in pf.forecast.cpu().numpy()[0]]
             records[-1]["status"] = [int(c) for c in pf.status.cpu().numpy()[0]]
+        if pf.present is not None:
+            records[-1]["present"] = int(pf.present.cpu().numpy()[0])
+            records[-1]["occupancy"] = [float(v) for v in pf.occupancy.cpu().numpy()[0]]
 
     for i in range(n):
         pf = session.push(frames[0][i:i + 1], frames[1][i:i + 1])

@@ -479,6 +479,53 @@ int hupr_pose_track_f32(const float* heat, long rows, int H, int W, float ratio,
 #define HUPR_SMOOTH_DEGENERATE 3
 int hupr_pose_smooth_rts_f32(const float* states, const int* status, const float* keypoints, long T, long rows, float rate_hz,
                              float accel_psd, float* smoothed, float* velocity, float* covariance, int* flag, hupr_stream_t stream);
+/* Scene occupancy (csrc/cfar.hip): cell-averaging constant-false-alarm-rate detection on the (range, azimuth) maps of a sensor-frame's
+ * elevation-mean planes, a per-frame summary of the detections, and a presence gate over the summaries (Rohling 1983; Richards,
+ * Fundamentals of Radar Signal Processing, ch. 6).  New, no reference counterpart.  One workgroup per frame, 48 KB of LDS, no atomics,
+ * fixed reduction order: every output is bit-identical from run to run.
+ * planes : float [n][16][64][64], what hupr_fft_chain_loader_means_f32 writes: plane 2 f + c is Doppler slot f = 0..7, c = re / im, the
+ *          spatial axes are (range r, azimuth a).  Clutter removal has nulled everything static: the planes hold movers plus noise, and
+ *          under noise a cell is complex Gaussian, its power exponentially distributed.
+ * Slot 4.  The clutter-nulled zero-Doppler slot f = 4 (planes 8 and 9) is never read: its mask is 0, its SNR 0, whatever it holds.
+ * Power.   For the other seven slots p_f[r][a] = x[2f][r][a]^2 + x[2f+1][r][a]^2.
+ * Training cells.  guard = g >= 0, train = t >= 1, w = g + t <= 8.  Inside one slot T(r, a) = {(r', a') inside the map :
+ *          g < max(|r' - r|, |a' - a|) <= w}; neither axis wraps, cells outside the map are not counted, so N = |T| is smaller near the
+ *          border (N >= 3).  noise = (sum of p over T) / N.  The sum is built from training cells only, never as a difference of sums
+ *          that hold the cell under test: per row the cells of the columns a - w .. a + w beyond the guard columns, in increasing a',
+ *          and those of the guard columns; then over the rows r - w .. r + w in increasing r', a row beyond the guard rows adding both
+ *          of its sums, a guard row the first.  With p's two roundings and the division this bounds the relative error of noise by
+ *          (4 w + 3) 2^-24 and that of snr by (4 w + 6) 2^-24.
+ * Threshold.  alpha[N] = N (pfa^(-1/N) - 1), the exact factor for exponential cells at false-alarm probability pfa.
+ *          alpha_table : float [table_len] on the device, entry N = alpha[N] computed in fp64 and rounded to fp32, entry 0 unused
+ *          (+inf); table_len >= (2 w + 1)^2 - (2 g + 1)^2 + 1.  hupr_cfar_table_len / hupr_cfar_alpha_table_f32 size and fill a HOST
+ *          table.  The kernel reads entry N of the cell's own window, so the design rate also holds at the border.
+ *          A cell detects iff p > alpha[N] * noise (both sides fp32; a NaN on either side does not detect).
+ *          snr = p / noise, 0 where p and noise are both 0.
+ * mask_or_null : unsigned char [n][8][64][64], 1 = detection.  snr_or_null : float, the same shape.  Either may be null.
+ * summary : float [n][8] = (count, peak_snr, peak_f, peak_r, peak_a, centroid_r, centroid_a, doppler): the number of detections over
+ *          the seven slots; the SNR and the slot, range and azimuth of the detection with the largest SNR, ties to the lowest (f, r, a)
+ *          in that order; the SNR-weighted mean range and azimuth of all detections; the SNR-weighted mean of the signed Doppler bin
+ *          d = f - 4 (its sign tells approaching from receding).  Without a detection (0, 0, -1, -1, -1, 0, 0, 0).  The weighted sums
+ *          are accumulated in fp64.
+ * hupr_cfar_ra_stream_f32 runs the same kernel on the centre frame of a live-stream session (hupr_mnet_stream_f32 above), read from
+ * the session's ring: frame `lane` is the horizontal sensor's ring slot (centre mod G) of that lane, centre = flush ? poses emitted :
+ * frames pushed - lookahead, read from the session state on the device.  It goes behind the hupr_mnet_stream_* launch of the same push
+ * or flush, which has filed the newest frame, and in front of hupr_stream_advance; no argument depends on the frame number.
+ * hupr_presence_update, one call per emitted frame: gate_state int [lanes][4] = (present, hits, misses, frames), all zero = a new
+ * sequence.  hit = count >= min_cells (count = summary[lane][0]); hits = hit ? hits + 1 : 0; misses = hit ? 0 : misses + 1; an absent
+ * lane becomes present when hits >= confirm, a present lane absent when misses > hold; frames += 1 (the three counters saturate at
+ * 2^31 - 1).  present_out int [lanes].  hold bridges the pauses of a person who stands still and so vanishes under clutter removal.
+ * All entries return -1 (HUPR_ERR_ARG) before any launch for guard < 0, train < 1, guard + train > 8, a table shorter than the window
+ * needs, pfa outside (0, 1), min_cells < 1, confirm < 1, hold < 0, a negative count and null pointers; n == 0 / lanes == 0 is a no-op. */
+int hupr_cfar_table_len(int guard, int train);
+int hupr_cfar_alpha_table_f32(double pfa, int guard, int train, float* host_table, int table_len);
+int hupr_cfar_ra_f32(const float* planes, int n, int guard, int train, const float* alpha_table, int table_len,
+                     unsigned char* mask_or_null, float* snr_or_null, float* summary, hupr_stream_t stream);
+int hupr_cfar_ra_stream_f32(const float* ring, const void* stream_state, int lookahead, int flush, int lanes, int G, int guard,
+                            int train, const float* alpha_table, int table_len, unsigned char* mask_or_null, float* snr_or_null,
+                            float* summary, hupr_stream_t stream);
+int hupr_presence_update(const float* summary, int lanes, int min_cells, int confirm, int hold, int* gate_state, int* present_out,
+                         hupr_stream_t stream);
 
 /* tri-/bilinear align_corners=True resampling (models/layers.py:84,89,199,204; gcn_networks.py:49,63) */
 int hupr_interp_linear_fwd_f32(const float* x, float* y, int Bn, int Di, int Hi, int Wi, int Do, int Ho, int Wo,
