@@ -4,21 +4,13 @@
 //     hupr_k_argmax_rows, hupr_k_pose_decode and hupr_k_pose_track
 //   * first moments of the weights max(h, 0) over the window of the given radius around the peak, clipped to the map (radius 0: the
 //     whole map), in a summation order fixed by the window alone
-//   * optionally the One-Euro filter of hupr_k_pose_decode on the image-pixel keypoint, restated here line for line (pose_decode.hip
-//     is pinned to one kernel), on the same [rows][8] state
+//   * optionally the One-Euro filter of hupr_k_pose_decode on the image-pixel keypoint: the one body and the one [rows][8] state of
+//     pose_filter.h (this decode stays a source of its own because pose_decode.hip is pinned to one kernel)
 // The rule is stated in full beside hupr_pose_decode_integral_f32 in include/hupr.h.
 #include "hupr_common.h"
-#include "pose_refine.h"
+#include "pose_filter.h"
 
 namespace hupr {
-
-constexpr int kFilterFloats = 8;      // per row: x, y, dx, dy (filtered position and velocity), valid, 3 x pad: pose_decode.hip's state
-
-struct OneEuro {
-    float rate, min_cutoff, beta, d_cutoff, min_score;
-};
-
-__device__ __forceinline__ float euro_alpha(float rate, float cutoff) { return 1.f / (1.f + rate / (6.283185307179586f * cutoff)); }
 
 // One wave = one row.  Nothing is shared between workgroups; the filter state of a row is read and written by lane 0 of its wave.
 __global__ __launch_bounds__(64) void hupr_k_pose_decode_integral(const float* __restrict__ heat, int H, int W, float ratio, int radius,
@@ -55,41 +47,8 @@ __global__ __launch_bounds__(64) void hupr_k_pose_decode_integral(const float* _
         const float tx = mx / m, ty = my / m;
         if (finitef(tx) && finitef(ty)) { ox = tx; oy = ty; }
     }
-    // a joint whose maximum is <= 0 decodes to (0, 0), as in hupr_k_pose_decode
-    const float keep = positive ? 1.f : 0.f;
-    const float x = ((float)px + ox) * keep * ratio, y = ((float)py + oy) * keep * ratio;
-    idx[r] = bi;
-    maxval[r] = best;
-    *reinterpret_cast<float2*>(raw + r * 2) = make_float2(x, y);
-    if (!state) return;
-
-    // ---- One-Euro filter: hupr_k_pose_decode's --------------------------------------------------------------------------------------
-    float* s = state + r * kFilterFloats;
-    const float sx = s[0], sy = s[1], svx = s[2], svy = s[3];
-    const bool valid = s[4] != 0.f;
-    const bool missing = !(best > f.min_score) || !finitef(x) || !finitef(y);
-    float fx = x, fy = y, vx = 0.f, vy = 0.f;
-    if (missing) {
-        if (valid) { fx = sx; fy = sy; }                  // the joint holds its place; the state is left as it is
-    } else {
-        if (valid) {
-            const float ad = euro_alpha(f.rate, f.d_cutoff);
-            const float rx = (x - sx) * f.rate, ry = (y - sy) * f.rate;
-            vx = ad * rx + (1.f - ad) * svx;
-            vy = ad * ry + (1.f - ad) * svy;
-            const float ax = euro_alpha(f.rate, f.min_cutoff + f.beta * fabsf(vx));
-            const float ay = euro_alpha(f.rate, f.min_cutoff + f.beta * fabsf(vy));
-            fx = ax * x + (1.f - ax) * sx;
-            fy = ay * y + (1.f - ay) * sy;
-        }
-        s[0] = fx;
-        s[1] = fy;
-        s[2] = vx;
-        s[3] = vy;
-        s[4] = 1.f;
-    }
-    if (filtered) *reinterpret_cast<float2*>(filtered + r * 2) = make_float2(fx, fy);
-    if (velocity) *reinterpret_cast<float2*>(velocity + r * 2) = make_float2(vx, vy);
+    const float2 k = store_keypoint(r, bi, best, px, py, ox, oy, positive, ratio, idx, maxval, raw);
+    euro_step(state, r, f, best, k.x, k.y, filtered, velocity);
 }
 
 }  // namespace hupr
@@ -102,22 +61,13 @@ extern "C" int hupr_pose_decode_integral_f32(const float* heat, long rows, int H
                                              float* velocity_or_null, hupr_stream_t stream) {
     if (rows == 0) return HUPR_OK;
     HUPR_REQUIRE(heat && idx && maxval && raw_keypoints, "hupr_pose_decode_integral_f32: null pointer");
-    HUPR_REQUIRE(rows > 0 && rows < (1L << 31) && H > 0 && W > 0 && (long)H * W < (1L << 31),
-                 "hupr_pose_decode_integral_f32: bad shape (rows %ld, H %d, W %d)", rows, H, W);
+    if (int e = pose_shape("hupr_pose_decode_integral_f32", rows, H, W)) return e;
     HUPR_REQUIRE(radius >= 0, "hupr_pose_decode_integral_f32: bad radius %d (0 = the whole map, else >= 1)", radius);
-    if (filter_state_or_null) {
-        HUPR_REQUIRE(rate_hz > 0.f && rate_hz < INFINITY && min_cutoff > 0.f && min_cutoff < INFINITY && d_cutoff > 0.f &&
-                         d_cutoff < INFINITY && beta >= 0.f && beta < INFINITY && min_score == min_score,
-                     "hupr_pose_decode_integral_f32: bad filter parameter (rate_hz %g, min_cutoff %g and d_cutoff %g must be positive, "
-                     "beta %g non-negative, min_score %g a number)", rate_hz, min_cutoff, d_cutoff, beta, min_score);
-    } else {
-        HUPR_REQUIRE(!keypoints_or_null && !velocity_or_null,
-                     "hupr_pose_decode_integral_f32: filtered keypoints / velocity asked for without a filter state");
-    }
+    const OneEuro f = {rate_hz, min_cutoff, beta, d_cutoff, min_score};
+    if (int e = euro_check("hupr_pose_decode_integral_f32", filter_state_or_null, f, keypoints_or_null, velocity_or_null)) return e;
     // radius 0 is the whole map; any radius >= max(H, W) - 1 clips to the same window, so both become max(H, W) (no overflow in px + r)
     const int whole = H > W ? H : W;
     const int rad = (radius == 0 || radius > whole) ? whole : radius;
-    const OneEuro f = {rate_hz, min_cutoff, beta, d_cutoff, min_score};
     HUPR_LAUNCH(hupr_k_pose_decode_integral, dim3((unsigned)rows), dim3(64), 0, as_stream(stream), heat, H, W, ratio, rad,
                 filter_state_or_null, f, idx, maxval, raw_keypoints, keypoints_or_null, velocity_or_null);
     HUPR_LAUNCH_OK("hupr_k_pose_decode_integral");

@@ -1,5 +1,6 @@
 // Sub-pixel refinement of a heat-map peak, shared by hupr_k_pose_decode (pose_decode.hip) and hupr_k_pose_track (pose_track.hip) so
-// that the two decode to the same bits.  The rule is stated beside hupr_pose_decode_f32 in include/hupr.h.
+// that the two decode to the same bits, and the tail of those two and of hupr_k_pose_decode_integral (pose_integral.hip): the keypoint
+// with its stores, and the entries' shape rule.  The rule is stated beside hupr_pose_decode_f32 in include/hupr.h.
 #pragma once
 #include "hupr_common.h"
 
@@ -47,6 +48,25 @@ __device__ __forceinline__ void peak_offset(const float* row, int H, int W, int 
             }
         }
     }
+}
+
+// The decoded keypoint of row r, called by lane 0: stores index, maximum and the image-pixel (x, y) and returns (x, y).  A joint whose
+// maximum is <= 0 decodes to (0, 0) (misc/metrics.py); with a zero offset these are the floats of hupr_k_stream_keypoints.
+__device__ __forceinline__ float2 store_keypoint(long r, int bi, float best, int px, int py, float ox, float oy, bool positive,
+                                                 float ratio, int* idx, float* maxval, float* raw) {
+    const float keep = positive ? 1.f : 0.f;
+    const float2 k = make_float2(((float)px + ox) * keep * ratio, ((float)py + oy) * keep * ratio);
+    idx[r] = bi;
+    maxval[r] = best;
+    *reinterpret_cast<float2*>(raw + r * 2) = k;
+    return k;
+}
+
+// the shape rule shared by the entries of the three decodes: the kernels index a row's H * W pixels with an int
+static inline int pose_shape(const char* name, long rows, int H, int W) {
+    HUPR_REQUIRE(rows > 0 && rows < (1L << 31) && H > 0 && W > 0 && (long)H * W < (1L << 31), "%s: bad shape (rows %ld, H %d, W %d)",
+                 name, rows, H, W);
+    return HUPR_OK;
 }
 
 }  // namespace hupr

@@ -4,36 +4,33 @@
 //     sequences (sequences x joints) share one launch
 //   * the successor's smoothed state (4 + 10 values) stays in registers; the filter's state of a frame is read as four float4
 //   * no LDS, no atomics, no scratch: every output is bit-identical from run to run and independent of the other rows
-// The rule is stated in full beside hupr_pose_smooth_rts_f32 in include/hupr.h.
+// The rule is stated in full beside hupr_pose_smooth_rts_f32 in include/hupr.h; the tracker's model is pose_track_model.h's.
 #include "hupr_common.h"
 #include "pose_refine.h"
+#include "pose_track_model.h"
 
 namespace hupr {
-
-constexpr int kStateFloats = 16;      // the tracker's state of one row (csrc/pose_track.hip)
-constexpr int kStarted = 3, kLost = 4;                                          // HUPR_TRACK_STARTED, HUPR_TRACK_LOST
-constexpr int kSmoothed = 0, kEnd = 1, kPassthrough = 2, kDegenerate = 3;       // HUPR_SMOOTH_*
 
 // the upper triangle of a symmetric 4 x 4 matrix row by row, as the tracker's state keeps it
 __host__ __device__ constexpr int tri(int i, int j) { return i <= j ? i * (9 - i) / 2 + (j - i) : j * (9 - j) / 2 + (i - j); }
 
 // One backward step.  x, p: the filter's state of frame k; xs, ps: the smoothed state of frame k + 1 on entry, of frame k on return.
 // false (xs, ps untouched) where a Cholesky pivot is not positive and finite or a result is not finite.
-__device__ __forceinline__ bool rts_step(const float (&x)[4], const float (&p)[10], float (&xs)[4], float (&ps)[10], float dt, float q11,
-                                         float q12, float q22) {
+__device__ __forceinline__ bool rts_step(const float (&x)[4], const float (&p)[10], float (&xs)[4], float (&ps)[10], float dt,
+                                         ProcessNoise q) {
     // ---- predict, with the tracker's own expressions: xp = F x, Pp = F P F^T + Q ------------------------------------------------------
     float xp[4] = {x[0] + dt * x[2], x[1] + dt * x[3], x[2], x[3]};
     float pp[10];
-    pp[tri(0, 0)] = p[tri(0, 0)] + (dt * (2.f * p[tri(0, 2)]) + dt * dt * p[tri(2, 2)] + q11);
+    pp[tri(0, 0)] = p[tri(0, 0)] + (dt * (2.f * p[tri(0, 2)]) + dt * dt * p[tri(2, 2)] + q.q11);
     pp[tri(0, 1)] = p[tri(0, 1)] + (dt * (p[tri(0, 3)] + p[tri(1, 2)]) + dt * dt * p[tri(2, 3)]);
-    pp[tri(1, 1)] = p[tri(1, 1)] + (dt * (2.f * p[tri(1, 3)]) + dt * dt * p[tri(3, 3)] + q11);
-    pp[tri(0, 2)] = p[tri(0, 2)] + (dt * p[tri(2, 2)] + q12);
+    pp[tri(1, 1)] = p[tri(1, 1)] + (dt * (2.f * p[tri(1, 3)]) + dt * dt * p[tri(3, 3)] + q.q11);
+    pp[tri(0, 2)] = p[tri(0, 2)] + (dt * p[tri(2, 2)] + q.q12);
     pp[tri(0, 3)] = p[tri(0, 3)] + dt * p[tri(2, 3)];
     pp[tri(1, 2)] = p[tri(1, 2)] + dt * p[tri(2, 3)];
-    pp[tri(1, 3)] = p[tri(1, 3)] + (dt * p[tri(3, 3)] + q12);
-    pp[tri(2, 2)] = p[tri(2, 2)] + q22;
+    pp[tri(1, 3)] = p[tri(1, 3)] + (dt * p[tri(3, 3)] + q.q12);
+    pp[tri(2, 2)] = p[tri(2, 2)] + q.q22;
     pp[tri(2, 3)] = p[tri(2, 3)];
-    pp[tri(3, 3)] = p[tri(3, 3)] + q22;
+    pp[tri(3, 3)] = p[tri(3, 3)] + q.q22;
 
     // ---- Cholesky Pp = L L^T, column by column; l[tri(i, j)] = L[i][j] for i >= j ------------------------------------------------------
     float l[10], inv[4];
@@ -124,7 +121,7 @@ __global__ __launch_bounds__(64) void hupr_k_pose_smooth_rts(const float* __rest
     const long r = (long)blockIdx.x * 64 + threadIdx.x;
     if (r >= rows) return;
     const float dt = 1.f / rate;
-    const float q11 = accel_psd * dt * dt * dt * (1.f / 3.f), q12 = accel_psd * dt * dt * 0.5f, q22 = accel_psd * dt;
+    const ProcessNoise q = process_noise(accel_psd, dt);
     float xs[4] = {0.f, 0.f, 0.f, 0.f};
     float ps[10] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     bool chained = false;                      // frame k + 1 exists and continues the track of frame k
@@ -132,21 +129,21 @@ __global__ __launch_bounds__(64) void hupr_k_pose_smooth_rts(const float* __rest
         const long e = k * rows + r;
         const int code = status[e];
         int fl;
-        if (code == kLost) {
+        if (code == HUPR_TRACK_LOST) {
             *reinterpret_cast<float2*>(smoothed + e * 2) = *reinterpret_cast<const float2*>(keypoints + e * 2);
             *reinterpret_cast<float2*>(velocity + e * 2) = make_float2(0.f, 0.f);
             covariance[e * 3 + 0] = 0.f;
             covariance[e * 3 + 1] = 0.f;
             covariance[e * 3 + 2] = 0.f;
-            fl = kPassthrough;
+            fl = HUPR_SMOOTH_PASSTHROUGH;
         } else {
-            const float4* s = reinterpret_cast<const float4*>(states + e * kStateFloats);
+            const float4* s = reinterpret_cast<const float4*>(states + e * kTrackFloats);
             const float4 s0 = s[0], s1 = s[1], s2 = s[2], s3 = s[3];
             const float x[4] = {s0.x, s0.y, s0.z, s0.w};
             const float p[10] = {s1.x, s1.y, s1.z, s1.w, s2.x, s2.y, s2.z, s2.w, s3.x, s3.y};
-            fl = kEnd;
-            if (chained) fl = rts_step(x, p, xs, ps, dt, q11, q12, q22) ? kSmoothed : kDegenerate;
-            if (fl != kSmoothed) {             // the end of a segment and a degenerate frame: the filter's own state, and the chain goes on from it
+            fl = HUPR_SMOOTH_END;
+            if (chained) fl = rts_step(x, p, xs, ps, dt, q) ? HUPR_SMOOTH_SMOOTHED : HUPR_SMOOTH_DEGENERATE;
+            if (fl != HUPR_SMOOTH_SMOOTHED) {  // the end of a segment and a degenerate frame: the filter's own state, and the chain goes on from it
 #pragma unroll
                 for (int j = 0; j < 4; ++j) xs[j] = x[j];
 #pragma unroll
@@ -159,7 +156,7 @@ __global__ __launch_bounds__(64) void hupr_k_pose_smooth_rts(const float* __rest
             covariance[e * 3 + 2] = ps[tri(1, 1)];
         }
         flag[e] = fl;
-        chained = code != kLost && code != kStarted;
+        chained = code != HUPR_TRACK_LOST && code != HUPR_TRACK_STARTED;
     }
 }
 

@@ -1,17 +1,17 @@
 // Keypoint decode with a constant-velocity Kalman filter per joint: the tracking tail of the live stream.
-//   * arg-max and sub-pixel refinement exactly as hupr_k_pose_decode (wave_argmax_row, pose_refine.h): the same index, maximum and raw
-//     keypoint, bit for bit
+//   * arg-max, sub-pixel refinement and the keypoint's stores exactly as hupr_k_pose_decode (wave_argmax_row, pose_refine.h): the
+//     same index, maximum and raw keypoint, bit for bit
 //   * the measurement covariance read off the heat-map: second central moments of the 7 x 7 window around the peak
 //   * predict / gate / update of a constant-velocity Kalman filter (Kalman 1960) with the white-acceleration process noise and the
 //     chi-square gate of Bar-Shalom, Li & Kirubarajan (2001), its state on the device, so that the filtered pose, its velocity, its
 //     covariance and a forecast come out of the same launch — and of the same captured graph — as the decode
-// The rule is stated in full beside hupr_pose_track_f32 in include/hupr.h.
+// The rule is stated in full beside hupr_pose_track_f32 in include/hupr.h; pose_track_model.h holds what the smoother shares.
 #include "hupr_common.h"
 #include "pose_refine.h"
+#include "pose_track_model.h"
 
 namespace hupr {
 
-constexpr int kTrackFloats = 16;      // per row: x, y, vx, vy, the 10 upper-triangle entries of P (row-major), live, coast
 constexpr int kWindowRadius = 3;      // the covariance window: 7 x 7 pixels around the peak, clipped to the map
 constexpr int kWindowSide = 2 * kWindowRadius + 1;
 
@@ -52,11 +52,8 @@ __global__ __launch_bounds__(64) void hupr_k_pose_track(const float* __restrict_
     const float mxx = wave_sum(w * ex * ex) / m, mxy = wave_sum(w * ex * ey) / m, myy = wave_sum(w * ey * ey) / m;
     if (lane != 0) return;
 
-    const float keep = positive ? 1.f : 0.f;
-    const float zx = ((float)px + ox) * keep * ratio, zy = ((float)py + oy) * keep * ratio;
-    idx[r] = bi;
-    maxval[r] = best;
-    *reinterpret_cast<float2*>(raw + r * 2) = make_float2(zx, zy);
+    const float2 z = store_keypoint(r, bi, best, px, py, ox, oy, positive, ratio, idx, maxval, raw);
+    const float zx = z.x, zy = z.y;
 
     // ---- measurement noise and whether there is a measurement at all --------------------------------------------------------------
     const float gain = ratio * ratio * f.heatmap_gain, floor2 = f.meas_std * f.meas_std;
@@ -69,23 +66,23 @@ __global__ __launch_bounds__(64) void hupr_k_pose_track(const float* __restrict_
     float p00 = s1.x, p01 = s1.y, p02 = s1.z, p03 = s1.w, p11 = s2.x, p12 = s2.y, p13 = s2.z, p22 = s2.w, p23 = s3.x, p33 = s3.y;
     bool live = s3.z != 0.f;
     float coast = s3.w;
-    int code = 4;                                                                      // LOST
+    int code = HUPR_TRACK_LOST;
 
     if (live) {
         // ---- predict: x- = F x, P- = F P F^T + Q ------------------------------------------------------------------------------------
         const float dt = 1.f / f.rate;
-        const float q11 = f.accel_psd * dt * dt * dt * (1.f / 3.f), q12 = f.accel_psd * dt * dt * 0.5f, q22 = f.accel_psd * dt;
+        const ProcessNoise q = process_noise(f.accel_psd, dt);
         x0 += dt * x2;
         x1 += dt * x3;
-        p00 += dt * (2.f * p02) + dt * dt * p22 + q11;
+        p00 += dt * (2.f * p02) + dt * dt * p22 + q.q11;
         p01 += dt * (p03 + p12) + dt * dt * p23;
-        p11 += dt * (2.f * p13) + dt * dt * p33 + q11;
-        p02 += dt * p22 + q12;
+        p11 += dt * (2.f * p13) + dt * dt * p33 + q.q11;
+        p02 += dt * p22 + q.q12;
         p03 += dt * p23;
         p12 += dt * p23;
-        p13 += dt * p33 + q12;
-        p22 += q22;
-        p33 += q22;
+        p13 += dt * p33 + q.q12;
+        p22 += q.q22;
+        p33 += q.q22;
 
         // ---- gate: d2 = nu^T S^-1 nu through the closed-form 2 x 2 inverse ----------------------------------------------------------------
         bool accepted = false;
@@ -136,12 +133,12 @@ __global__ __launch_bounds__(64) void hupr_k_pose_track(const float* __restrict_
             p13 = 0.5f * (n13 + n31);
             p23 = 0.5f * (n23 + n32);
             coast = 0.f;
-            code = 0;                                                                  // UPDATED
+            code = HUPR_TRACK_UPDATED;
         } else if (coast + 1.f > (float)f.max_coast) {
             live = false;                                                              // the track ends; a usable sample starts the next
         } else {
             coast += 1.f;
-            code = usable ? 2 : 1;                                                     // COASTED_GATED : COASTED_MISSING
+            code = usable ? HUPR_TRACK_COASTED_GATED : HUPR_TRACK_COASTED_MISSING;
         }
     }
     if (!live) {
@@ -151,7 +148,7 @@ __global__ __launch_bounds__(64) void hupr_k_pose_track(const float* __restrict_
             p22 = p33 = f.init_speed_std * f.init_speed_std;
             p02 = p03 = p12 = p13 = p23 = 0.f;
             live = true;
-            code = 3;                                                                  // STARTED
+            code = HUPR_TRACK_STARTED;
         } else {
             x0 = x1 = x2 = x3 = 0.f;
             p00 = p01 = p02 = p03 = p11 = p12 = p13 = p22 = p23 = p33 = 0.f;
@@ -189,8 +186,7 @@ extern "C" int hupr_pose_track_f32(const float* heat, long rows, int H, int W, f
     if (rows == 0) return HUPR_OK;
     HUPR_REQUIRE(heat && state && idx && maxval && raw_keypoints && keypoints && velocity && covariance && forecast && status,
                  "hupr_pose_track_f32: null pointer");
-    HUPR_REQUIRE(rows > 0 && rows < (1L << 31) && H > 0 && W > 0 && (long)H * W < (1L << 31),
-                 "hupr_pose_track_f32: bad shape (rows %ld, H %d, W %d)", rows, H, W);
+    if (int e = pose_shape("hupr_pose_track_f32", rows, H, W)) return e;
     HUPR_REQUIRE(((uintptr_t)state & 15) == 0, "hupr_pose_track_f32: the state must be 16-byte aligned");
     HUPR_REQUIRE(rate_hz > 0.f && rate_hz < INFINITY && meas_std > 0.f && meas_std < INFINITY && gate > 0.f && gate < INFINITY &&
                      init_speed_std > 0.f && init_speed_std < INFINITY && accel_psd >= 0.f && accel_psd < INFINITY &&

@@ -1954,10 +1954,47 @@ def argmax_rows(p):
     return idx, mx
 
 
+def _pose_state(bytes_fn, rows, device):
+    """A zero-filled ("never seen") per-row state of the size the library's ``bytes_fn(rows)`` gives, as (rows, floats) fp32."""
+    n = int(bytes_fn(rows)) // 4
+    return torch.zeros((rows, n // max(rows, 1)), dtype=torch.float32, device=device)
+
+
+def _pose_heat(name, heat):
+    """heat (..., H, W) fp32, checked in ``name``'s name -> (contiguous heat, lead shape, rows, H, W)."""
+    if heat.dim() < 2:
+        raise ValueError("%s needs (..., H, W) heat-maps, got shape %r" % (name, tuple(heat.shape)))
+    if heat.dtype != torch.float32:
+        raise ValueError("%s needs fp32 heat-maps, got %s" % (name, heat.dtype))
+    heat = _c(heat)
+    lead, (H, W) = tuple(heat.shape[:-2]), heat.shape[-2:]
+    return heat, lead, int(np.prod(lead, dtype=np.int64)), H, W
+
+
+def _pose_decode(entry, checked, mode, ratio, filter_state, smoothing):
+    """Allocate and launch for the two plain decodes: ``entry`` is the library's function, ``checked`` what ``_pose_heat`` returned,
+    ``mode`` the one argument in which the two differ (refine / radius)."""
+    if (filter_state is None) != (smoothing is None):
+        raise ValueError("filter_state and smoothing go together")
+    heat, lead, rows, H, W = checked
+    idx = torch.empty(lead, dtype=torch.int32, device=heat.device)
+    mx = torch.empty(lead, dtype=torch.float32, device=heat.device)
+    raw = torch.empty(lead + (2,), dtype=torch.float32, device=heat.device)
+    kp = vel = None
+    params = (0.0,) * 5
+    if filter_state is not None:
+        if filter_state.dtype != torch.float32 or filter_state.numel() * 4 != int(rt.lib().hupr_pose_filter_state_bytes(rows)):
+            raise ValueError("filter_state must be the fp32 tensor pose_filter_state(%d, device) returns" % rows)
+        kp, vel = torch.empty_like(raw), torch.empty_like(raw)
+        params = tuple(float(getattr(smoothing, k)) for k in ("rate_hz", "min_cutoff", "beta", "d_cutoff", "min_score"))
+    rt.check(entry(rt.ptr(heat), rows, H, W, float(ratio), mode, rt.ptr(filter_state), *params, rt.ptr(idx), rt.ptr(mx), rt.ptr(raw),
+                   rt.ptr(kp), rt.ptr(vel), rt.stream()))
+    return idx, mx, raw, kp, vel
+
+
 def pose_filter_state(rows, device):
     """A zero-filled ("never seen") One-Euro filter state for ``rows`` (sample, joint) rows: (rows, 8) fp32."""
-    n = int(rt.lib().hupr_pose_filter_state_bytes(rows)) // 4
-    return torch.zeros((rows, n // max(rows, 1)), dtype=torch.float32, device=device)
+    return _pose_state(rt.lib().hupr_pose_filter_state_bytes, rows, device)
 
 
 def pose_decode(heat, ratio, refine=True, filter_state=None, smoothing=None):
@@ -1967,28 +2004,8 @@ def pose_decode(heat, ratio, refine=True, filter_state=None, smoothing=None):
     ``refine`` is false.  ``filter_state`` (``pose_filter_state``, advanced in place) together with ``smoothing`` (an object with
     ``rate_hz``, ``min_cutoff``, ``beta``, ``d_cutoff``, ``min_score``: tools.stream.PoseSmoothing) adds the One-Euro filter: the
     filtered keypoints and the velocity in pixels per second, both None without it.  Device tensors, no sync."""
-    if heat.dim() < 2:
-        raise ValueError("pose_decode needs (..., H, W) heat-maps, got shape %r" % (tuple(heat.shape),))
-    if heat.dtype != torch.float32:
-        raise ValueError("pose_decode needs fp32 heat-maps, got %s" % heat.dtype)
-    if (filter_state is None) != (smoothing is None):
-        raise ValueError("filter_state and smoothing go together")
-    heat = _c(heat)
-    lead, (H, W) = tuple(heat.shape[:-2]), heat.shape[-2:]
-    rows = int(np.prod(lead, dtype=np.int64))
-    idx = torch.empty(lead, dtype=torch.int32, device=heat.device)
-    mx = torch.empty(lead, dtype=torch.float32, device=heat.device)
-    raw = torch.empty(lead + (2,), dtype=torch.float32, device=heat.device)
-    kp = vel = None
-    params = (0.0,) * 5
-    if filter_state is not None:
-        if filter_state.dtype != torch.float32 or filter_state.numel() * 4 != int(rt.lib().hupr_pose_filter_state_bytes(rows)):
-            raise ValueError("filter_state must be the fp32 tensor pose_filter_state(%d, device) returns" % rows)
-        kp, vel = torch.empty_like(raw), torch.empty_like(raw)
-        params = tuple(float(getattr(smoothing, k)) for k in ("rate_hz", "min_cutoff", "beta", "d_cutoff", "min_score"))
-    rt.check(rt.lib().hupr_pose_decode_f32(rt.ptr(heat), rows, H, W, float(ratio), int(bool(refine)), rt.ptr(filter_state), *params,
-                                           rt.ptr(idx), rt.ptr(mx), rt.ptr(raw), rt.ptr(kp), rt.ptr(vel), rt.stream()))
-    return idx, mx, raw, kp, vel
+    checked = _pose_heat("pose_decode", heat)
+    return _pose_decode(rt.lib().hupr_pose_decode_f32, checked, int(bool(refine)), ratio, filter_state, smoothing)
 
 
 def pose_decode_integral(heat, ratio, radius, filter_state=None, smoothing=None):
@@ -1996,31 +2013,11 @@ def pose_decode_integral(heat, ratio, radius, filter_state=None, smoothing=None)
     hupr_pose_decode_integral_f32 in include/hupr.h): the raw keypoint is the mass centroid of the weights max(h, 0) over the window
     of ``radius`` pixels around the arg-max, clipped to the map, times ``ratio``; ``radius`` 0 is the whole map, the centroid the
     integral coordinate loss trains.  ``idx`` / ``maxval`` are ``argmax_rows``' bits.  ``filter_state`` and ``smoothing`` are
-    ``pose_decode``'s: the same state tensor, the same One-Euro filter.  Device tensors, no sync."""
-    if heat.dim() < 2:
-        raise ValueError("pose_decode_integral needs (..., H, W) heat-maps, got shape %r" % (tuple(heat.shape),))
-    if heat.dtype != torch.float32:
-        raise ValueError("pose_decode_integral needs fp32 heat-maps, got %s" % heat.dtype)
+    ``pose_decode``'s: the same state tensor, the same One-Euro filter (csrc/pose_filter.h).  Device tensors, no sync."""
+    checked = _pose_heat("pose_decode_integral", heat)
     if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 0 <= radius < 2 ** 31:
         raise ValueError("pose_decode_integral needs an integer radius >= 0 (0 = the whole map), got %r" % (radius,))
-    if (filter_state is None) != (smoothing is None):
-        raise ValueError("filter_state and smoothing go together")
-    heat = _c(heat)
-    lead, (H, W) = tuple(heat.shape[:-2]), heat.shape[-2:]
-    rows = int(np.prod(lead, dtype=np.int64))
-    idx = torch.empty(lead, dtype=torch.int32, device=heat.device)
-    mx = torch.empty(lead, dtype=torch.float32, device=heat.device)
-    raw = torch.empty(lead + (2,), dtype=torch.float32, device=heat.device)
-    kp = vel = None
-    params = (0.0,) * 5
-    if filter_state is not None:
-        if filter_state.dtype != torch.float32 or filter_state.numel() * 4 != int(rt.lib().hupr_pose_filter_state_bytes(rows)):
-            raise ValueError("filter_state must be the fp32 tensor pose_filter_state(%d, device) returns" % rows)
-        kp, vel = torch.empty_like(raw), torch.empty_like(raw)
-        params = tuple(float(getattr(smoothing, k)) for k in ("rate_hz", "min_cutoff", "beta", "d_cutoff", "min_score"))
-    rt.check(rt.lib().hupr_pose_decode_integral_f32(rt.ptr(heat), rows, H, W, float(ratio), int(radius), rt.ptr(filter_state), *params,
-                                                    rt.ptr(idx), rt.ptr(mx), rt.ptr(raw), rt.ptr(kp), rt.ptr(vel), rt.stream()))
-    return idx, mx, raw, kp, vel
+    return _pose_decode(rt.lib().hupr_pose_decode_integral_f32, checked, int(radius), ratio, filter_state, smoothing)
 
 
 TRACK_UPDATED, TRACK_COASTED_MISSING, TRACK_COASTED_GATED, TRACK_STARTED, TRACK_LOST = range(5)      # pose_track's status codes
@@ -2030,8 +2027,7 @@ _TRACK_PARAMS = ("rate_hz", "accel_psd", "meas_std", "heatmap_gain", "gate", "ma
 def pose_track_state(rows, device):
     """A zero-filled ("never seen") Kalman track state for ``rows`` (sample, joint) rows: (rows, 16) fp32 = x, y, vx, vy, the upper
     triangle of the 4 x 4 covariance row by row, live, coast."""
-    n = int(rt.lib().hupr_pose_track_state_bytes(rows)) // 4
-    return torch.zeros((rows, n // max(rows, 1)), dtype=torch.float32, device=device)
+    return _pose_state(rt.lib().hupr_pose_track_state_bytes, rows, device)
 
 
 def pose_track(heat, ratio, refine=True, track_state=None, tracking=None):
@@ -2041,15 +2037,9 @@ def pose_track(heat, ratio, refine=True, track_state=None, tracking=None):
     ``pose_decode``'s bits.  ``track_state`` (``pose_track_state``, advanced in place) and ``tracking`` (an object with ``rate_hz``,
     ``accel_psd``, ``meas_std``, ``heatmap_gain``, ``gate``, ``max_coast``, ``init_speed_std``, ``min_score``, ``horizon_s``:
     tools.stream.PoseTracking) are both required.  One call is one frame.  Device tensors, no sync."""
-    if heat.dim() < 2:
-        raise ValueError("pose_track needs (..., H, W) heat-maps, got shape %r" % (tuple(heat.shape),))
-    if heat.dtype != torch.float32:
-        raise ValueError("pose_track needs fp32 heat-maps, got %s" % heat.dtype)
+    heat, lead, rows, H, W = _pose_heat("pose_track", heat)
     if track_state is None or tracking is None:
         raise ValueError("pose_track needs its track_state and its tracking parameters")
-    heat = _c(heat)
-    lead, (H, W) = tuple(heat.shape[:-2]), heat.shape[-2:]
-    rows = int(np.prod(lead, dtype=np.int64))
     if (not isinstance(track_state, torch.Tensor) or track_state.dtype != torch.float32 or not track_state.is_contiguous()
             or track_state.numel() * 4 != int(rt.lib().hupr_pose_track_state_bytes(rows))):
         raise ValueError("track_state must be the fp32 tensor pose_track_state(%d, device) returns" % rows)

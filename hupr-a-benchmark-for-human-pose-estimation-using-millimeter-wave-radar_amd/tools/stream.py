@@ -94,6 +94,24 @@ DECODES = ("argmax", "subpixel", "integral")
 WEIGHTS = ("live", "averaged")      # which parameters of model_best.pth: as trained, or their moving average (TRAINING.emaDecay)
 
 
+def _finite(error, field, v):
+    """``v`` where it is a finite number and no bool; otherwise ``error`` in the name of ``field`` ("Class.field")."""
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(v):
+        raise error("%s must be a finite number, got %r" % (field, v))
+    return v
+
+
+def _count(error, field, v, lo):
+    """``v`` as an int where it is an integer (no bool) with lo <= v < 2^31; otherwise ``error`` in the name of ``field``."""
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v < 2 ** 31:
+        raise error("%s must be an integer >= %d, got %r" % (field, lo, v))
+    return int(v)
+
+
+def _settings_repr(self):
+    return "%s(%s)" % (type(self).__name__, ", ".join("%s=%r" % (k, getattr(self, k)) for k in self.__slots__))
+
+
 class PoseSmoothing:
     """One-Euro filter settings (Casiez et al.) of a session: ``rate_hz`` the frame rate of the stream, ``min_cutoff`` (Hz) the
     cut-off at rest, ``beta`` its growth per pixel / second of speed, ``d_cutoff`` (Hz) the cut-off of the velocity estimate.  A
@@ -103,9 +121,7 @@ class PoseSmoothing:
 
     def __init__(self, rate_hz, min_cutoff=1.0, beta=0.01, d_cutoff=1.0, min_score=0.0):
         vals = dict(rate_hz=rate_hz, min_cutoff=min_cutoff, beta=beta, d_cutoff=d_cutoff, min_score=min_score)
-        for k, v in vals.items():
-            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(v):
-                raise SmoothingError("PoseSmoothing.%s must be a finite number, got %r" % (k, v))
+        vals = {k: _finite(SmoothingError, "PoseSmoothing." + k, v) for k, v in vals.items()}
         for k in ("rate_hz", "min_cutoff", "d_cutoff"):
             if not vals[k] > 0:
                 raise SmoothingError("PoseSmoothing.%s must be positive, got %r" % (k, vals[k]))
@@ -114,8 +130,7 @@ class PoseSmoothing:
         for k, v in vals.items():
             setattr(self, k, float(v))
 
-    def __repr__(self):
-        return "PoseSmoothing(%s)" % ", ".join("%s=%r" % (k, getattr(self, k)) for k in self.__slots__)
+    __repr__ = _settings_repr
 
 
 class PoseTracking:
@@ -133,23 +148,18 @@ class PoseTracking:
                  min_score=0.0, horizon_s=0.0):
         vals = dict(rate_hz=rate_hz, accel_psd=accel_psd, meas_std=meas_std, heatmap_gain=heatmap_gain, gate=gate,
                     init_speed_std=init_speed_std, min_score=min_score, horizon_s=horizon_s)
-        for k, v in vals.items():
-            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(v):
-                raise TrackingError("PoseTracking.%s must be a finite number, got %r" % (k, v))
+        vals = {k: _finite(TrackingError, "PoseTracking." + k, v) for k, v in vals.items()}
         for k in ("rate_hz", "meas_std", "gate", "init_speed_std"):
             if not vals[k] > 0:
                 raise TrackingError("PoseTracking.%s must be positive, got %r" % (k, vals[k]))
         for k in ("accel_psd", "heatmap_gain", "horizon_s"):
             if vals[k] < 0:
                 raise TrackingError("PoseTracking.%s must not be negative, got %r" % (k, vals[k]))
-        if isinstance(max_coast, bool) or not isinstance(max_coast, (int, np.integer)) or not 0 <= max_coast < 2 ** 31:
-            raise TrackingError("PoseTracking.max_coast must be an integer >= 0, got %r" % (max_coast,))
+        self.max_coast = _count(TrackingError, "PoseTracking.max_coast", max_coast, 0)
         for k, v in vals.items():
             setattr(self, k, float(v))
-        self.max_coast = int(max_coast)
 
-    def __repr__(self):
-        return "PoseTracking(%s)" % ", ".join("%s=%r" % (k, getattr(self, k)) for k in self.__slots__)
+    __repr__ = _settings_repr
 
     def with_horizon(self, horizon_s):
         """A copy that forecasts ``horizon_s`` seconds ahead."""
@@ -171,11 +181,10 @@ class PresenceGate:
             pfa, guard, train = check_cfar(pfa, guard, train)
         except ValueError as e:
             raise PresenceError("PresenceGate: %s" % e) from None
+        vals = dict(pfa=pfa, guard=guard, train=train)
         for k, v, lo in (("min_cells", min_cells, 1), ("confirm", confirm, 1), ("hold", hold, 0)):
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v < 2 ** 31:
-                raise PresenceError("PresenceGate.%s must be an integer >= %d, got %r" % (k, lo, v))
-        for k, v in (("pfa", pfa), ("guard", guard), ("train", train), ("min_cells", int(min_cells)), ("confirm", int(confirm)),
-                     ("hold", int(hold))):
+            vals[k] = _count(PresenceError, "PresenceGate." + k, v, lo)
+        for k, v in vals.items():
             object.__setattr__(self, k, v)
 
     def __setattr__(self, name, value):
@@ -190,8 +199,7 @@ class PresenceGate:
     def __hash__(self):
         return hash(tuple(getattr(self, k) for k in self.__slots__))
 
-    def __repr__(self):
-        return "PresenceGate(%s)" % ", ".join("%s=%r" % (k, getattr(self, k)) for k in self.__slots__)
+    __repr__ = _settings_repr
 
 
 def check_presence(presence):

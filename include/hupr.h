@@ -391,8 +391,10 @@ int hupr_pose_decode_f32(const float* heat, long rows, int H, int W, float ratio
  *             maxval <= 0 (the window is then not read), where m is not positive and finite, or where Mx / m or My / m is not finite.
  * raw_keypoints [rows][2] = ((px + ox) * ratio, (py + oy) * ratio), (0, 0) where maxval <= 0, as in hupr_pose_decode_f32.
  * filter_state_or_null, rate_hz, min_cutoff, beta, d_cutoff, min_score, keypoints_or_null, velocity_or_null: the One-Euro stage of
- *   hupr_pose_decode_f32 on this raw keypoint, word for word: the same [rows][8] state of hupr_pose_filter_state_bytes(rows) bytes
- *   (a session may not mix the two decodes on one state and expect either's track), the same meaning of missing, the same outputs.
+ *   hupr_pose_decode_f32 on this raw keypoint: one definition of the filter serves both entries (csrc/pose_filter.h), so the state is
+ *   the same [rows][8] of hupr_pose_filter_state_bytes(rows) bytes, missing means the same, and equal raw keypoints give equal
+ *   outputs and equal states, bit for bit.  A state may pass from one decode to the other; the filter then goes on from it, on raw
+ *   keypoints that differ between the two decodes.
  * Returns -1 (HUPR_ERR_ARG) before any launch for a null required pointer, radius < 0, H or W below 1, rows or H * W beyond 2^31, and
  * the filter-argument errors of hupr_pose_decode_f32.  rows == 0 is a no-op. */
 int hupr_pose_decode_integral_f32(const float* heat, long rows, int H, int W, float ratio, int radius, float* filter_state_or_null,

@@ -6,6 +6,8 @@ import re
 
 import pytest
 
+from listing import parse_listing
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -97,11 +99,7 @@ def test_hot_kernels_keep_their_register_and_lds_budgets():
         pytest.skip("no device listings (library not built in this tree)")
     meta = {}
     for f in lst:
-        txt = open(f).read()
-        for blk in re.findall(r"- \.agpr_count:.*?(?=\n  - \.agpr_count:|\namdhsa\.target)", txt, flags=re.S):
-            get = lambda key: re.search(r"\.%s:\s+(\S+)" % key, blk).group(1)
-            meta[get("name")] = dict(vgpr=int(get("vgpr_count")), spill=int(get("vgpr_spill_count")),
-                                     scratch=int(get("private_segment_fixed_size")), lds=int(get("group_segment_fixed_size")))
+        meta.update(parse_listing(open(f).read()))
     assert len(meta) >= 150
     # (substring of the mangled name, max unified VGPRs as the code object states them, max static LDS bytes).  512-thread kernels
     # with one workgroup per CU run two waves per SIMD: 256 registers each; the FFT kernels are sized for >= 3-4 waves per SIMD

@@ -5,7 +5,6 @@ rule (``ref_bone`` in tests/bone_loss_ref.py) that tests/test_bone_loss_gpu.py c
 reference is its own statement; it is checked here against torch's fp64 autograd of the same forward and on hand-built planes.
 The sign margin the GPU cases rely on is asserted here too, so the seeds they fix can be checked without a GPU."""
 import ctypes
-import os
 import re
 
 import numpy as np
@@ -14,6 +13,7 @@ import torch
 
 from bone_loss_ref import (A0, A1, CASES, FACTOR, G, SKELETON0, STRIDE, bone_bound, bones_for, make_bone_weights, make_case, ref_bone,
                            ref_position, sign_margin)
+from listing import kernel_metadata
 
 NAN, INF = float("nan"), float("inf")
 
@@ -295,17 +295,7 @@ def test_bone_loss_kernels_use_no_scratch():
     """The listing the build keeps for csrc/bone_loss.hip: the plane and backward kernels in their 16-byte and 4-byte forms and the
     one-workgroup kernel, nothing else; 0 spilled registers, 0 bytes of scratch (the bone table is read from the kernel's arguments,
     not copied to private memory), 256 threads, at most 64 VGPRs (eight waves per SIMD fit)."""
-    import __graft_entry__ as g
-    g.build()
-    path = os.path.join(g.PKG, "build", "bone_loss-hip-amdgcn-amd-amdhsa-gfx950.s")
-    assert os.path.exists(path), "the build keeps the device listing of every source (csrc/Makefile, --save-temps=obj)"
-    txt = open(path).read()
-    meta = {}
-    for blk in re.findall(r"- \.agpr_count:.*?(?=\n  - \.agpr_count:|\namdhsa\.target)", txt, flags=re.S):
-        get = lambda key: re.search(r"\.%s:\s+(\S+)" % key, blk).group(1)
-        meta[get("name")] = dict(vgpr=int(get("vgpr_count")), spill=int(get("vgpr_spill_count")), sspill=int(get("sgpr_spill_count")),
-                                 scratch=int(get("private_segment_fixed_size")), lds=int(get("group_segment_fixed_size")),
-                                 threads=int(get("max_flat_workgroup_size")))
+    meta = kernel_metadata("bone_loss")
     kinds = sorted(re.search(r"hupr_k_bone_loss_[a-z]+(ILb[01]E)?", name).group(0) for name in meta)
     assert kinds == ["hupr_k_bone_loss_bwdILb0E", "hupr_k_bone_loss_bwdILb1E", "hupr_k_bone_loss_planeILb0E",
                      "hupr_k_bone_loss_planeILb1E", "hupr_k_bone_loss_sum"], sorted(meta)

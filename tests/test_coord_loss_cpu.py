@@ -5,12 +5,13 @@ tests/test_coord_loss_gpu.py compares the kernels with (``ref_coord``).  The rul
 is checked here against torch's fp64 autograd of the same forward and on hand-built planes.  The input generator of the GPU tests
 (``make_case``) and the sign margin they assert (``sign_margin``) live here too, so that the seeds they fix can be checked without
 a GPU (``test_the_fixed_seeds_leave_no_sign_to_rounding``)."""
-import os
 import re
 
 import numpy as np
 import pytest
 import torch
+
+from listing import kernel_metadata
 
 NAN, INF = float("nan"), float("inf")
 
@@ -299,17 +300,7 @@ def test_function_refuses_what_it_cannot_run():
 def test_coord_loss_kernels_use_no_scratch():
     """The listing the build keeps for csrc/coord_loss.hip: the plane and backward kernels in their 16-byte and 4-byte forms and the
     sum kernel, nothing else; 0 spilled registers, 0 bytes of scratch, 256 threads, at most 64 VGPRs (eight waves per SIMD fit)."""
-    import __graft_entry__ as g
-    g.build()
-    path = os.path.join(g.PKG, "build", "coord_loss-hip-amdgcn-amd-amdhsa-gfx950.s")
-    assert os.path.exists(path), "the build keeps the device listing of every source (csrc/Makefile, --save-temps=obj)"
-    txt = open(path).read()
-    meta = {}
-    for blk in re.findall(r"- \.agpr_count:.*?(?=\n  - \.agpr_count:|\namdhsa\.target)", txt, flags=re.S):
-        get = lambda key: re.search(r"\.%s:\s+(\S+)" % key, blk).group(1)
-        meta[get("name")] = dict(vgpr=int(get("vgpr_count")), spill=int(get("vgpr_spill_count")), sspill=int(get("sgpr_spill_count")),
-                                 scratch=int(get("private_segment_fixed_size")), lds=int(get("group_segment_fixed_size")),
-                                 threads=int(get("max_flat_workgroup_size")))
+    meta = kernel_metadata("coord_loss")
     kinds = sorted(re.search(r"hupr_k_coord_loss_[a-z]+(ILb[01]E)?", name).group(0) for name in meta)
     assert kinds == ["hupr_k_coord_loss_bwdILb0E", "hupr_k_coord_loss_bwdILb1E", "hupr_k_coord_loss_planeILb0E",
                      "hupr_k_coord_loss_planeILb1E", "hupr_k_coord_loss_sum"], sorted(meta)

@@ -1,11 +1,11 @@
 """CPU (-m "not gpu"): the argument checks of the sub-pixel decode / One-Euro filter at every layer (C ABI through ctypes,
 ``PoseSmoothing``, ``TEST.decode``, ``PoseStream``), and the register / scratch metadata of csrc/pose_decode.hip.  No launch."""
 import copy
-import os
-import re
 
 import pytest
 import torch
+
+from listing import kernel_metadata
 
 
 @pytest.fixture(scope="module")
@@ -166,17 +166,7 @@ def test_stream_command_needs_a_rate_to_smooth():
 
 def test_pose_decode_kernel_uses_no_scratch():
     """The listing the build keeps for csrc/pose_decode.hip: its one kernel with 0 spilled registers, 0 bytes of scratch, no LDS."""
-    import __graft_entry__ as g
-    g.build()
-    path = os.path.join(g.PKG, "build", "pose_decode-hip-amdgcn-amd-amdhsa-gfx950.s")
-    assert os.path.exists(path), "the build keeps the device listing of every source (csrc/Makefile, --save-temps=obj)"
-    txt = open(path).read()
-    meta = {}
-    for blk in re.findall(r"- \.agpr_count:.*?(?=\n  - \.agpr_count:|\namdhsa\.target)", txt, flags=re.S):
-        get = lambda key: re.search(r"\.%s:\s+(\S+)" % key, blk).group(1)
-        meta[get("name")] = dict(vgpr=int(get("vgpr_count")), spill=int(get("vgpr_spill_count")), sspill=int(get("sgpr_spill_count")),
-                                 scratch=int(get("private_segment_fixed_size")), lds=int(get("group_segment_fixed_size")),
-                                 threads=int(get("max_flat_workgroup_size")))
+    meta = kernel_metadata("pose_decode")
     assert len(meta) == 1 and "hupr_k_pose_decode" in next(iter(meta)), sorted(meta)
     assert "hupr_k_stream_keypoints" not in next(iter(meta))
     m = next(iter(meta.values()))

@@ -3,8 +3,6 @@
 register / scratch metadata of csrc/pose_integral.hip, and what the rule is worth, on its fp64 restatement (tests/pose_integral_ref.py):
 against the restated Taylor decode under noise, and on clean targets."""
 import copy
-import os
-import re
 
 import numpy as np
 import pytest
@@ -13,6 +11,7 @@ import torch
 import pose_integral_ref as ref
 from hupr_amd.misc.metrics import default_decode_radius
 from test_pose_decode_gpu import ref_decode as ref_taylor          # the fp64 restatement of hupr_pose_decode_f32's Taylor step
+from listing import kernel_metadata
 
 GOOD = (10.0, 1.0, 0.01, 1.0, 0.0)      # rate_hz, min_cutoff, beta, d_cutoff, min_score
 
@@ -206,17 +205,7 @@ def test_stream_command_takes_the_integral_decode():
 def test_pose_integral_kernel_uses_no_scratch():
     """The listing the build keeps for csrc/pose_integral.hip: its one kernel, 64 threads, with 0 spilled registers, 0 bytes of scratch
     and no LDS — read from the code-object metadata only."""
-    import __graft_entry__ as g
-    g.build()
-    path = os.path.join(g.PKG, "build", "pose_integral-hip-amdgcn-amd-amdhsa-gfx950.s")
-    assert os.path.exists(path), "the build keeps the device listing of every source (csrc/Makefile, --save-temps=obj)"
-    txt = open(path).read()
-    meta = {}
-    for blk in re.findall(r"- \.agpr_count:.*?(?=\n  - \.agpr_count:|\namdhsa\.target)", txt, flags=re.S):
-        get = lambda key: re.search(r"\.%s:\s+(\S+)" % key, blk).group(1)
-        meta[get("name")] = dict(vgpr=int(get("vgpr_count")), spill=int(get("vgpr_spill_count")), sspill=int(get("sgpr_spill_count")),
-                                 scratch=int(get("private_segment_fixed_size")), lds=int(get("group_segment_fixed_size")),
-                                 threads=int(get("max_flat_workgroup_size")))
+    meta = kernel_metadata("pose_integral")
     assert len(meta) == 1 and "hupr_k_pose_decode_integral" in next(iter(meta)), sorted(meta)
     m = next(iter(meta.values()))
     print(m)

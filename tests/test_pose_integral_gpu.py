@@ -287,6 +287,77 @@ def test_one_euro_filter_follows_the_fp64_recurrence_and_a_lost_joint_holds_its_
     assert torch.equal(last[4][:, 0:2], last[2]) and torch.equal(last[4][:, 2:4], last[3]) and last[4][:, 4].eq(1).all().item()
 
 
+PT, PH, PW = 12, 8, 12
+GONE, NEVER, LATE = (3, 8), 13, 20
+
+
+def _bounce(n, length):
+    """0, 1, ..., length - 1, length - 2, ..., 1, 0, 1, ...: a step of one pixel per frame between the two ends."""
+    v = n % (2 * (length - 1))
+    return v if v < length else 2 * (length - 1) - v
+
+
+@functools.lru_cache(maxsize=None)
+def pixel_maps():
+    """(PT, 2 x 14 rows, 8, 12), zero but for one pixel of 0.5 that moves by one pixel per frame, and that pixel's (x, y), (-1, -1) on
+    an empty map.  Even rows bounce inside the map and never touch its border; odd rows run along one of its four edges.  Rows GONE
+    are empty in frames 4-5, row NEVER in every frame, row LATE before frame 6."""
+    maps = np.zeros((PT, FROWS, PH, PW), dtype=np.float32)
+    where = np.full((PT, FROWS, 2), -1)
+    for t in range(PT):
+        for r in range(FROWS):
+            if r == NEVER or (r in GONE and 4 <= t <= 5) or (r == LATE and t < 6):
+                continue
+            if r % 2 == 0:
+                x, y = 1 + _bounce(t + r, PW - 2), 1 + _bounce((0 if r % 4 == 0 else t) + r // 2, PH - 2)
+            elif r % 4 == 1:
+                x, y = _bounce(t + r, PW), (0 if r % 8 == 1 else PH - 1)
+            else:
+                x, y = (0 if r % 8 == 3 else PW - 1), _bounce(t + r, PH)
+            maps[t, r, y, x] = 0.5
+            where[t, r] = x, y
+    maps.setflags(write=False)
+    return maps, where
+
+
+def test_both_decodes_run_one_filter_on_one_state_layout():
+    """On a map that is one pixel, ``pose_decode(refine=False)`` and ``pose_decode_integral(radius=2)`` decode the same raw keypoint
+    exactly (offset 0 in both: the window's mass is that pixel), so the One-Euro filter behind them (csrc/pose_filter.h) must give the
+    same bits: filtered keypoints, velocity and state in every frame, also after the two state tensors change hands halfway."""
+    from hupr_amd import functional as F_
+    from hupr_amd.tools import PoseSmoothing
+    maps, where = pixel_maps()
+    border = (where[..., 0] == 0) | (where[..., 0] == PW - 1) | (where[..., 1] == 0) | (where[..., 1] == PH - 1)
+    assert (~border.any(axis=0)).sum() >= FROWS // 2                                      # off the border on at least half the rows
+    seen = (where[1:, :, 0] >= 0) & (where[:-1, :, 0] >= 0)
+    assert (np.abs(np.diff(where, axis=0)).max(axis=-1)[seen] == 1).all() and seen.sum() > 200         # one pixel per frame
+    sm = PoseSmoothing(10.0, beta=0.05)
+    heat = dev(maps).view(PT, 2, 14, PH, PW)
+    s_taylor, s_integral = F_.pose_filter_state(FROWS, "cuda"), F_.pose_filter_state(FROWS, "cuda")
+    seq = []
+    for t in range(PT):
+        if t == PT // 2:
+            s_taylor, s_integral = s_integral, s_taylor
+        a = F_.pose_decode(heat[t], RATIO, refine=False, filter_state=s_taylor, smoothing=sm)
+        b = F_.pose_decode_integral(heat[t], RATIO, 2, filter_state=s_integral, smoothing=sm)
+        for what, u, v in zip(("index", "maximum", "raw keypoints", "filtered keypoints", "velocity"), a, b):
+            assert torch.equal(u.view(torch.int32), v.view(torch.int32)), (what, t)       # bit for bit
+        assert torch.equal(s_taylor.view(torch.int32), s_integral.view(torch.int32)), ("state", t)
+        want = np.where(where[t] >= 0, where[t], 0).astype(np.float32) * np.float32(RATIO)
+        assert np.array_equal(a[2].reshape(FROWS, 2).cpu().numpy(), want), t
+        seq.append([x.reshape(FROWS, 2).clone() for x in a[2:]])
+    raws, kps, vels = zip(*seq)
+    # the filter did something to compare: it lags, it reports speeds, and the special rows took the paths they are there for
+    assert max((k - r).abs().max().item() for k, r in zip(kps, raws)) > 1.0 and max(v.abs().max().item() for v in vels) > 5.0
+    for r in GONE:
+        for t in (4, 5):
+            assert torch.equal(kps[t][r], kps[3][r]) and not vels[t][r].any().item() and not raws[t][r].any().item()
+        assert not torch.equal(kps[6][r], kps[3][r])
+    assert not s_taylor[NEVER].any().item() and all(not k[NEVER].any().item() for k in kps)
+    assert not any(k[LATE].any().item() for k in kps[:6]) and torch.equal(kps[6][LATE], raws[6][LATE]) and not vels[6][LATE].any().item()
+    assert vels[7][LATE].any().item() and s_taylor[:, 4].tolist() == [0.0 if r == NEVER else 1.0 for r in range(FROWS)]
+
+
 # ---- 7: the live stream --------------------------------------------------------------------------------------------------------------------------
 class _IntegralCtx(_Ctx):
     """tests/test_stream_decode_gpu.py's context with the session's decode arguments as the key."""

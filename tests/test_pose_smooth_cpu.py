@@ -12,6 +12,7 @@ import pytest
 
 import pose_smooth_ref as sr
 import pose_track_ref as ref
+from listing import kernel_metadata
 
 
 def _truth():
@@ -132,19 +133,7 @@ def test_the_fp32_restatement_agrees_with_the_fp64_one():
 def test_pose_smooth_kernel_uses_no_scratch():
     """The listing the build keeps for csrc/pose_smooth.hip: its one kernel, 64 threads, with 0 spilled registers, 0 bytes of scratch
     and no LDS — read from the code-object metadata only (DESIGN.md records the register count)."""
-    import os
-    import re
-    import __graft_entry__ as g
-    g.build()
-    path = os.path.join(g.PKG, "build", "pose_smooth-hip-amdgcn-amd-amdhsa-gfx950.s")
-    assert os.path.exists(path), "the build keeps the device listing of every source (csrc/Makefile, --save-temps=obj)"
-    txt = open(path).read()
-    meta = {}
-    for blk in re.findall(r"- \.agpr_count:.*?(?=\n  - \.agpr_count:|\namdhsa\.target)", txt, flags=re.S):
-        get = lambda key: re.search(r"\.%s:\s+(\S+)" % key, blk).group(1)
-        meta[get("name")] = dict(vgpr=int(get("vgpr_count")), spill=int(get("vgpr_spill_count")), sspill=int(get("sgpr_spill_count")),
-                                 scratch=int(get("private_segment_fixed_size")), lds=int(get("group_segment_fixed_size")),
-                                 threads=int(get("max_flat_workgroup_size")))
+    meta = kernel_metadata("pose_smooth")
     assert len(meta) == 1 and "hupr_k_pose_smooth_rts" in next(iter(meta)), sorted(meta)
     m = next(iter(meta.values()))
     print(m)

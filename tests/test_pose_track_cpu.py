@@ -1,14 +1,13 @@
 """CPU (-m "not gpu"): the argument checks of the Kalman joint tracker at every layer (C ABI through ctypes, ``PoseTracking``,
 ``functional.pose_track``, ``PoseStream``, the command line), ``TrackedPoseFrame``, the register / scratch metadata of
 csrc/pose_track.hip, and the rule's own worth on its fp64 restatement (tests/pose_track_ref.py).  No launch."""
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
 import pose_track_ref as ref
+from listing import kernel_metadata
 
 
 @pytest.fixture(scope="module")
@@ -191,17 +190,7 @@ def test_stream_command_tracking_arguments():
 def test_pose_track_kernel_uses_no_scratch():
     """The listing the build keeps for csrc/pose_track.hip: its one kernel, 64 threads, with 0 spilled registers, 0 bytes of scratch
     and no LDS — read from the code-object metadata only."""
-    import __graft_entry__ as g
-    g.build()
-    path = os.path.join(g.PKG, "build", "pose_track-hip-amdgcn-amd-amdhsa-gfx950.s")
-    assert os.path.exists(path), "the build keeps the device listing of every source (csrc/Makefile, --save-temps=obj)"
-    txt = open(path).read()
-    meta = {}
-    for blk in re.findall(r"- \.agpr_count:.*?(?=\n  - \.agpr_count:|\namdhsa\.target)", txt, flags=re.S):
-        get = lambda key: re.search(r"\.%s:\s+(\S+)" % key, blk).group(1)
-        meta[get("name")] = dict(vgpr=int(get("vgpr_count")), spill=int(get("vgpr_spill_count")), sspill=int(get("sgpr_spill_count")),
-                                 scratch=int(get("private_segment_fixed_size")), lds=int(get("group_segment_fixed_size")),
-                                 threads=int(get("max_flat_workgroup_size")))
+    meta = kernel_metadata("pose_track")
     assert len(meta) == 1 and "hupr_k_pose_track" in next(iter(meta)), sorted(meta)
     m = next(iter(meta.values()))
     print(m)

@@ -4,6 +4,7 @@ import pytest
 import torch
 
 from hupr_amd.datasets.dataset import window_indices
+from listing import kernel_metadata
 
 DURATIONS = (1, 2, 3, 5, 8, 20, 600)
 GROUPS = (2, 4, 8)
@@ -148,18 +149,7 @@ def test_stream_entry_points_check_their_arguments_on_the_host():
 def test_stream_kernels_use_no_scratch():
     """The listing the build keeps for csrc/stream_window.hip: every kernel of the file with 0 spilled registers and 0 bytes of
     scratch, the window kernel in both stores within one wave's 256 registers (two waves per SIMD at least)."""
-    import os
-    import re
-    import __graft_entry__ as g
-    g.build()
-    path = os.path.join(g.PKG, "build", "stream_window-hip-amdgcn-amd-amdhsa-gfx950.s")
-    assert os.path.exists(path), "the build keeps the device listing of every source (csrc/Makefile, --save-temps=obj)"
-    txt = open(path).read()
-    meta = {}
-    for blk in re.findall(r"- \.agpr_count:.*?(?=\n  - \.agpr_count:|\namdhsa\.target)", txt, flags=re.S):
-        get = lambda key: re.search(r"\.%s:\s+(\S+)" % key, blk).group(1)
-        meta[get("name")] = dict(vgpr=int(get("vgpr_count")), spill=int(get("vgpr_spill_count")), sspill=int(get("sgpr_spill_count")),
-                                 scratch=int(get("private_segment_fixed_size")), lds=int(get("group_segment_fixed_size")))
+    meta = kernel_metadata("stream_window")
     for pat, count in (("hupr_k_mnet_stream", 2), ("hupr_k_stream_advance", 1), ("hupr_k_stream_reset", 1), ("hupr_k_stream_keypoints", 1)):
         assert len([n for n in meta if pat in n]) == count, (pat, sorted(meta))
     for n, m in meta.items():

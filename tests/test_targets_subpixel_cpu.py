@@ -3,12 +3,12 @@ hupr_gaussian_targets_subpixel_f32 through ctypes, ``TRAINING.targets`` / ``Loss
 ``functional.gaussian_targets_subpixel``'s argument handling, ``misc.oks_eval.mean_position_error`` on hand-built records, and the
 register / scratch metadata of csrc/targets.hip."""
 import copy
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
+
+from listing import kernel_metadata
 
 
 @pytest.fixture(scope="module")
@@ -131,17 +131,7 @@ def test_mean_position_error_on_hand_built_records():
 def test_targets_kernels_use_no_scratch():
     """The listing the build keeps for csrc/targets.hip: the two forms of its one kernel (16-byte and 4-byte stores) and nothing else,
     0 spilled registers, 0 bytes of scratch, no LDS, at most 64 VGPRs."""
-    import __graft_entry__ as g
-    g.build()
-    path = os.path.join(g.PKG, "build", "targets-hip-amdgcn-amd-amdhsa-gfx950.s")
-    assert os.path.exists(path), "the build keeps the device listing of every source (csrc/Makefile, --save-temps=obj)"
-    txt = open(path).read()
-    meta = {}
-    for blk in re.findall(r"- \.agpr_count:.*?(?=\n  - \.agpr_count:|\namdhsa\.target)", txt, flags=re.S):
-        get = lambda key: re.search(r"\.%s:\s+(\S+)" % key, blk).group(1)
-        meta[get("name")] = dict(vgpr=int(get("vgpr_count")), spill=int(get("vgpr_spill_count")), sspill=int(get("sgpr_spill_count")),
-                                 scratch=int(get("private_segment_fixed_size")), lds=int(get("group_segment_fixed_size")),
-                                 threads=int(get("max_flat_workgroup_size")))
+    meta = kernel_metadata("targets")
     assert len(meta) == 2 and all("hupr_k_gaussian_targets_subpixel" in name for name in meta), sorted(meta)
     assert {name[name.index("subpixelILb"):][:13] for name in meta} == {"subpixelILb0E", "subpixelILb1E"}, sorted(meta)
     for name, m in meta.items():
