@@ -23,7 +23,7 @@ struct HaloArgs {
     int nd, nh, nw;          // tiles per axis
     int n_co_tiles;
     int ablate;              // profiling only (128-voxel kernel): bit0 skip halo fill, bit2 skip epilogue stores; always 0 — its setter
-                             // hupr_debug_halo_ablate went with the script that used it (the debug header holds at most 13 entries)
+                             // hupr_debug_halo_ablate went with the script that used it (the debug header holds at most 11 switches)
     unsigned long long* trace;  // profiling only: s_memtime stamps of workgroup 0 / wave 0 (scripts/halo_trace.py) or null
     double* stats;           // 256-voxel kernel, bf16 output, no bias / residual: per-workgroup column sums [grid][2][Co] of the
                              // stored (rounded) output and its square — the BatchNorm statistics pass fused into the epilogue

@@ -403,14 +403,21 @@ __global__ __launch_bounds__(256) void hupr_k_interp_bwd(const T* __restrict__ d
 
 using namespace hupr;
 
+// Workgroups of the three MNet launches, decided once for the launchers and for hupr_debug_mnet_grid: op 0 hupr_k_mnet_fwd and op 1
+// hupr_k_mnet_fwd_means walk 256 pixels per pass on at most 8192 workgroups, op 2 hupr_k_mnet_bwd 64 pixels per pass on at most 1024
+// (partial[grid][160] is what hupr_mnet_bwd_ws_bytes sizes).
+static int mnet_grid(int op, long n_bg, int pixels) {
+    const long total = n_bg * pixels;
+    return (op == 2) ? (int)min((long)1024, (total + 63) / 64) : (int)min((long)8192, (total + 255) / 256);
+}
+
 // (a3) MNet forward.  x: (n_bg = B*G, F=8, 2, pixels = R*A, E=8) fp32;  w: (32,2,2,1,1); bias: (32)
 // out: (n_bg, pixels, 32) channels-last, fp32 or (bf16act) bf16
 template <typename T>
 static int mnet_fwd(const char* who, const float* x, const float* w, const float* bias, T* out, float* means, long n_bg,
                     int pixels, hupr_stream_t stream) {
     HUPR_REQUIRE(x && w && bias && out && n_bg > 0 && pixels > 0, "%s: bad argument", who);
-    const long total = n_bg * pixels;
-    const int grid = (int)min((long)8192, (total + 255) / 256);
+    const int grid = mnet_grid(0, n_bg, pixels);
     HUPR_LAUNCH(hupr_k_mnet_fwd<T>, dim3(grid), dim3(256), 0, as_stream(stream), x, w, bias, out, means, n_bg, pixels);
     HUPR_LAUNCH_OK("hupr_k_mnet_fwd");
     return HUPR_OK;
@@ -428,8 +435,7 @@ template <typename T>
 static int mnet_fwd_means(const char* who, const float* mp, const float* w, const float* bias, T* out, float* means, long n_bg,
                           int pixels, hupr_stream_t stream) {
     HUPR_REQUIRE(mp && w && bias && out && n_bg > 0 && pixels > 0, "%s: bad argument", who);
-    const long total = n_bg * pixels;
-    const int grid = (int)min((long)8192, (total + 255) / 256);
+    const int grid = mnet_grid(1, n_bg, pixels);
     HUPR_LAUNCH(hupr_k_mnet_fwd_means<T>, dim3(grid), dim3(256), 0, as_stream(stream), mp, w, bias, out, means, n_bg, pixels);
     HUPR_LAUNCH_OK("hupr_k_mnet_fwd_means");
     return HUPR_OK;
@@ -451,8 +457,7 @@ static int mnet_bwd(const char* who, const float* x, const float* means, const f
                     float* dw, float* dbias, long n_bg, int pixels, void* ws, size_t ws_bytes, hupr_stream_t stream) {
     HUPR_REQUIRE((x || means) && w && bias && dy && dw && dbias && ws && n_bg > 0 && pixels > 0, "%s: bad argument", who);
     if (ws_bytes < hupr_mnet_bwd_ws_bytes()) return fail(HUPR_ERR_WORKSPACE, "%s: workspace too small", who);
-    const long total = n_bg * pixels;
-    const int grid = (int)min((long)1024, (total + 63) / 64);      // 64 pixels per workgroup pass; partial[grid][160]
+    const int grid = mnet_grid(2, n_bg, pixels);
     hipStream_t s = as_stream(stream);
     HUPR_LAUNCH(hupr_k_mnet_bwd<T>, dim3(grid), dim3(256), 0, s, x, w, bias, dy, means, n_bg, pixels,
                        reinterpret_cast<float*>(ws));
@@ -473,6 +478,11 @@ extern "C" int hupr_mnet_bwd_bf16act(const float* x_or_null, const float* means_
                     pixels, ws, ws_bytes, stream);
 }
 
+extern "C" int hupr_debug_mnet_grid(int op, long n_bg, int pixels) {
+    HUPR_REQUIRE(op >= 0 && op <= 2 && n_bg > 0 && pixels > 0, "hupr_debug_mnet_grid: bad argument");
+    return mnet_grid(op, n_bg, pixels);
+}
+
 static int interp_check(const char* who, int Bn, int Di, int Hi, int Wi, int Do, int Ho, int Wo, int C, int in_ld,
                         int out_ld) {
     HUPR_REQUIRE(Bn > 0 && Di > 0 && Hi > 0 && Wi > 0 && Do > 0 && Ho > 0 && Wo > 0, "%s: bad extents", who);
@@ -481,15 +491,50 @@ static int interp_check(const char* who, int Bn, int Di, int Hi, int Wi, int Do,
     return HUPR_OK;
 }
 
+// The launch decision of the six resampling entry points, made once for the launchers and for hupr_debug_interp_route: the argument
+// checks (all but the pointers), the channel vectors per thread and the workgroups.  V: channels per 16-byte vector of the storage
+// type (4 fp32, 8 bf16).  The forward kernel walks (output voxel, 4 channels) items on at most 8192 workgroups; the backward gather
+// (input voxel, VPT vectors of V channels) items on at most 16384, with 4 vectors per thread while the grid stays full.
+struct InterpPlan {
+    int vpt, grid;
+};
+static int interp_plan(const char* who, bool backward, int V, int Bn, int Di, int Hi, int Wi, int Do, int Ho, int Wo, int C,
+                       int in_ld, int out_ld, InterpPlan* p) {
+    int rc = interp_check(who, Bn, Di, Hi, Wi, Do, Ho, Wo, C, in_ld, out_ld);
+    if (rc) return rc;
+    if (!backward) {
+        const long total = (long)Bn * Do * Ho * Wo * (C / 4);
+        p->vpt = 1;
+        p->grid = (int)min((long)8192, (total + 255) / 256);
+        return HUPR_OK;
+    }
+    HUPR_REQUIRE(C % V == 0 && in_ld % V == 0 && out_ld % V == 0, "%s: channels / strides must be multiples of %d", who, V);
+    const long voxels = (long)Bn * Di * Hi * Wi;
+    p->vpt = (C % (4 * V) == 0 && voxels * (C / (4 * V)) >= 256 * 256) ? 4 : 1;       // 4 vectors per thread while the grid stays full
+    const long total = voxels * (C / (p->vpt * V));
+    p->grid = (int)min((long)16384, (total + 255) / 256);
+    return HUPR_OK;
+}
+
+extern "C" int hupr_debug_interp_route(int op, int bf16, int Bn, int Di, int Hi, int Wi, int Do, int Ho, int Wo, int C, int in_ld,
+                                       int out_ld, int* grid_out) {
+    HUPR_REQUIRE(op >= 0 && op <= 2, "hupr_debug_interp_route: bad op %d", op);
+    InterpPlan p;
+    int rc = interp_plan("hupr_debug_interp_route", op != 0, bf16 ? 8 : 4, Bn, Di, Hi, Wi, Do, Ho, Wo, C, in_ld, out_ld, &p);
+    if (rc) return rc;
+    if (grid_out) *grid_out = p.grid;
+    return p.vpt;
+}
+
 template <typename T>
 static int interp_fwd(const char* who, const T* x, T* y, int Bn, int Di, int Hi, int Wi, int Do, int Ho, int Wo, int C,
                       int in_ld, int out_ld, hupr_stream_t stream) {
     HUPR_REQUIRE(x && y, "%s: null pointer", who);
-    int rc = interp_check(who, Bn, Di, Hi, Wi, Do, Ho, Wo, C, in_ld, out_ld);
+    InterpPlan p;
+    int rc = interp_plan(who, false, ActVec<T>::V, Bn, Di, Hi, Wi, Do, Ho, Wo, C, in_ld, out_ld, &p);
     if (rc) return rc;
-    const long total = (long)Bn * Do * Ho * Wo * (C / 4);
-    HUPR_LAUNCH((hupr_k_interp_fwd<T, false>), dim3((int)min((long)8192, (total + 255) / 256)), dim3(256), 0,
-                       as_stream(stream), x, y, Bn, Di, Hi, Wi, Do, Ho, Wo, C, in_ld, out_ld);
+    HUPR_LAUNCH((hupr_k_interp_fwd<T, false>), dim3(p.grid), dim3(256), 0, as_stream(stream), x, y, Bn, Di, Hi, Wi, Do, Ho, Wo, C,
+                in_ld, out_ld);
     HUPR_LAUNCH_OK("hupr_k_interp_fwd");
     return HUPR_OK;
 }
@@ -508,20 +553,15 @@ template <typename T, bool ACC = false>
 static int interp_bwd(const char* who, const T* dy, T* dx, int Bn, int Di, int Hi, int Wi, int Do, int Ho, int Wo, int C,
                       int in_ld, int out_ld, hupr_stream_t stream) {
     HUPR_REQUIRE(dy && dx, "%s: null pointer", who);
-    int rc = interp_check(who, Bn, Di, Hi, Wi, Do, Ho, Wo, C, in_ld, out_ld);
+    InterpPlan p;
+    int rc = interp_plan(who, true, ActVec<T>::V, Bn, Di, Hi, Wi, Do, Ho, Wo, C, in_ld, out_ld, &p);
     if (rc) return rc;
-    constexpr int V = ActVec<T>::V;
-    HUPR_REQUIRE(C % V == 0 && in_ld % V == 0 && out_ld % V == 0, "%s: channels / strides must be multiples of %d", who, V);
-    const long voxels = (long)Bn * Di * Hi * Wi;
-    if (C % (4 * V) == 0 && voxels * (C / (4 * V)) >= 256 * 256) {       // 4 vectors per thread while the grid stays full
-        const long total = voxels * (C / (4 * V));
-        HUPR_LAUNCH((hupr_k_interp_bwd<T, 4, ACC>), dim3((int)min((long)16384, (total + 255) / 256)), dim3(256), 0,
-                           as_stream(stream), dy, dx, Bn, Di, Hi, Wi, Do, Ho, Wo, C, in_ld, out_ld);
-    } else {
-        const long total = voxels * (C / V);
-        HUPR_LAUNCH((hupr_k_interp_bwd<T, 1, ACC>), dim3((int)min((long)16384, (total + 255) / 256)), dim3(256), 0,
-                           as_stream(stream), dy, dx, Bn, Di, Hi, Wi, Do, Ho, Wo, C, in_ld, out_ld);
-    }
+    if (p.vpt == 4)
+        HUPR_LAUNCH((hupr_k_interp_bwd<T, 4, ACC>), dim3(p.grid), dim3(256), 0, as_stream(stream), dy, dx, Bn, Di, Hi, Wi, Do, Ho,
+                    Wo, C, in_ld, out_ld);
+    else
+        HUPR_LAUNCH((hupr_k_interp_bwd<T, 1, ACC>), dim3(p.grid), dim3(256), 0, as_stream(stream), dy, dx, Bn, Di, Hi, Wi, Do, Ho,
+                    Wo, C, in_ld, out_ld);
     HUPR_LAUNCH_OK("hupr_k_interp_bwd");
     return HUPR_OK;
 }

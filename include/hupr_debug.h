@@ -35,6 +35,15 @@ int hupr_debug_wgrad_route(int Bn, int D, int H, int W, int Ci, int in_ld, int C
      * launched.  HUPR_ERR_ARG / HUPR_ERR_WORKSPACE where the call is refused.  route & 15: 1 hupr_k_wgrad_halo_m16<true> (3-D taps), 2
      * m16<false>, 3 m16<true, true> (K quarters); 4-7 hupr_k_wgrad_halo_glds<IS3D, CI32> = 4 + 2 * IS3D + CI32 (the 32 x 32 x 16 kernel);
      * 8-11 the register-staged hupr_k_wgrad_halo_bf16<ABF, IS3D> = 8 + 2 * ABF + IS3D.  + 16: the XCD-aware 1-D grid; + 32: two gradients */
+int hupr_debug_interp_route(int op, int bf16, int Bn, int Di, int Hi, int Wi, int Do, int Ho, int Wo, int C, int in_ld, int out_ld,
+                            int* grid_out);
+    /* test aid: the launch hupr_interp_linear_fwd_* (op 0), _bwd_* (op 1) or _bwd_acc_* (op 2) would make, _f32 (bf16 = 0) or _bf16act
+     * (bf16 = 1), from the plan the launchers themselves use (csrc/spatial.hip: interp_plan).  Nothing is launched.  Returns the channel
+     * vectors per thread of the kernel (forward: 1; backward: 1 or 4), HUPR_ERR_ARG where the call is refused; *grid_out (may be null): its
+     * workgroups. */
+int hupr_debug_mnet_grid(int op, long n_bg, int pixels);
+    /* test aid: the workgroups of hupr_mnet_fwd_* (op 0), hupr_mnet_fwd_means_* (op 1) or hupr_mnet_bwd_* (op 2) on n_bg x pixels, from the
+     * function the launchers themselves use; HUPR_ERR_ARG for another op or an empty extent.  Nothing is launched. */
 #ifdef __cplusplus
 }
 #endif
