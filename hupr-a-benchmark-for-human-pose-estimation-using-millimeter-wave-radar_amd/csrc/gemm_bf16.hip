@@ -386,22 +386,16 @@ __global__ __launch_bounds__(256) void hupr_k_gemm_bf16(GemmArgs p) {
 }
 
 template <int BM, int BN, int WM, int WN, int AM, int BMD>
-static void launch_h(const GemmArgs& a, int batch, hipStream_t s) {
-    const int mt = (a.M + BM - 1) / BM, nt = (a.N + BN - 1) / BN;
-    HUPR_LAUNCH((hupr_k_gemm_bf16<BM, BN, WM, WN, AM, BMD>), dim3(mt * nt, a.ksplit, batch), dim3(256), 0, s, a);
+static void launch_h(const GemmArgs& a, int grid_x, int batch, hipStream_t s) {
+    HUPR_LAUNCH((hupr_k_gemm_bf16<BM, BN, WM, WN, AM, BMD>), dim3(grid_x, a.ksplit, batch), dim3(256), 0, s, a);
 }
 
 template <int AM, int BMD>
-static void dispatch_h(const GemmArgs& a, int batch, hipStream_t s) {
-    auto blocks = [&](int bm, int bn) { return (long)((a.M + bm - 1) / bm) * ((a.N + bn - 1) / bn) * batch; };
-    if (a.N > 64) {
-        if (a.M > 64 && blocks(128, 128) >= 512) launch_h<128, 128, 2, 2, AM, BMD>(a, batch, s);
-        else if (blocks(64, 128) >= 512) launch_h<64, 128, 1, 4, AM, BMD>(a, batch, s);
-        else launch_h<64, 64, 2, 2, AM, BMD>(a, batch, s);      // small problems (level-0 attention GEMMs): two workgroups per CU
-    } else {
-        if (a.M > 64 && blocks(128, 64) >= 512) launch_h<128, 64, 2, 2, AM, BMD>(a, batch, s);
-        else launch_h<64, 64, 2, 2, AM, BMD>(a, batch, s);
-    }
+static void dispatch_h(const GemmArgs& a, const GemmPlan& p, hipStream_t s) {
+    if (p.bm == 128 && p.bn == 128) launch_h<128, 128, 2, 2, AM, BMD>(a, p.grid_x, p.grid_z, s);
+    else if (p.bm == 64 && p.bn == 128) launch_h<64, 128, 1, 4, AM, BMD>(a, p.grid_x, p.grid_z, s);
+    else if (p.bm == 128 && p.bn == 64) launch_h<128, 64, 2, 2, AM, BMD>(a, p.grid_x, p.grid_z, s);
+    else launch_h<64, 64, 2, 2, AM, BMD>(a, p.grid_x, p.grid_z, s);
 }
 
 }  // namespace hupr
@@ -412,7 +406,9 @@ extern "C" int hupr_gemm_bf16(int ta, int tb, const float* A, const float* B, fl
                               long ldb, long ldc, int batch, long a_bs, long b_bs, long c_bs, const float* res,
                               long res_ld, long res_bs, int accumulate, hupr_stream_t stream) {
     HUPR_REQUIRE(A && B && C, "hupr_gemm_bf16: null pointer");
-    HUPR_REQUIRE(M > 0 && N > 0 && K > 0 && batch > 0 && batch <= 65535, "hupr_gemm_bf16: bad shape %d %d %d x%d", M, N, K, batch);
+    GemmPlan p;
+    int rc = gemm_plan("hupr_gemm_bf16", 1, ta, tb, M, N, K, batch, &p);
+    if (rc) return rc;
     GemmArgs a;
     fill_common(a);
     a.A = A; a.B = B; a.C = C; a.M = M; a.N = N; a.K = K;
@@ -421,10 +417,9 @@ extern "C" int hupr_gemm_bf16(int ta, int tb, const float* A, const float* B, fl
     a.res = res; a.res_ld = res_ld; a.res_bs0 = res_bs;
     a.accumulate = accumulate;
     hipStream_t s = as_stream(stream);
-    if (ta == 0 && tb == 1) dispatch_h<A_ROWK, B_NK>(a, batch, s);
-    else if (ta == 0 && tb == 0) dispatch_h<A_ROWK, B_KN>(a, batch, s);
-    else if (ta == 1 && tb == 0) dispatch_h<A_KM, B_KN>(a, batch, s);
-    else return fail(HUPR_ERR_ARG, "hupr_gemm_bf16: unsupported transpose combination %d %d", ta, tb);
+    if (ta == 0 && tb == 1) dispatch_h<A_ROWK, B_NK>(a, p, s);
+    else if (ta == 0 && tb == 0) dispatch_h<A_ROWK, B_KN>(a, p, s);
+    else dispatch_h<A_KM, B_KN>(a, p, s);
     HUPR_LAUNCH_OK("hupr_k_gemm_bf16");
     return HUPR_OK;
 }
@@ -437,20 +432,17 @@ static int conv_fwd_h(const char* who, const void* x, const float* wp, const flo
     GemmArgs a;
     fill_common(a);
     a.g = ConvGeom{Di, Hi, Wi, Ci, in_ld, Do, Ho, Wo, kd, kh, kw, pd, ph, pw};
-    int rc = check_geom(who, Bn, a.g, Co, 8);
+    GemmPlan p;
+    int rc = conv_fwd_plan(who, 1, Bn, a.g, Co, flags, accumulate, res != nullptr, &p);
     if (rc) return rc;
-    HUPR_REQUIRE(Do == Di + 2 * pd - kd + 1 && Ho == Hi + 2 * ph - kh + 1 && Wo == Wi + 2 * pw - kw + 1,
-                 "%s: output extent does not match stride-1 convolution", who);
-    HUPR_REQUIRE(!(flags & GEMM_C_BF16) || (!accumulate && !res), "%s: bf16 output excludes accumulate/residual", who);
     const long M = (long)Bn * Do * Ho * Wo;
-    HUPR_REQUIRE(M < (1L << 31), "%s: too many output voxels", who);
     a.A = reinterpret_cast<const float*>(x); a.B = wp; a.C = reinterpret_cast<float*>(y);
     a.M = (int)M; a.N = Co; a.K = kd * kh * kw * Ci;
     a.lda = 0; a.ldb = a.K; a.ldc = out_ld;
     a.bias = bias; a.res = res; a.res_ld = res_ld;
     a.accumulate = accumulate;
     a.flags = flags;
-    dispatch_h<A_CONV, B_NK>(a, 1, as_stream(stream));
+    dispatch_h<A_CONV, B_NK>(a, p, as_stream(stream));
     HUPR_LAUNCH_OK("hupr_k_gemm_bf16<conv>");
     return HUPR_OK;
 }
@@ -489,7 +481,9 @@ extern "C" int hupr_tmerge_dgrad_bf16(const float* dy, const float* wp1, void* d
     a.b_bs0 = 0; a.b_bs1 = -(long)Co;
     a.c_bs0 = (long)G * HW * Ci; a.c_bs1 = (long)HW * Ci;
     a.flags = dx_bf16 ? GEMM_C_BF16 : 0;
-    dispatch_h<A_ROWK, B_NK>(a, Bn * G, as_stream(stream));
+    GemmPlan p;
+    gemm_tile_plan(1, a.M, a.N, Bn * G, &p);
+    dispatch_h<A_ROWK, B_NK>(a, p, as_stream(stream));
     HUPR_LAUNCH_OK("hupr_k_gemm_bf16<tmerge dgrad>");
     return HUPR_OK;
 }
@@ -501,31 +495,22 @@ static int conv_wgrad_h(const void* x, int x_bf16, const float* dy, float* dw, i
     GemmArgs a;
     fill_common(a);
     a.g = ConvGeom{Di, Hi, Wi, Ci, in_ld, Do, Ho, Wo, kd, kh, kw, pd, ph, pw};
-    int rc = check_geom("hupr_conv_wgrad_bf16", Bn, a.g, Co, 4);
+    WgradPlan p;
+    int rc = wgrad_plan("hupr_conv_wgrad_bf16", 1, Bn, a.g, Co, x_bf16, ws_bytes, (reinterpret_cast<uintptr_t>(ws) & 15) == 0, &p);
     if (rc) return rc;
     const long Mv = (long)Bn * Do * Ho * Wo;
-    HUPR_REQUIRE(Mv < (1L << 31), "hupr_conv_wgrad_bf16: too many output voxels");
     const int taps = kd * kh * kw;
     a.A = dy; a.B = reinterpret_cast<const float*>(x); a.C = reinterpret_cast<float*>(ws);
     a.flags = x_bf16 ? GEMM_B_BF16 : 0;
     a.M = Co; a.N = taps * Ci; a.K = (int)Mv;
     a.lda = dy_ld; a.ldb = 0; a.ldc = a.N;
-    const int bm = (Co <= 64) ? 64 : 128;
-    const long tiles = (long)((Co + bm - 1) / bm) * ((a.N + 127) / 128);
-    const int ktiles = (int)((Mv + BKH - 1) / BKH);
     a.split_stride = (long)a.M * a.N;
-    const size_t in_bytes = (size_t)Mv * ((size_t)Co * sizeof(float) + (size_t)taps * Ci * (x_bf16 ? 2 : 4));
-    int splits = wgrad_splits(tiles, ktiles, (size_t)a.split_stride * sizeof(float), in_bytes);
-    while (splits > 1 && (size_t)splits * a.split_stride * sizeof(float) > ws_bytes) splits >>= 1;
-    a.ksplit = splits;
-    if (ws_bytes < (size_t)splits * a.split_stride * sizeof(float))
-        return fail(HUPR_ERR_WORKSPACE, "hupr_conv_wgrad_bf16: workspace %zu < %zu", ws_bytes,
-                    (size_t)splits * a.split_stride * sizeof(float));
+    a.ksplit = p.splits;
     hipStream_t s = as_stream(stream);
-    if (bm == 64) launch_h<64, 128, 1, 4, A_KM, B_CONVK>(a, 1, s);
-    else launch_h<128, 128, 2, 2, A_KM, B_CONVK>(a, 1, s);
+    if (p.bm == 64) launch_h<64, 128, 1, 4, A_KM, B_CONVK>(a, p.grid_x, 1, s);
+    else launch_h<128, 128, 2, 2, A_KM, B_CONVK>(a, p.grid_x, 1, s);
     HUPR_LAUNCH_OK("hupr_k_gemm_bf16<wgrad>");
-    launch_splitk_reduce(reinterpret_cast<const float*>(ws), dw, a.split_stride, splits, a.split_stride, taps, Ci, s);
+    launch_splitk_reduce(reinterpret_cast<const float*>(ws), dw, a.split_stride, p.splits, a.split_stride, taps, Ci, s);
     HUPR_LAUNCH_OK("hupr_k_splitk_reduce");
     return HUPR_OK;
 }

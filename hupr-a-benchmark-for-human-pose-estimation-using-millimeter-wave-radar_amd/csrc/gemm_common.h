@@ -82,4 +82,98 @@ inline int wgrad_splits(long tiles, long ktiles, size_t one_bytes, size_t in_byt
 void launch_splitk_reduce(const float* part, float* out, long n, int splits, long split_stride, int taps, int ci,
                           hipStream_t s, float* out2 = nullptr, long n_first = 0);
 
+// ---- launch plans ---------------------------------------------------------------------------------------------------------------
+// Every launch decision of the two engines is made once, here, for the launchers and for hupr_debug_gemm_route: the argument checks
+// (all but the pointers), the tile, the grid, and for a weight gradient the K slices, the workspace it needs and the reduce kernel.
+// engine: 0 = gemm_f32.hip (32-deep K tiles), 1 = gemm_bf16.hip (64-deep).
+
+struct GemmPlan {
+    int bm, bn;               // block tile
+    int grid_x, grid_z;       // output tiles, batch
+};
+
+// Largest tile that still gives >= ~2 workgroups per CU (256 CUs); N tile from N.  The fp32 engine has a 128 x 32 tile for N <= 32
+// and keeps 64 x 128 for a small wide problem; the bf16 engine sends small problems (level-0 attention GEMMs) to 64 x 64.
+inline void gemm_tile_plan(int engine, int M, int N, int batch, GemmPlan* p) {
+    auto blocks = [&](int bm, int bn) { return (long)((M + bm - 1) / bm) * ((N + bn - 1) / bn) * batch; };
+    int bm, bn;
+    if (N > 64) {
+        if (M > 64 && blocks(128, 128) >= 512) { bm = 128; bn = 128; }
+        else if (engine == 0 || blocks(64, 128) >= 512) { bm = 64; bn = 128; }
+        else { bm = 64; bn = 64; }
+    } else if (N > 32 || engine == 1) {
+        if (M > 64 && blocks(128, 64) >= 512) { bm = 128; bn = 64; }
+        else { bm = 64; bn = 64; }
+    } else {
+        bm = 128; bn = 32;
+    }
+    p->bm = bm; p->bn = bn;
+    p->grid_x = ((M + bm - 1) / bm) * ((N + bn - 1) / bn);
+    p->grid_z = batch;
+}
+
+// batched GEMM (hupr_gemm_f32 / hupr_gemm_bf16): C = op(A) op(B), (ta, tb) in {(0, 1), (0, 0), (1, 0)}
+inline int gemm_plan(const char* who, int engine, int ta, int tb, int M, int N, int K, int batch, GemmPlan* p) {
+    HUPR_REQUIRE(M > 0 && N > 0 && K > 0 && batch > 0, "%s: bad shape %d %d %d x%d", who, M, N, K, batch);
+    HUPR_REQUIRE(batch <= 65535, "%s: batch %d > 65535", who, batch);
+    HUPR_REQUIRE((ta == 0 && (tb == 0 || tb == 1)) || (ta == 1 && tb == 0), "%s: unsupported transpose combination %d %d", who, ta, tb);
+    gemm_tile_plan(engine, M, N, batch, p);
+    return HUPR_OK;
+}
+
+// forward convolution / input gradient (A_CONV x B_NK): M = output voxels, N = Co.  flags: GEMM_A_BF16 / GEMM_C_BF16 (bf16 engine)
+inline int conv_fwd_plan(const char* who, int engine, int Bn, const ConvGeom& g, int Co, int flags, int accumulate, bool has_res,
+                         GemmPlan* p) {
+    int rc = check_geom(who, Bn, g, Co, engine == 0 ? 32 : 8);
+    if (rc) return rc;
+    HUPR_REQUIRE(g.Do == g.Di + 2 * g.pd - g.kd + 1 && g.Ho == g.Hi + 2 * g.ph - g.kh + 1 && g.Wo == g.Wi + 2 * g.pw - g.kw + 1,
+                 "%s: output extent does not match stride-1 convolution", who);
+    HUPR_REQUIRE(!(flags & GEMM_C_BF16) || (!accumulate && !has_res), "%s: bf16 output excludes accumulate/residual", who);
+    const long M = (long)Bn * g.Do * g.Ho * g.Wo;
+    HUPR_REQUIRE(M < (1L << 31), "%s: too many output voxels", who);
+    gemm_tile_plan(engine, (int)M, Co, 1, p);
+    return HUPR_OK;
+}
+
+enum SplitkKernel { SPLITK_SCALAR = 0, SPLITK_REDUCE4_4 = 1, SPLITK_REDUCE4_16 = 2, SPLITK_REDUCE_T_4_8 = 3 };
+struct SplitkPlan {
+    int kernel;               // SplitkKernel
+    int grid;
+};
+// the reduce kernel of launch_splitk_reduce (gemm_f32.hip) and its workgroups, under hupr_debug_splitk_slices as set.  n_one: the
+// elements of ONE gradient (n, or n_first where two gradients share the tensor); part_aligned: the partials start on 16 bytes
+SplitkPlan splitk_reduce_plan(long n, long n_one, int splits, long split_stride, int taps, int ci, bool part_aligned, bool rows_ok);
+
+struct WgradPlan {
+    int bm, grid_x;           // 64 x 128 or 128 x 128 tiles over (Co, taps * Ci)
+    int splits;               // K slices = partial tensors (grid.y), after the caps and the workspace-shrink loop
+    size_t ws_need;           // bytes of workspace the launch writes
+    SplitkPlan red;
+};
+// weight gradient (A_KM x B_CONVK): M = Co, N = taps * Ci, K = output voxels, sliced so the grid fills the chip.  Returns
+// HUPR_ERR_WORKSPACE (with ws_need = one partial tensor) where even one slice does not fit.
+inline int wgrad_plan(const char* who, int engine, int Bn, const ConvGeom& g, int Co, int x_bf16, size_t ws_bytes, bool ws_aligned,
+                      WgradPlan* p) {
+    int rc = check_geom(who, Bn, g, Co, engine == 0 ? 32 : 4);
+    if (rc) return rc;
+    const long Mv = (long)Bn * g.Do * g.Ho * g.Wo;
+    HUPR_REQUIRE(Mv < (1L << 31), "%s: too many output voxels", who);
+    const int taps = g.kd * g.kh * g.kw, N = taps * g.Ci, bk = engine == 0 ? 32 : 64;
+    p->bm = (Co <= 64) ? 64 : 128;
+    // 128-wide n tiles (spanning taps when Ci < 128); slice the voxel axis so the grid fills the chip
+    p->grid_x = ((Co + p->bm - 1) / p->bm) * ((N + 127) / 128);
+    const long tiles = p->grid_x;
+    const int ktiles = (int)((Mv + bk - 1) / bk);
+    const long stride = (long)Co * N;
+    const size_t one = (size_t)stride * sizeof(float);
+    const size_t in_bytes = engine == 0 ? 0 : (size_t)Mv * ((size_t)Co * sizeof(float) + (size_t)taps * g.Ci * (x_bf16 ? 2 : 4));
+    int splits = wgrad_splits(tiles, ktiles, one, in_bytes);
+    while (splits > 1 && (size_t)splits * one > ws_bytes) splits >>= 1;
+    p->splits = splits;
+    p->ws_need = (size_t)splits * one;
+    if (ws_bytes < p->ws_need) return fail(HUPR_ERR_WORKSPACE, "%s: workspace %zu < %zu", who, ws_bytes, p->ws_need);
+    p->red = splitk_reduce_plan(stride, stride, splits, stride, taps, g.Ci, ws_aligned, true);
+    return HUPR_OK;
+}
+
 }  // namespace hupr

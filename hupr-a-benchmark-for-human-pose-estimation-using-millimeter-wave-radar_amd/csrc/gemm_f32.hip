@@ -379,25 +379,18 @@ __global__ void hupr_k_pack_weights(const float* __restrict__ w, float* __restri
 // host-side dispatch
 // ------------------------------------------------------------------------------------------
 template <int BM, int BN, int WM, int WN, int AM, int BMD>
-static void launch(const GemmArgs& a, int batch, hipStream_t s) {
-    const int mt = (a.M + BM - 1) / BM, nt = (a.N + BN - 1) / BN;
-    dim3 grid(mt * nt, a.ksplit, batch);
+static void launch(const GemmArgs& a, int grid_x, int batch, hipStream_t s) {
+    dim3 grid(grid_x, a.ksplit, batch);
     HUPR_LAUNCH((hupr_k_gemm_f32<BM, BN, WM, WN, AM, BMD>), grid, dim3(256), 0, s, a);
 }
 
 template <int AM, int BMD>
-static void dispatch_tiles(const GemmArgs& a, int batch, hipStream_t s) {
-    // largest tile that still gives >= ~2 workgroups per CU (256 CUs); N tile from N
-    auto blocks = [&](int bm, int bn) { return (long)((a.M + bm - 1) / bm) * ((a.N + bn - 1) / bn) * batch; };
-    if (a.N > 64) {
-        if (a.M > 64 && blocks(128, 128) >= 512) launch<128, 128, 2, 2, AM, BMD>(a, batch, s);
-        else launch<64, 128, 1, 4, AM, BMD>(a, batch, s);
-    } else if (a.N > 32) {
-        if (a.M > 64 && blocks(128, 64) >= 512) launch<128, 64, 2, 2, AM, BMD>(a, batch, s);
-        else launch<64, 64, 2, 2, AM, BMD>(a, batch, s);
-    } else {
-        launch<128, 32, 4, 1, AM, BMD>(a, batch, s);
-    }
+static void dispatch_tiles(const GemmArgs& a, const GemmPlan& p, hipStream_t s) {
+    if (p.bm == 128 && p.bn == 128) launch<128, 128, 2, 2, AM, BMD>(a, p.grid_x, p.grid_z, s);
+    else if (p.bm == 64 && p.bn == 128) launch<64, 128, 1, 4, AM, BMD>(a, p.grid_x, p.grid_z, s);
+    else if (p.bm == 128 && p.bn == 64) launch<128, 64, 2, 2, AM, BMD>(a, p.grid_x, p.grid_z, s);
+    else if (p.bm == 64 && p.bn == 64) launch<64, 64, 2, 2, AM, BMD>(a, p.grid_x, p.grid_z, s);
+    else launch<128, 32, 4, 1, AM, BMD>(a, p.grid_x, p.grid_z, s);
 }
 
 // Four outputs per thread (16-byte loads), the split axis cut into S slices per workgroup (256 / S columns of four outputs each) and
@@ -518,17 +511,12 @@ __global__ __launch_bounds__(256) void hupr_k_splitk_reduce_t(const float* __res
 static int g_splitk_slices = 0;      // test aid (hupr_debug_splitk_slices): 0 auto, 4 / 16 forced; + 256: the scattered-store kernel of rounds 1-5
 extern "C" void hupr_debug_splitk_slices(int s) { g_splitk_slices = s; }
 
-void launch_splitk_reduce(const float* part, float* out, long n, int splits, long split_stride, int taps, int ci,
-                          hipStream_t s, float* out2, long n_first) {
-    if (out2 != nullptr && !(n % 4 == 0 && ci % 4 == 0 && split_stride % 4 == 0 && n_first % 4 == 0 && (reinterpret_cast<uintptr_t>(part) & 15) == 0)) {
-        launch_splitk_reduce(part, out, n_first, splits, split_stride, taps, ci, s, nullptr, 0);         // two plain reductions
-        launch_splitk_reduce(part + n_first, out2, n - n_first, splits, split_stride, taps, ci, s, nullptr, 0);
-        return;
-    }
-    if (n % 4 == 0 && ci % 4 == 0 && split_stride % 4 == 0 && (reinterpret_cast<uintptr_t>(part) & 15) == 0) {
+SplitkPlan splitk_reduce_plan(long n, long n_one, int splits, long split_stride, int taps, int ci, bool part_aligned, bool rows_ok) {
+    SplitkPlan p;
+    if (n % 4 == 0 && ci % 4 == 0 && split_stride % 4 == 0 && part_aligned) {
         const long n4 = n / 4;
         // many partial tensors over a small output: 16 slices (a quarter of the columns per workgroup, four times the workgroups)
-        const long n4_one = out2 ? n_first / 4 : n4;          // (two gradients in one tensor: the choice each of them gets alone)
+        const long n4_one = n_one / 4;                        // (two gradients in one tensor: the choice each of them gets alone)
         const int forced = g_splitk_slices & 255;
         const bool s16 = forced ? forced == 16 : (splits >= 32 && n4_one <= (1L << 17));
         // convolution weight gradients ([co][tap][ci] partials) of the 4-slice class — the large gradients with few partial tensors
@@ -537,17 +525,41 @@ void launch_splitk_reduce(const float* part, float* out, long n, int splits, lon
         // sequential rounds of (element, slice) pairs there; measured 274 vs 208 us per step, profiles/r06_splitk_ab.txt.)
         constexpr int cb = 32;
         if (!s16 && taps > 1 && taps <= 27 && ci % cb == 0 && !(g_splitk_slices & 256) && (n / ((long)taps * ci)) * ((long)taps * ci) == n &&
-            (out2 == nullptr || n_first % ((long)taps * ci) == 0)) {
-            const int rows = (int)(n / ((long)taps * ci)), nb = ci / cb;
-            HUPR_LAUNCH((hupr_k_splitk_reduce_t<4, 8>), dim3(rows * nb), dim3(256), 0, s, part, out, splits, split_stride, taps, ci, nb, out2, n_first);
-            return;
+            rows_ok) {
+            p.kernel = SPLITK_REDUCE_T_4_8;
+            p.grid = (int)(n / ((long)taps * ci)) * (ci / cb);
+        } else if (s16) {
+            p.kernel = SPLITK_REDUCE4_16;
+            p.grid = (int)((n4 + 15) / 16);
+        } else {
+            p.kernel = SPLITK_REDUCE4_4;
+            p.grid = (int)((n4 + 63) / 64);
         }
-        if (s16) HUPR_LAUNCH(hupr_k_splitk_reduce4<16>, dim3((n4 + 15) / 16), dim3(256), 0, s, part, out, n4, splits, split_stride, taps, ci, out2, n_first);
-        else HUPR_LAUNCH(hupr_k_splitk_reduce4<4>, dim3((n4 + 63) / 64), dim3(256), 0, s, part, out, n4, splits, split_stride, taps, ci, out2, n_first);
+        return p;
+    }
+    p.kernel = SPLITK_SCALAR;
+    p.grid = (int)((n + 255) / 256);
+    return p;
+}
+
+void launch_splitk_reduce(const float* part, float* out, long n, int splits, long split_stride, int taps, int ci,
+                          hipStream_t s, float* out2, long n_first) {
+    if (out2 != nullptr && !(n % 4 == 0 && ci % 4 == 0 && split_stride % 4 == 0 && n_first % 4 == 0 && (reinterpret_cast<uintptr_t>(part) & 15) == 0)) {
+        launch_splitk_reduce(part, out, n_first, splits, split_stride, taps, ci, s, nullptr, 0);         // two plain reductions
+        launch_splitk_reduce(part + n_first, out2, n - n_first, splits, split_stride, taps, ci, s, nullptr, 0);
         return;
     }
-    HUPR_LAUNCH(hupr_k_splitk_reduce, dim3((n + 255) / 256), dim3(256), 0, s, part, out, n, splits, split_stride,
-                       taps, ci);
+    const SplitkPlan p = splitk_reduce_plan(n, out2 ? n_first : n, splits, split_stride, taps, ci, (reinterpret_cast<uintptr_t>(part) & 15) == 0,
+                                            out2 == nullptr || n_first % ((long)taps * ci) == 0);
+    const long n4 = n / 4;
+    if (p.kernel == SPLITK_REDUCE_T_4_8)
+        HUPR_LAUNCH((hupr_k_splitk_reduce_t<4, 8>), dim3(p.grid), dim3(256), 0, s, part, out, splits, split_stride, taps, ci, ci / 32, out2, n_first);
+    else if (p.kernel == SPLITK_REDUCE4_16)
+        HUPR_LAUNCH(hupr_k_splitk_reduce4<16>, dim3(p.grid), dim3(256), 0, s, part, out, n4, splits, split_stride, taps, ci, out2, n_first);
+    else if (p.kernel == SPLITK_REDUCE4_4)
+        HUPR_LAUNCH(hupr_k_splitk_reduce4<4>, dim3(p.grid), dim3(256), 0, s, part, out, n4, splits, split_stride, taps, ci, out2, n_first);
+    else
+        HUPR_LAUNCH(hupr_k_splitk_reduce, dim3(p.grid), dim3(256), 0, s, part, out, n, splits, split_stride, taps, ci);
 }
 
 }  // namespace hupr
@@ -561,8 +573,9 @@ extern "C" int hupr_gemm_f32(int ta, int tb, const float* A, const float* B, flo
                              long c_bs, const float* res, long res_ld, long res_bs, int accumulate,
                              hupr_stream_t stream) {
     HUPR_REQUIRE(A && B && C, "hupr_gemm_f32: null pointer");
-    HUPR_REQUIRE(M > 0 && N > 0 && K > 0 && batch > 0, "hupr_gemm_f32: bad shape %d %d %d x%d", M, N, K, batch);
-    HUPR_REQUIRE(batch <= 65535, "hupr_gemm_f32: batch %d > 65535", batch);
+    GemmPlan p;
+    int rc = gemm_plan("hupr_gemm_f32", 0, ta, tb, M, N, K, batch, &p);
+    if (rc) return rc;
     GemmArgs a;
     fill_common(a);
     a.A = A; a.B = B; a.C = C; a.M = M; a.N = N; a.K = K;
@@ -571,10 +584,9 @@ extern "C" int hupr_gemm_f32(int ta, int tb, const float* A, const float* B, flo
     a.res = res; a.res_ld = res_ld; a.res_bs0 = res_bs;
     a.accumulate = accumulate;
     hipStream_t s = as_stream(stream);
-    if (ta == 0 && tb == 1) dispatch_tiles<A_ROWK, B_NK>(a, batch, s);        // C = A B^T
-    else if (ta == 0 && tb == 0) dispatch_tiles<A_ROWK, B_KN>(a, batch, s);   // C = A B
-    else if (ta == 1 && tb == 0) dispatch_tiles<A_KM, B_KN>(a, batch, s);     // C = A^T B
-    else return fail(HUPR_ERR_ARG, "hupr_gemm_f32: unsupported transpose combination %d %d", ta, tb);
+    if (ta == 0 && tb == 1) dispatch_tiles<A_ROWK, B_NK>(a, p, s);        // C = A B^T
+    else if (ta == 0 && tb == 0) dispatch_tiles<A_ROWK, B_KN>(a, p, s);   // C = A B
+    else dispatch_tiles<A_KM, B_KN>(a, p, s);                             // C = A^T B
     HUPR_LAUNCH_OK("hupr_k_gemm_f32");
     return HUPR_OK;
 }
@@ -589,18 +601,16 @@ extern "C" int hupr_conv_fwd_f32(const float* x, const float* wp, const float* b
     GemmArgs a;
     fill_common(a);
     a.g = ConvGeom{Di, Hi, Wi, Ci, in_ld, Do, Ho, Wo, kd, kh, kw, pd, ph, pw};
-    int rc = check_geom("hupr_conv_fwd_f32", Bn, a.g, Co, 32);
+    GemmPlan p;
+    int rc = conv_fwd_plan("hupr_conv_fwd_f32", 0, Bn, a.g, Co, 0, accumulate, res != nullptr, &p);
     if (rc) return rc;
-    HUPR_REQUIRE(Do == Di + 2 * pd - kd + 1 && Ho == Hi + 2 * ph - kh + 1 && Wo == Wi + 2 * pw - kw + 1,
-                 "hupr_conv_fwd_f32: output extent does not match stride-1 convolution");
     const long M = (long)Bn * Do * Ho * Wo;
-    HUPR_REQUIRE(M < (1L << 31), "hupr_conv_fwd_f32: too many output voxels");
     a.A = x; a.B = wp; a.C = y;
     a.M = (int)M; a.N = Co; a.K = kd * kh * kw * Ci;
     a.lda = 0; a.ldb = a.K; a.ldc = out_ld;
     a.bias = bias; a.res = res; a.res_ld = res_ld;
     a.accumulate = accumulate;
-    dispatch_tiles<A_CONV, B_NK>(a, 1, as_stream(stream));
+    dispatch_tiles<A_CONV, B_NK>(a, p, as_stream(stream));
     HUPR_LAUNCH_OK("hupr_k_gemm_f32<conv>");
     return HUPR_OK;
 }
@@ -624,32 +634,52 @@ extern "C" int hupr_conv_wgrad_f32(const float* x, const float* dy, float* dw, i
     GemmArgs a;
     fill_common(a);
     a.g = ConvGeom{Di, Hi, Wi, Ci, in_ld, Do, Ho, Wo, kd, kh, kw, pd, ph, pw};
-    int rc = check_geom("hupr_conv_wgrad_f32", Bn, a.g, Co, 32);
+    WgradPlan p;
+    int rc = wgrad_plan("hupr_conv_wgrad_f32", 0, Bn, a.g, Co, 0, ws_bytes, (reinterpret_cast<uintptr_t>(ws) & 15) == 0, &p);
     if (rc) return rc;
     const long Mv = (long)Bn * Do * Ho * Wo;
-    HUPR_REQUIRE(Mv < (1L << 31), "hupr_conv_wgrad_f32: too many output voxels");
     const int taps = kd * kh * kw;
     a.A = dy; a.B = x; a.C = reinterpret_cast<float*>(ws);
     a.M = Co; a.N = taps * Ci; a.K = (int)Mv;
     a.lda = dy_ld; a.ldb = 0; a.ldc = a.N;
-    // 128-wide n tiles (spanning taps when Ci < 128); slice the voxel axis so the grid fills the chip
-    const int bn = 128;
-    const int bm = (Co <= 64) ? 64 : 128;
-    const long tiles = (long)((Co + bm - 1) / bm) * ((a.N + bn - 1) / bn);
-    const int ktiles = (int)((Mv + BK - 1) / BK);
     a.split_stride = (long)a.M * a.N;
-    int splits = wgrad_splits(tiles, ktiles, (size_t)a.split_stride * sizeof(float));
-    while (splits > 1 && (size_t)splits * a.split_stride * sizeof(float) > ws_bytes) splits >>= 1;
-    a.ksplit = splits;
-    if (ws_bytes < (size_t)splits * a.split_stride * sizeof(float))
-        return fail(HUPR_ERR_WORKSPACE, "hupr_conv_wgrad_f32: workspace %zu < %zu", ws_bytes,
-                    (size_t)splits * a.split_stride * sizeof(float));
+    a.ksplit = p.splits;
     hipStream_t s = as_stream(stream);
-    if (bm == 64) launch<64, 128, 1, 4, A_KM, B_CONVK>(a, 1, s);
-    else launch<128, 128, 2, 2, A_KM, B_CONVK>(a, 1, s);
+    if (p.bm == 64) launch<64, 128, 1, 4, A_KM, B_CONVK>(a, p.grid_x, 1, s);
+    else launch<128, 128, 2, 2, A_KM, B_CONVK>(a, p.grid_x, 1, s);
     HUPR_LAUNCH_OK("hupr_k_gemm_f32<wgrad>");
-    launch_splitk_reduce(reinterpret_cast<const float*>(ws), dw, a.split_stride, splits, a.split_stride, taps, Ci, s);
+    launch_splitk_reduce(reinterpret_cast<const float*>(ws), dw, a.split_stride, p.splits, a.split_stride, taps, Ci, s);
     HUPR_LAUNCH_OK("hupr_k_splitk_reduce");
+    return HUPR_OK;
+}
+
+// test aid (include/hupr_debug.h): the plans above, nothing launched
+extern "C" int hupr_debug_gemm_route(int engine, int op, const int* v, size_t ws_bytes, int ws_misalign, int* out) {
+    HUPR_REQUIRE((engine == 0 || engine == 1) && op >= 0 && op <= 2 && v && out, "hupr_debug_gemm_route: bad engine %d / op %d / null", engine, op);
+    const char* who = "hupr_debug_gemm_route";
+    if (op == 0) {
+        GemmPlan p;
+        int rc = gemm_plan(who, engine, v[0], v[1], v[2], v[3], v[4], v[5], &p);
+        if (rc) return rc;
+        out[0] = p.bm; out[1] = p.bn; out[2] = p.grid_x; out[3] = p.grid_z;
+        return HUPR_OK;
+    }
+    const ConvGeom g{v[1], v[2], v[3], v[4], v[5], v[6], v[7], v[8], v[10], v[11], v[12], v[13], v[14], v[15]};
+    if (op == 1) {
+        GemmPlan p;
+        HUPR_REQUIRE(engine == 1 || (!v[16] && !v[17]), "%s: bf16 storage on the fp32 engine", who);
+        int rc = conv_fwd_plan(who, engine, v[0], g, v[9], (v[16] ? GEMM_A_BF16 : 0) | (v[17] ? GEMM_C_BF16 : 0), v[18], v[19] != 0, &p);
+        if (rc) return rc;
+        out[0] = p.bm; out[1] = p.bn; out[2] = p.grid_x; out[3] = p.grid_z;
+        return HUPR_OK;
+    }
+    WgradPlan p;
+    p.ws_need = 0;
+    HUPR_REQUIRE(engine == 1 || !v[16], "%s: bf16 storage on the fp32 engine", who);
+    int rc = wgrad_plan(who, engine, v[0], g, v[9], v[16], ws_bytes, (ws_misalign & 15) == 0, &p);
+    out[5] = (int)p.ws_need;
+    if (rc) return rc;
+    out[0] = p.bm; out[1] = p.grid_x; out[2] = p.splits; out[3] = p.red.kernel; out[4] = p.red.grid;
     return HUPR_OK;
 }
 

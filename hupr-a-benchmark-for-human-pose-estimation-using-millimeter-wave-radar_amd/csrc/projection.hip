@@ -206,43 +206,62 @@ using namespace hupr;
 // 1 where hupr_mscsa_proj_fwd_bf16 applies: C in {64, 128} (levels 1 and 2; the 8 192 rows of level 3 stay on the engine), at least
 // one 16-row group
 extern "C" int hupr_mscsa_proj_supported(long M, int C) { return (M >= 16 && (C == 64 || C == 128)) ? 1 : 0; }
+// the input gradient: level 1 only (C = 64): at C = 128 the transposed 128 KB weight block costs more than the engine's whole launch (34.6 vs 20.7 us measured)
+extern "C" int hupr_mscsa_proj_dgrad_supported(long M, int C) { return (M >= 16 && C == 64) ? 1 : 0; }
+
+// The launch decision of the two projection kernels, made once for the launchers and for hupr_debug_mscsa_proj_grid: the shape check
+// and (threads per workgroup, row groups, column blocks of 256 output channels).  op 0: forward, op 1: input gradient.  A row group is
+// one step of a workgroup's persistent loop (16 rows per wave); at most 256 of them, one (C = 64) or two (C = 128) workgroups per CU.
+struct ProjPlan {
+    int threads, row_groups, col_blocks;
+};
+static int proj_plan(const char* who, int op, long M, int C, ProjPlan* p) {
+    HUPR_REQUIRE(op == 0 || op == 1, "%s: bad op %d", who, op);
+    HUPR_REQUIRE(op == 0 ? hupr_mscsa_proj_supported(M, C) : hupr_mscsa_proj_dgrad_supported(M, C), "%s: unsupported shape M=%ld C=%d", who, M, C);
+    p->threads = (op == 0 && C == 64) ? 1024 : 512;               // forward at C = 64: one 1024-thread workgroup per CU (16 waves x 16 rows per step)
+    const long rows = p->threads / 64 * 16;
+    const long groups = (M + rows - 1) / rows;
+    p->row_groups = (int)(groups < 256 ? groups : 256);
+    p->col_blocks = op == 0 ? 4 * C / 256 : 1;
+    return HUPR_OK;
+}
+extern "C" int hupr_debug_mscsa_proj_grid(int op, long M, int C, int* out) {
+    HUPR_REQUIRE(out, "hupr_debug_mscsa_proj_grid: null pointer");
+    ProjPlan p;
+    int rc = proj_plan("hupr_debug_mscsa_proj_grid", op, M, C, &p);
+    if (rc) return rc;
+    out[0] = p.threads; out[1] = p.row_groups; out[2] = p.col_blocks;
+    return HUPR_OK;
+}
 
 // Y (M, 4 C) bf16 = X (M, C) fp32 . Wc^T, Wc (4 C, C) fp32: the four 1 x 1 projections of one map of an MSCSA level
 // (reference models/layers.py:150-157) as one product; rows = the B H W pixels of the map, channels-last.
 extern "C" int hupr_mscsa_proj_fwd_bf16(const float* X, const float* Wc, void* Y, long M, int C, hupr_stream_t stream) {
     HUPR_REQUIRE(X && Wc && Y, "hupr_mscsa_proj_fwd_bf16: null pointer");
-    HUPR_REQUIRE(hupr_mscsa_proj_supported(M, C), "hupr_mscsa_proj_fwd_bf16: unsupported shape M=%ld C=%d", M, C);
+    ProjPlan p;
+    int rc = proj_plan("hupr_mscsa_proj_fwd_bf16", 0, M, C, &p);
+    if (rc) return rc;
     HUPR_REQUIRE(((uintptr_t)X & 15) == 0 && ((uintptr_t)Wc & 15) == 0 && ((uintptr_t)Y & 15) == 0, "hupr_mscsa_proj_fwd_bf16: misaligned buffer");
-    const int nb = 4 * C / 256;                                   // column blocks of 256 output channels
     hipStream_t s = as_stream(stream);
     __bf16* y = static_cast<__bf16*>(Y);
-    if (C == 64) {                                                // one 1024-thread workgroup per CU (16 waves x 16 rows per step)
-        const long groups = (M + 255) / 256;
-        const int nrg = (int)(groups < 256 ? groups : 256);
-        HUPR_LAUNCH((hupr_k_mscsa_proj_fwd<64, 1024>), dim3((unsigned)(nb * nrg)), dim3(1024), 0, s, X, Wc, y, M, nrg);
-    } else {                                                      // two column blocks: two 512-thread workgroups per CU
-        const long groups = (M + 127) / 128;
-        const int nrg = (int)(groups < 256 ? groups : 256);
-        HUPR_LAUNCH((hupr_k_mscsa_proj_fwd<128, 512>), dim3((unsigned)(nb * nrg)), dim3(512), 0, s, X, Wc, y, M, nrg);
-    }
+    const dim3 grid((unsigned)(p.col_blocks * p.row_groups));
+    if (C == 64) HUPR_LAUNCH((hupr_k_mscsa_proj_fwd<64, 1024>), grid, dim3(1024), 0, s, X, Wc, y, M, p.row_groups);
+    else HUPR_LAUNCH((hupr_k_mscsa_proj_fwd<128, 512>), grid, dim3(512), 0, s, X, Wc, y, M, p.row_groups);      // two column blocks: two 512-thread workgroups per CU
     HUPR_LAUNCH_OK("hupr_k_mscsa_proj_fwd");
     return HUPR_OK;
 }
-
-// level 1 only (C = 64): at C = 128 the transposed 128 KB weight block costs more than the engine's whole launch (34.6 vs 20.7 us measured)
-extern "C" int hupr_mscsa_proj_dgrad_supported(long M, int C) { return (M >= 16 && C == 64) ? 1 : 0; }
 
 // dX (M, C) fp32 = dY (M, 4 C) fp32 . Wc (+ res (M, C) fp32 or null): the input gradient of the four projections of one map, the value
 // gradient dV of the map's attentions as its residual term (functional.MSCSALevelFn.backward).  res may alias nothing it writes.
 extern "C" int hupr_mscsa_proj_dgrad_f32(const float* dY, const float* Wc, const float* res, float* dX, long M, int C, hupr_stream_t stream) {
     HUPR_REQUIRE(dY && Wc && dX, "hupr_mscsa_proj_dgrad_f32: null pointer");
-    HUPR_REQUIRE(hupr_mscsa_proj_dgrad_supported(M, C), "hupr_mscsa_proj_dgrad_f32: unsupported shape M=%ld C=%d", M, C);
+    ProjPlan p;
+    int rc = proj_plan("hupr_mscsa_proj_dgrad_f32", 1, M, C, &p);
+    if (rc) return rc;
     HUPR_REQUIRE(((uintptr_t)dY & 15) == 0 && ((uintptr_t)Wc & 15) == 0 && ((uintptr_t)dX & 15) == 0 && ((uintptr_t)res & 15) == 0,
                  "hupr_mscsa_proj_dgrad_f32: misaligned buffer");
-    hipStream_t s = as_stream(stream);
-    const long groups = (M + 127) / 128;                          // 512-thread workgroups: 8 waves x 16 rows per step, one per CU
-    const int nrg = (int)(groups < 256 ? groups : 256);
-    HUPR_LAUNCH((hupr_k_mscsa_proj_dgrad<64, 512>), dim3((unsigned)nrg), dim3(512), 0, s, dY, Wc, res, dX, M, nrg);
+    hipStream_t s = as_stream(stream);      // 512-thread workgroups: 8 waves x 16 rows per step, one per CU
+    HUPR_LAUNCH((hupr_k_mscsa_proj_dgrad<64, 512>), dim3((unsigned)p.row_groups), dim3(512), 0, s, dY, Wc, res, dX, M, p.row_groups);
     HUPR_LAUNCH_OK("hupr_k_mscsa_proj_dgrad");
     return HUPR_OK;
 }

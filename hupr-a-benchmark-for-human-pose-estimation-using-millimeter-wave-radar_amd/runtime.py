@@ -107,6 +107,8 @@ SIGNATURES = {
     "hupr_debug_wgrad_route": (c_int, [c_int] * 11 + [c_size_t, ctypes.POINTER(c_int)]),
     "hupr_debug_interp_route": (c_int, [c_int] * 12 + [ctypes.POINTER(c_int)]),
     "hupr_debug_mnet_grid": (c_int, [c_int, c_long, c_int]),
+    "hupr_debug_gemm_route": (c_int, [c_int, c_int, ctypes.POINTER(c_int), c_size_t, c_int, ctypes.POINTER(c_int)]),
+    "hupr_debug_mscsa_proj_grid": (c_int, [c_int, c_long, c_int, ctypes.POINTER(c_int)]),
     "hupr_conv3x3_halo_supported": (c_int, [c_int] * 10),
     "hupr_conv3x3_halo_bf16": (c_int, [c_void_p] * 5 + [c_int] * 10 + [c_void_p]),
     "hupr_conv3x3_wgrad_halo_ws_bytes": (c_size_t, [c_int, c_int, c_int]),

@@ -44,6 +44,20 @@ int hupr_debug_interp_route(int op, int bf16, int Bn, int Di, int Hi, int Wi, in
 int hupr_debug_mnet_grid(int op, long n_bg, int pixels);
     /* test aid: the workgroups of hupr_mnet_fwd_* (op 0), hupr_mnet_fwd_means_* (op 1) or hupr_mnet_bwd_* (op 2) on n_bg x pixels, from the
      * function the launchers themselves use; HUPR_ERR_ARG for another op or an empty extent.  Nothing is launched. */
+int hupr_debug_gemm_route(int engine, int op, const int* v, size_t ws_bytes, int ws_misalign, int* out);
+    /* test aid: the launch the GEMM engines (engine 0: csrc/gemm_f32.hip, 1: csrc/gemm_bf16.hip) would make, from the plans the launchers
+     * themselves use (csrc/gemm_common.h); nothing is launched, the pointers of a call aside every check of the entry point is made.
+     * op 0, hupr_gemm_*: v = {ta, tb, M, N, K, batch} (hupr_tmerge_dgrad_bf16: {0, 1, HW, Ci, Co, Bn G}); out = {BM, BN, grid.x, grid.z}.
+     * op 1, hupr_conv_fwd_* : v = {Bn, Di, Hi, Wi, Ci, in_ld, Do, Ho, Wo, Co, kd, kh, kw, pd, ph, pw, x_bf16, y_bf16, accumulate, residual
+     * given}; out as for op 0.  op 2, hupr_conv_wgrad_*: v = the same first 16 and x_bf16, with a workspace of ws_bytes whose address
+     * is ws_misalign modulo 16; out = {BM, grid.x, K slices (partial tensors), reduce kernel, its workgroups, workspace bytes written}
+     * — reduce kernel 0 hupr_k_splitk_reduce, 1 hupr_k_splitk_reduce4<4>, 2 hupr_k_splitk_reduce4<16>, 3 hupr_k_splitk_reduce_t<4, 8>,
+     * under hupr_debug_splitk_slices as set.  Returns 0, or HUPR_ERR_ARG / HUPR_ERR_WORKSPACE where the call is refused (out[5] is then
+     * one partial tensor's bytes, or 0). */
+int hupr_debug_mscsa_proj_grid(int op, long M, int C, int* out);
+    /* test aid: out = {threads per workgroup, row groups, column blocks} of hupr_mscsa_proj_fwd_bf16 (op 0) or hupr_mscsa_proj_dgrad_f32
+     * (op 1) on M rows of C channels, from the plan the launchers themselves use (grid = row groups x column blocks); HUPR_ERR_ARG where
+     * the call is refused.  Nothing is launched. */
 #ifdef __cplusplus
 }
 #endif

@@ -32,7 +32,7 @@ def test_operator_header_holds_no_debug_entry_points():
     """include/hupr.h is the operator contract only; test / profiling switches live in include/hupr_debug.h."""
     assert not [n for n in _declared(("hupr.h",)) if n.startswith("hupr_debug_")]
     dbg = _declared(("hupr_debug.h",))
-    assert dbg and all(n.startswith("hupr_debug_") for n in dbg) and len(dbg) <= 15      # 11 switches + 4 route answers
+    assert dbg and all(n.startswith("hupr_debug_") for n in dbg) and len(dbg) <= 17      # 11 switches + 6 route answers
 
 
 def test_every_declared_symbol_is_exported(built):
