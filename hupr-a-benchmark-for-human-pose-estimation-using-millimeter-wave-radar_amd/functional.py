@@ -2030,13 +2030,56 @@ def pose_track_state(rows, device):
     return _pose_state(rt.lib().hupr_pose_track_state_bytes, rows, device)
 
 
-def pose_track(heat, ratio, refine=True, track_state=None, tracking=None):
+MAX_CANDIDATES = 4                  # of pose_track's association and of pose_peaks
+
+
+def check_peaks(K, min_separation, peak_ratio, name="pose_peaks"):
+    """The three candidate parameters of ``pose_peaks`` and of the associating ``pose_track``, checked in ``name``'s name ->
+    (int K in 1..4, int min_separation >= 0 in heat-map pixels, float peak_ratio in (0, 1])."""
+    for what, v in (("K", K), ("min_separation", min_separation)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError("%s needs an integer %s, got %r" % (name, what, v))
+    if not 1 <= K <= MAX_CANDIDATES:
+        raise ValueError("%s needs K in 1..%d, got %r" % (name, MAX_CANDIDATES, K))
+    if not 0 <= min_separation < 2 ** 31:
+        raise ValueError("%s needs min_separation >= 0, got %r" % (name, min_separation))
+    if isinstance(peak_ratio, bool) or not isinstance(peak_ratio, (int, float, np.integer, np.floating)) or not 0 < peak_ratio <= 1:
+        raise ValueError("%s needs peak_ratio in (0, 1], got %r" % (name, peak_ratio))
+    return int(K), int(min_separation), float(peak_ratio)
+
+
+def _pose_candidates(lead, K, device):
+    """The four candidate outputs for ``lead`` rows of K slots: positions, scores, indices, counts."""
+    return (torch.empty(lead + (K, 2), dtype=torch.float32, device=device), torch.empty(lead + (K,), dtype=torch.float32, device=device),
+            torch.empty(lead + (K,), dtype=torch.int32, device=device), torch.empty(lead, dtype=torch.int32, device=device))
+
+
+def pose_peaks(heat, ratio, K, min_separation=3, peak_ratio=0.25, refine=True):
+    """heat (..., H, W) fp32 GPU -> (positions (..., K, 2) in image pixels, scores (..., K), pixel indices int32 (..., K), count int32
+    (...)): the up to ``K`` <= 4 peaks of every map that the associating tracker chooses among, in one launch and without a tracker
+    (csrc/pose_assoc.hip; the rule is stated beside hupr_pose_track_assoc_f32 in include/hupr.h).  Peak 0 is ``pose_decode``'s
+    arg-max; the others are the next 3 x 3 local maxima by value that are at least ``peak_ratio`` times as high and lie more than
+    ``min_separation`` heat-map pixels (Chebyshev) from every peak taken; slots past the count hold zeros.  Device tensors, no sync."""
+    heat, lead, rows, H, W = _pose_heat("pose_peaks", heat)
+    K, min_separation, peak_ratio = check_peaks(K, min_separation, peak_ratio)
+    xy, score, index, count = _pose_candidates(lead, K, heat.device)
+    rt.check(rt.lib().hupr_pose_peaks_f32(rt.ptr(heat), rows, H, W, float(ratio), int(bool(refine)), K, min_separation, peak_ratio,
+                                          rt.ptr(xy), rt.ptr(score), rt.ptr(index), rt.ptr(count), rt.stream()))
+    return xy, score, index, count
+
+
+def pose_track(heat, ratio, refine=True, track_state=None, tracking=None, present=None):
     """heat (..., H, W) fp32 GPU -> (idx int32 (...), maxval (...), raw keypoints (..., 2), filtered keypoints (..., 2), velocity
     (..., 2), position covariance (..., 3) = (Pxx, Pxy, Pyy), forecast (..., 2), status int32 (...)) in one launch
     (csrc/pose_track.hip; the rule is stated beside hupr_pose_track_f32 in include/hupr.h).  ``idx`` / ``maxval`` / raw keypoints are
     ``pose_decode``'s bits.  ``track_state`` (``pose_track_state``, advanced in place) and ``tracking`` (an object with ``rate_hz``,
     ``accel_psd``, ``meas_std``, ``heatmap_gain``, ``gate``, ``max_coast``, ``init_speed_std``, ``min_score``, ``horizon_s``:
-    tools.stream.PoseTracking) are both required.  One call is one frame.  Device tensors, no sync."""
+    tools.stream.PoseTracking) are both required.  One call is one frame.  Device tensors, no sync.
+    With ``tracking.candidates`` > 1, or with ``present`` (int32, the shape of ``heat`` without its last three axes: one flag per
+    group of joints, 0 = nobody there, the group has no measurement in this frame), the launch is the associating tracker's
+    (csrc/pose_assoc.hip, hupr_pose_track_assoc_f32): it reads ``tracking.candidates``, ``min_separation`` and ``peak_ratio`` too and
+    returns the eight outputs plus (candidate positions (..., K, 2), candidate scores (..., K), candidate count int32 (...), chosen
+    int32 (...), -1 where no measurement went into the state)."""
     heat, lead, rows, H, W = _pose_heat("pose_track", heat)
     if track_state is None or tracking is None:
         raise ValueError("pose_track needs its track_state and its tracking parameters")
@@ -2051,10 +2094,29 @@ def pose_track(heat, ratio, refine=True, track_state=None, tracking=None):
     raw, kp, vel, fc = (torch.empty(lead + (2,), dtype=torch.float32, device=heat.device) for _ in range(4))
     cov = torch.empty(lead + (3,), dtype=torch.float32, device=heat.device)
     status = torch.empty(lead, dtype=torch.int32, device=heat.device)
-    rt.check(rt.lib().hupr_pose_track_f32(rt.ptr(heat), rows, H, W, float(ratio), int(bool(refine)), rt.ptr(track_state), *params,
-                                          rt.ptr(idx), rt.ptr(mx), rt.ptr(raw), rt.ptr(kp), rt.ptr(vel), rt.ptr(cov), rt.ptr(fc),
-                                          rt.ptr(status), rt.stream()))
-    return idx, mx, raw, kp, vel, cov, fc, status
+    K = getattr(tracking, "candidates", 1)
+    if K == 1 and present is None:
+        rt.check(rt.lib().hupr_pose_track_f32(rt.ptr(heat), rows, H, W, float(ratio), int(bool(refine)), rt.ptr(track_state), *params,
+                                              rt.ptr(idx), rt.ptr(mx), rt.ptr(raw), rt.ptr(kp), rt.ptr(vel), rt.ptr(cov), rt.ptr(fc),
+                                              rt.ptr(status), rt.stream()))
+        return idx, mx, raw, kp, vel, cov, fc, status
+    K, sep, floor = check_peaks(K, getattr(tracking, "min_separation", 3), getattr(tracking, "peak_ratio", 0.25), "pose_track")
+    group = 1
+    if present is not None:
+        if (not isinstance(present, torch.Tensor) or present.dtype != torch.int32 or tuple(present.shape) != lead[:-1]
+                or not present.is_contiguous()):
+            raise ValueError("present must be a contiguous int32 tensor of shape %r (one flag per group of %d rows)"
+                             % (lead[:-1], lead[-1] if lead else 1))
+        if present.device != heat.device:
+            raise ValueError("present is on %s, the heat-maps on %s" % (present.device, heat.device))
+        group = lead[-1] if lead else 1
+    xy, score, _, count = _pose_candidates(lead, K, heat.device)
+    chosen = torch.empty(lead, dtype=torch.int32, device=heat.device)
+    rt.check(rt.lib().hupr_pose_track_assoc_f32(rt.ptr(heat), rows, H, W, float(ratio), int(bool(refine)), rt.ptr(track_state), *params,
+                                                K, sep, floor, rt.ptr(present), group, rt.ptr(idx), rt.ptr(mx), rt.ptr(raw),
+                                                rt.ptr(kp), rt.ptr(vel), rt.ptr(cov), rt.ptr(fc), rt.ptr(status), rt.ptr(xy),
+                                                rt.ptr(score), rt.ptr(count), rt.ptr(chosen), rt.stream()))
+    return idx, mx, raw, kp, vel, cov, fc, status, xy, score, count, chosen
 
 
 SMOOTH_SMOOTHED, SMOOTH_END, SMOOTH_PASSTHROUGH, SMOOTH_DEGENERATE = range(4)                   # pose_smooth_rts's flags

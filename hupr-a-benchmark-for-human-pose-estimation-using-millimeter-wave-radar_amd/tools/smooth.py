@@ -102,12 +102,15 @@ class TrackHistory:
 
 class SequenceSmoother:
     """A tracker (``functional.pose_track`` on a state of its own) that remembers: ``track(heat, ratio, refine)`` is one frame of
-    ``rows`` heat-maps and returns ``pose_track``'s tuple; ``new_sequence()`` zeroes the state, so that the next frame starts new
-    tracks and the smoother's chain breaks there by itself; ``smooth()`` smooths everything tracked so far in one launch."""
+    ``rows`` heat-maps and returns ``pose_track``'s tuple (with ``tracking.candidates`` > 1 the associating tracker's twelve);
+    ``new_sequence()`` zeroes the state, so that the next frame starts new tracks and the smoother's chain breaks there by itself;
+    ``smooth()`` smooths everything tracked so far in one launch."""
 
     def __init__(self, tracking, rows, device):
         if not isinstance(tracking, PoseTracking):
             raise TrackingError("tracking must be a PoseTracking, got %r" % (tracking,))
+        if tracking.gate_on_presence:
+            raise TrackingError("PoseTracking.gate_on_presence needs a live session with presence: there is no gate to ask here")
         if isinstance(rows, bool) or not isinstance(rows, (int, np.integer)) or rows < 1:
             raise ValueError("rows must be a positive integer, got %r" % (rows,))
         self.tracking, self.rows, self.device = tracking, int(rows), torch.device(device)
@@ -119,7 +122,7 @@ class SequenceSmoother:
 
     def track(self, heat, ratio, refine=True):
         out = F_.pose_track(heat, ratio, refine=refine, track_state=self.state, tracking=self.tracking)
-        _, mx, raw, kp, _, _, _, status = out
+        mx, raw, kp, status = out[1], out[2], out[3], out[7]
         self.history.append(self.state, status, kp, raw, mx)
         return out
 
@@ -184,7 +187,7 @@ def temporal_setting(cfg):
         if not hasattr(kw, "__dict__") or isinstance(kw, type):
             raise ValueError("TEST.tracking must be a mapping of PoseTracking arguments, got %r" % (kw,))
         kw = vars(kw)
-    known = tuple(k for k in PoseTracking.__slots__ if k != "rate_hz")
+    known = tuple(k for k in PoseTracking.ARGUMENTS if k != "rate_hz")
     for k in kw:
         if k not in known:
             raise ValueError("TEST.tracking.%s is no PoseTracking argument (%s; the rate is TEST.temporalRate)" % (k, ", ".join(known)))

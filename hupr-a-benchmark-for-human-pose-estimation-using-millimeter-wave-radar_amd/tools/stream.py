@@ -19,7 +19,10 @@ Decode: by default the keypoint is the arg-max pixel times imgSize / heatmapSize
 refines the peak to sub-pixel position and ``smooth=PoseSmoothing(rate_hz)`` runs a One-Euro filter over the keypoints, its state on
 the device; either replaces the two decode launches by one (csrc/pose_decode.hip), inside the captured graph like them.
 ``track=PoseTracking(rate_hz)`` runs a constant-velocity Kalman filter per joint instead (csrc/pose_track.hip, one launch likewise):
-outliers are gated, drop-outs coast on the track's velocity, every joint carries a covariance and a forecast.
+outliers are gated, drop-outs coast on the track's velocity, every joint carries a covariance and a forecast.  With
+``PoseTracking(candidates=C)``, C > 1, the track chooses its measurement among up to C peaks of the heat-map instead of taking the
+strongest (csrc/pose_assoc.hip, one launch in the tracker's place), and ``gate_on_presence=True`` takes the measurement away where the
+presence gate sees nobody.
 ``decode="integral"`` decodes the mass centroid of the window of ``decode_radius`` pixels around the peak (default: the targets' patch
 radius; 0: the whole map) — what the integral coordinate loss trains — in one launch of csrc/pose_integral.hip in place of the two,
 ``smooth`` included; it does not combine with ``track``, whose measurement is pinned to the sub-pixel decode.
@@ -27,7 +30,8 @@ radius; 0: the whole map) — what the integral coordinate loss trains — in on
     python -m hupr_amd.tools.stream --config mscsa_prgcn.yaml --dir <logs name> --raw <dir with hori/ and vert/ adc_data.bin>
                                     [--lookahead N] [--math f32|bf16] [--no-graph] [--out poses.json]
                                     [--decode argmax|subpixel|integral [--decode-radius N]] [--smooth --rate FPS]
-                                    [--track --rate FPS [--predict-now] [--accel-psd Q] [--gate D2] [--max-coast N] [--rts]]
+                                    [--track --rate FPS [--predict-now] [--accel-psd Q] [--gate D2] [--max-coast N] [--rts]
+                                     [--track-candidates N] [--track-separation N] [--track-peak-ratio X] [--track-on-presence]]
                                     [--presence [--pfa X] [--cfar-guard N] [--cfar-train N] [--min-cells N] [--confirm N] [--hold N]]
 
 ``presence=PresenceGate(...)`` / ``--presence``: scene occupancy.  A CA-CFAR detector on the centre frame's horizontal mean planes and a
@@ -133,7 +137,13 @@ class PoseSmoothing:
     __repr__ = _settings_repr
 
 
-class PoseTracking:
+class _AssociationFields:
+    """The four settings ``PoseTracking`` gained with the choice among heat-map peaks (a base class of their own, so that
+    ``PoseTracking.__slots__`` lists what it always listed; ``PoseTracking.ARGUMENTS`` lists all)."""
+    __slots__ = ("candidates", "min_separation", "peak_ratio", "gate_on_presence")
+
+
+class PoseTracking(_AssociationFields):
     """Kalman tracker settings of a session (a constant-velocity filter per joint; the rule is stated beside hupr_pose_track_f32 in
     include/hupr.h): ``rate_hz`` the frame rate of the stream; ``accel_psd`` (pixel^2 / s^3) the power of the white acceleration that
     drives the process noise; the measurement noise is ``heatmap_gain`` times the spread of the heat-map around its peak plus
@@ -141,13 +151,20 @@ class PoseTracking:
     quantile, 2 d.o.f.; the default is the 99.9 % one); ``max_coast`` the number of consecutive frames a track goes on without an
     accepted measurement before it ends; ``init_speed_std`` (pixel / s) the velocity uncertainty of a new track; a joint whose score
     is <= ``min_score`` has no measurement; ``horizon_s`` (s) how far ahead of the filtered pose the forecast looks.  The defaults
-    are guesses: good values for real captures are unmeasured."""
+    are guesses: good values for real captures are unmeasured.
+    ``candidates`` (1..4) > 1: the track chooses its measurement among that many peaks of the heat-map (csrc/pose_assoc.hip; the
+    rule is stated beside hupr_pose_track_assoc_f32): the arg-max and the next local maxima that are at least ``peak_ratio`` (in
+    (0, 1]) times as high and more than ``min_separation`` heat-map pixels from every peak taken; the one inside the gate with the
+    smallest d2 + ln det S updates the track.  ``gate_on_presence`` (a session with ``presence`` only): a lane the presence gate calls
+    empty has no measurement, its tracks coast and end.  The defaults of these three are guesses too, unmeasured on real captures;
+    ``candidates=1`` is today's tracker, and stays the default because a second candidate can be the wrong one."""
     __slots__ = ("rate_hz", "accel_psd", "meas_std", "heatmap_gain", "gate", "max_coast", "init_speed_std", "min_score", "horizon_s")
+    ARGUMENTS = __slots__ + _AssociationFields.__slots__
 
     def __init__(self, rate_hz, accel_psd=200.0, meas_std=1.0, heatmap_gain=1.0, gate=13.816, max_coast=5, init_speed_std=50.0,
-                 min_score=0.0, horizon_s=0.0):
+                 min_score=0.0, horizon_s=0.0, candidates=1, min_separation=3, peak_ratio=0.25, gate_on_presence=False):
         vals = dict(rate_hz=rate_hz, accel_psd=accel_psd, meas_std=meas_std, heatmap_gain=heatmap_gain, gate=gate,
-                    init_speed_std=init_speed_std, min_score=min_score, horizon_s=horizon_s)
+                    init_speed_std=init_speed_std, min_score=min_score, horizon_s=horizon_s, peak_ratio=peak_ratio)
         vals = {k: _finite(TrackingError, "PoseTracking." + k, v) for k, v in vals.items()}
         for k in ("rate_hz", "meas_std", "gate", "init_speed_std"):
             if not vals[k] > 0:
@@ -155,15 +172,30 @@ class PoseTracking:
         for k in ("accel_psd", "heatmap_gain", "horizon_s"):
             if vals[k] < 0:
                 raise TrackingError("PoseTracking.%s must not be negative, got %r" % (k, vals[k]))
+        if not 0 < peak_ratio <= 1:
+            raise TrackingError("PoseTracking.peak_ratio must be in (0, 1], got %r" % (peak_ratio,))
         self.max_coast = _count(TrackingError, "PoseTracking.max_coast", max_coast, 0)
+        self.candidates = _count(TrackingError, "PoseTracking.candidates", candidates, 1)
+        if self.candidates > F_.MAX_CANDIDATES:
+            raise TrackingError("PoseTracking.candidates must be an integer in 1..%d, got %r" % (F_.MAX_CANDIDATES, candidates))
+        self.min_separation = _count(TrackingError, "PoseTracking.min_separation", min_separation, 0)
+        if not isinstance(gate_on_presence, bool):
+            raise TrackingError("PoseTracking.gate_on_presence must be True or False, got %r" % (gate_on_presence,))
+        self.gate_on_presence = gate_on_presence
         for k, v in vals.items():
             setattr(self, k, float(v))
 
-    __repr__ = _settings_repr
+    def __repr__(self):
+        return "PoseTracking(%s)" % ", ".join("%s=%r" % (k, getattr(self, k)) for k in self.ARGUMENTS)
+
+    @property
+    def associates(self):
+        """Whether a session with these settings launches the associating tracker (csrc/pose_assoc.hip) instead of the plain one."""
+        return self.candidates > 1 or self.gate_on_presence
 
     def with_horizon(self, horizon_s):
         """A copy that forecasts ``horizon_s`` seconds ahead."""
-        return PoseTracking(**dict({k: getattr(self, k) for k in self.__slots__}, horizon_s=horizon_s))
+        return PoseTracking(**dict({k: getattr(self, k) for k in self.ARGUMENTS}, horizon_s=horizon_s))
 
 
 class PresenceGate:
@@ -251,11 +283,13 @@ def check_decode(decode, smooth, decode_radius=None, heatmap_size=None):
         raise DecodeError(str(e)) from None
 
 
-def check_track(track, smooth, predict_now, decode="argmax"):
+def check_track(track, smooth, predict_now, decode="argmax", presence=None):
     """The session's tracker arguments: ``track`` None or a PoseTracking, never beside ``smooth`` or ``decode="integral"``;
-    ``predict_now`` only with it."""
+    ``predict_now`` only with it; ``gate_on_presence`` only in a session with ``presence``."""
     if track is not None and not isinstance(track, PoseTracking):
         raise TrackingError("track must be a PoseTracking or None, got %r" % (track,))
+    if track is not None and track.gate_on_presence and presence is None:
+        raise TrackingError("PoseTracking.gate_on_presence needs presence: the verdict is the presence gate's")
     if track is not None and decode == "integral":
         raise TrackingError("track and decode='integral' exclude each other: the tracker's measurement is the sub-pixel decode's")
     if track is not None and smooth is not None:
@@ -370,21 +404,32 @@ class PoseFrame(_OccupancyFields):
         return self._map(lambda t: t.cpu())
 
 
-class TrackedPoseFrame(PoseFrame):
+class _CandidateFields(PoseFrame):
+    """The four fields an associating tracking session adds to every frame it emits (a base class of their own, for the same reason)."""
+    __slots__ = ("candidates", "candidate_scores", "candidate_count", "chosen")
+
+
+class TrackedPoseFrame(_CandidateFields):
     """What a tracking session (``track=PoseTracking(...)``) emits.  ``keypoints`` are the Kalman-filtered ones, ``raw_keypoints`` the
     decoded ones, ``velocity`` the track's; ``covariance`` (lanes, K, 3) = (Pxx, Pxy, Pyy) of the filtered position in image pixels
-    squared; ``forecast`` (lanes, K, 2) the position ``horizon_s`` ahead; ``status`` (lanes, K) int32, one of ``STATUS``'s codes."""
+    squared; ``forecast`` (lanes, K, 2) the position ``horizon_s`` ahead; ``status`` (lanes, K) int32, one of ``STATUS``'s codes.
+    With ``PoseTracking(candidates=C > 1)`` or ``gate_on_presence`` also ``candidates`` (lanes, K, C, 2), the heat-map peaks every
+    joint's track chose among, in image pixels (peak 0 is ``raw_keypoints``), ``candidate_scores`` (lanes, K, C) their heat-map
+    values, ``candidate_count`` (lanes, K) int32 how many there are (the slots behind hold zeros) and ``chosen`` (lanes, K) int32,
+    the peak that went into the track in this frame, -1 for none; all four None otherwise."""
     __slots__ = ("covariance", "forecast", "status")
     STATUS = ("UPDATED", "COASTED_MISSING", "COASTED_GATED", "STARTED", "LOST")
 
     def __init__(self, frame, keypoints, scores, indices, heatmap, gcn_heatmap, raw_keypoints, velocity, covariance, forecast, status,
-                 present=None, occupancy=None):
+                 present=None, occupancy=None, candidates=None, candidate_scores=None, candidate_count=None, chosen=None):
         super().__init__(frame, keypoints, scores, indices, heatmap, gcn_heatmap, raw_keypoints, velocity, present, occupancy)
         self.covariance, self.forecast, self.status = covariance, forecast, status
+        self.candidates, self.candidate_scores, self.candidate_count, self.chosen = candidates, candidate_scores, candidate_count, chosen
 
     def _map(self, fn):
         return TrackedPoseFrame(self.frame, *[None if getattr(self, k) is None else fn(getattr(self, k))
-                                              for k in PoseFrame.__slots__[1:] + self.__slots__ + _OccupancyFields.__slots__])
+                                              for k in PoseFrame.__slots__[1:] + self.__slots__ + _OccupancyFields.__slots__
+                                              + _CandidateFields.__slots__])
 
 
 class PoseStream:
@@ -415,8 +460,13 @@ class PoseStream:
     ``presence=PresenceGate(...)``: scene occupancy.  Behind the window MNet of every push or flush that emits a pose, a CA-CFAR
     detector runs on the centre frame's horizontal mean planes, read from the ring, and a presence gate runs over its detections
     (csrc/cfar.hip: two launches, inside the graph replay); the emitted frame gains ``present`` and ``occupancy``, and ``reset()``
-    clears the gate.  The gate reports only: keypoints, scores and the tracker's input are what they are without it, bit for bit.
-    (Feeding absence to the tracker as a missing measurement is left to a later change.)  It composes with every other setting."""
+    clears the gate.  By itself the gate reports only: keypoints, scores and the tracker's input are what they are without it, bit
+    for bit.  It composes with every other setting.
+    ``track=PoseTracking(..., candidates=C)`` with C > 1: every joint's track chooses its measurement among up to C peaks of its
+    heat-map (csrc/pose_assoc.hip: one launch in place of the tracker's, inside the same graph replay), and the emitted frame gains
+    ``candidates``, ``candidate_scores``, ``candidate_count`` and ``chosen``.  ``PoseTracking(gate_on_presence=True)`` (needs
+    ``presence``) hands that launch the gate's verdict on the emitted frame: a lane the gate calls empty has no measurement, its tracks
+    coast and then report LOST.  With ``candidates=1`` and no coupling the session launches the plain tracker, as before."""
 
     def __init__(self, model, cfg, lanes=1, lookahead=None, graph=True, device=None, decode="argmax", smooth=None, track=None,
                  predict_now=False, decode_radius=None, tdm_compensation=False, history=False, presence=None):
@@ -425,7 +475,7 @@ class PoseStream:
         self.schedule = StreamSchedule(self.G, lookahead)
         self.lookahead = self.schedule.lookahead
         self.decode_radius = check_decode(decode, smooth, decode_radius, D.heatmapSize)
-        check_track(track, smooth, predict_now, decode)
+        check_track(track, smooth, predict_now, decode, presence)
         self.decode, self.smooth, self.predict_now = decode, smooth, bool(predict_now)
         if not isinstance(tdm_compensation, bool):
             raise StreamError("tdm_compensation must be True or False, got %r" % (tdm_compensation,))
@@ -481,6 +531,14 @@ class PoseStream:
                 self._cov = torch.empty((lanes, self.K, 3), dtype=torch.float32, device=dev)
                 self._status = torch.empty((lanes, self.K), dtype=torch.int32, device=dev)
                 self._tstate = F_.pose_track_state(lanes * self.K, dev)
+            # the associating tracker (csrc/pose_assoc.hip) in its place: the candidates it chose among and its choice
+            self._cxy = self._cscore = self._ccount = self._chosen = None
+            if track is not None and track.associates:
+                C = track.candidates
+                self._cxy = torch.zeros((lanes, self.K, C, 2), dtype=torch.float32, device=dev)
+                self._cscore = torch.zeros((lanes, self.K, C), dtype=torch.float32, device=dev)
+                self._ccount = torch.zeros((lanes, self.K), dtype=torch.int32, device=dev)
+                self._chosen = torch.full((lanes, self.K), -1, dtype=torch.int32, device=dev)
             self._history = None
             if history:
                 from .smooth import TrackHistory
@@ -544,11 +602,17 @@ class PoseStream:
         rows = self.lanes * self.K
         if self.track is not None:
             t = self.track
-            rt.check(L.hupr_pose_track_f32(rt.ptr(F_._c(gcn)), rows, self.H, self.W, self.ratio, int(self.decode == "subpixel"),
-                                           rt.ptr(self._tstate), t.rate_hz, t.accel_psd, t.meas_std, t.heatmap_gain, t.gate,
-                                           t.max_coast, t.init_speed_std, t.min_score, t.horizon_s, rt.ptr(self._idx),
-                                           rt.ptr(self._mx), rt.ptr(self._raw), rt.ptr(self._kp), rt.ptr(self._vel),
-                                           rt.ptr(self._cov), rt.ptr(self._fc), rt.ptr(self._status), s))
+            head = (rt.ptr(F_._c(gcn)), rows, self.H, self.W, self.ratio, int(self.decode == "subpixel"), rt.ptr(self._tstate),
+                    t.rate_hz, t.accel_psd, t.meas_std, t.heatmap_gain, t.gate, t.max_coast, t.init_speed_std, t.min_score, t.horizon_s)
+            outs = (rt.ptr(self._idx), rt.ptr(self._mx), rt.ptr(self._raw), rt.ptr(self._kp), rt.ptr(self._vel), rt.ptr(self._cov),
+                    rt.ptr(self._fc), rt.ptr(self._status))
+            if t.associates:                           # the presence launches of _front precede this one on the same stream
+                present = self._present if t.gate_on_presence else None
+                rt.check(L.hupr_pose_track_assoc_f32(*head, t.candidates, t.min_separation, t.peak_ratio, rt.ptr(present), self.K,
+                                                     *outs, rt.ptr(self._cxy), rt.ptr(self._cscore), rt.ptr(self._ccount),
+                                                     rt.ptr(self._chosen), s))
+            else:
+                rt.check(L.hupr_pose_track_f32(*head, *outs, s))
             return heat, gcn
         if self._fused:
             f = self.smooth
@@ -585,7 +649,7 @@ class PoseStream:
             self._history.append(self._tstate, self._status, self._kp, self._raw, self._mx)
         if self.track is not None:
             return TrackedPoseFrame(center, self._kp, self._mx, self._idx, out[0], out[1], self._raw, self._vel, self._cov, self._fc,
-                                    self._status, self._present, self._occ)
+                                    self._status, self._present, self._occ, self._cxy, self._cscore, self._ccount, self._chosen)
         return PoseFrame(center, self._kp, self._mx, self._idx, out[0], out[1], self._raw, self._vel, self._present, self._occ)
 
     # -- public ---------------------------------------------------------------------------------------------------------------
@@ -679,6 +743,14 @@ def parse(argv=None):
     p.add_argument("--accel-psd", type=float, default=None, help="with --track: white-acceleration power, pixel^2 / s^3 (default 200)")
     p.add_argument("--gate", type=float, default=None, help="with --track: largest accepted squared Mahalanobis distance (default 13.816)")
     p.add_argument("--max-coast", type=int, default=None, help="with --track: frames a track survives without a measurement (default 5)")
+    p.add_argument("--track-candidates", type=int, default=None, help="with --track: heat-map peaks every track chooses its measurement "
+                   "among, 1..4 (default 1: the strongest)")
+    p.add_argument("--track-separation", type=int, default=None, help="with --track: two peaks lie more than this many heat-map pixels "
+                   "apart (default 3)")
+    p.add_argument("--track-peak-ratio", type=float, default=None, help="with --track: a further peak is at least this fraction of the "
+                   "strongest (default 0.25)")
+    p.add_argument("--track-on-presence", action="store_true", help="with --track and --presence: no measurement while the presence gate "
+                   "sees nobody")
     p.add_argument("--rts", action="store_true", help="with --track: after the flush, smooth the whole recording backwards (Rauch-Tung-"
                    "Striebel); every record gains smoothed, smoothed_velocity, smoothed_covariance and smoothed_flag")
     p.add_argument("--tdm-compensation", action="store_true", help="compensate the TDM Doppler phase in the FFT chain (weights trained "
@@ -708,9 +780,19 @@ def parse(argv=None):
         p.error("--decode-radius must be 0 (the whole map) or a positive number of heat-map pixels")
     if not args.track:
         for flag, given in (("--predict-now", args.predict_now), ("--accel-psd", args.accel_psd is not None),
-                            ("--gate", args.gate is not None), ("--max-coast", args.max_coast is not None), ("--rts", args.rts)):
+                            ("--gate", args.gate is not None), ("--max-coast", args.max_coast is not None), ("--rts", args.rts),
+                            ("--track-candidates", args.track_candidates is not None),
+                            ("--track-separation", args.track_separation is not None),
+                            ("--track-peak-ratio", args.track_peak_ratio is not None), ("--track-on-presence", args.track_on_presence)):
             if given:
                 p.error("%s needs --track" % flag)
+    else:
+        if args.track_on_presence and not args.presence:
+            p.error("--track-on-presence needs --presence")
+        try:
+            tracking_from_args(args)
+        except TrackingError as e:
+            p.error(str(e))
     if not args.presence:
         for flag, dest in PRESENCE_FLAGS:
             if getattr(args, dest) is not None:
@@ -740,7 +822,10 @@ def tracking_from_args(args):
     if not args.track:
         return None
     kw = {k: getattr(args, k) for k in ("accel_psd", "gate", "max_coast") if getattr(args, k) is not None}
-    return PoseTracking(args.rate, **kw)
+    for dest, k in (("track_candidates", "candidates"), ("track_separation", "min_separation"), ("track_peak_ratio", "peak_ratio")):
+        if getattr(args, dest) is not None:
+            kw[k] = getattr(args, dest)
+    return PoseTracking(args.rate, gate_on_presence=args.track_on_presence, **kw)
 
 
 def add_smoothed(records, seq, lane=0):
@@ -823,6 +908,11 @@ def main(argv=None):
             records[-1]["covariance"] = [[float(v) for v in c] for c in pf.covariance.cpu().numpy()[0]]
             records[-1]["forecast"] = [[float(x), float(y)] for x, y in pf.forecast.cpu().numpy()[0]]
             records[-1]["status"] = [int(c) for c in pf.status.cpu().numpy()[0]]
+            if pf.chosen is not None:
+                records[-1]["candidates"] = [[[float(x), float(y), float(v)] for (x, y), v in zip(xy[:n], sc[:n])] for xy, sc, n in
+                                             zip(pf.candidates.cpu().numpy()[0], pf.candidate_scores.cpu().numpy()[0],
+                                                 pf.candidate_count.cpu().numpy()[0])]
+                records[-1]["chosen"] = [int(c) for c in pf.chosen.cpu().numpy()[0]]
         if pf.present is not None:
             records[-1]["present"] = int(pf.present.cpu().numpy()[0])
             records[-1]["occupancy"] = [float(v) for v in pf.occupancy.cpu().numpy()[0]]

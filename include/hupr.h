@@ -446,6 +446,50 @@ int hupr_pose_track_f32(const float* heat, long rows, int H, int W, float ratio,
                         float accel_psd, float meas_std, float heatmap_gain, float gate, int max_coast, float init_speed_std,
                         float min_score, float horizon_s, int* idx, float* maxval, float* raw_keypoints, float* keypoints,
                         float* velocity, float* covariance, float* forecast, int* status, hupr_stream_t stream);
+/* hupr_pose_track_f32 with a choice of measurement (csrc/pose_assoc.hip): up to K <= 4 peaks of every heat-map are decoded, and a live
+ * track is updated with the one inside its gate that it finds most likely — the nearest-neighbour standard filter (Bar-Shalom, Li &
+ * Kirubarajan 2001) — instead of the strongest.  New, no reference counterpart.  One 64-lane wave per row, no scratch, no LDS, no
+ * atomics: the same maps and the same state give the same bits.  Everything not said here is hupr_pose_track_f32's: the arguments up
+ * to horizon_s, the state and its layout (so a state may pass between the two entries, and hupr_pose_smooth_rts_f32 reads either's),
+ * predict, gate, update, coasting, the eight outputs and the status codes.  With K = 1 and present_or_null = NULL the eight outputs
+ * and the state are hupr_pose_track_f32's bit for bit.
+ * Candidates of a row (one H x W map, pixel index p = y W + x):
+ *   Candidate 0 is the arg-max: idx, maxval and raw_keypoints are its index, value and refined keypoint, those of
+ *     hupr_pose_track_f32 bit for bit.  A row whose maximum is not > 0 has no candidate (cand_count 0) and no measurement.
+ *   A pixel q stands in front of a pixel p when h[q] > h[p], or h[q] == h[p] and q < p.  A NaN pixel stands in front of nothing, and
+ *     nothing stands in front of it.  p is a local maximum when h[p] > 0 and none of its up to eight neighbours inside the map stands
+ *     in front of it (for maps without NaN: h[p] > h[q], or h[p] == h[q] and p < q, for every neighbour q).  A NaN pixel is never one.
+ *   Candidates 1 .. K-1 are taken greedily: the next one is the local maximum in front of all others (value descending, index
+ *     ascending) among those with h[p] >= peak_ratio * maxval (the fp32 product) and at Chebyshev distance > min_separation heat-map
+ *     pixels from every candidate already taken.  The list ends early when nothing qualifies.
+ *   Every candidate gets the sub-pixel refinement of hupr_pose_decode_f32 (for the same refine) and its own measurement covariance
+ *     R_k from the radius-3 window around its pixel, exactly as candidate 0 does in hupr_pose_track_f32.  Its score is h[p].
+ *   Usable candidate: score > min_score, keypoint finite, window mass > 0, R_k finite — and its group is present (below).
+ * Association (live track only), after the prediction: every usable candidate k gets nu_k, S_k = H P- H^T + R_k and d2_k as in
+ *   hupr_pose_track_f32.  Those with det S_k > 0 and finite and d2_k <= gate compete on c_k = d2_k + ln det S_k — minus twice the
+ *   log-likelihood of nu_k up to a constant, so a broad bump does not win on its inflated R alone.  The smallest c_k is the
+ *   measurement of the update; a tie goes to the lower k.  No such candidate: the track coasts or ends as in hupr_pose_track_f32,
+ *   with status HUPR_TRACK_COASTED_GATED if any candidate was usable, else HUPR_TRACK_COASTED_MISSING.
+ * No live track (also one that ended in this frame): candidate 0 starts one if it is usable, as in hupr_pose_track_f32.
+ * Presence coupling.  present_or_null : int [rows / rows_per_group], one flag per group of rows_per_group consecutive rows (the joints
+ *   of a lane).  Where the flag is 0 no candidate of the group is usable in this frame: a live track coasts with
+ *   HUPR_TRACK_COASTED_MISSING (or ends), a row without one stays HUPR_TRACK_LOST.  NULL: no coupling, rows_per_group is not read.
+ * Outputs beside hupr_pose_track_f32's eight: cand_xy [rows][K][2] the candidates' keypoints in image pixels, cand_score [rows][K]
+ *   their heat-map values, cand_count [rows] int, chosen [rows] int: the candidate whose measurement went into the state in this frame
+ *   (the update's; 0 with HUPR_TRACK_STARTED), -1 when none did.  Slots k >= cand_count hold zeros.
+ * Returns -1 (HUPR_ERR_ARG) before any launch for hupr_pose_track_f32's errors, a null output, K outside 1..4, min_separation < 0,
+ * peak_ratio outside (0, 1] or NaN, and, with present_or_null, rows_per_group < 1 or rows no multiple of it.  rows == 0 is a no-op. */
+int hupr_pose_track_assoc_f32(const float* heat, long rows, int H, int W, float ratio, int refine, float* state, float rate_hz,
+                              float accel_psd, float meas_std, float heatmap_gain, float gate, int max_coast, float init_speed_std,
+                              float min_score, float horizon_s, int K, int min_separation, float peak_ratio,
+                              const int* present_or_null, int rows_per_group, int* idx, float* maxval, float* raw_keypoints,
+                              float* keypoints, float* velocity, float* covariance, float* forecast, int* status, float* cand_xy,
+                              float* cand_score, int* cand_count, int* chosen, hupr_stream_t stream);
+/* The candidates of hupr_pose_track_assoc_f32 alone, without a tracker (the same kernel with no state): cand_xy [rows][K][2],
+ * cand_score [rows][K], cand_idx [rows][K] int (the pixel index p) and cand_count [rows] int, slots k >= cand_count zero.  The same
+ * argument errors; rows == 0 is a no-op. */
+int hupr_pose_peaks_f32(const float* heat, long rows, int H, int W, float ratio, int refine, int K, int min_separation,
+                        float peak_ratio, float* cand_xy, float* cand_score, int* cand_idx, int* cand_count, hupr_stream_t stream);
 /* Fixed-interval Rauch-Tung-Striebel smoother over a recorded run of hupr_pose_track_f32 in one launch (csrc/pose_smooth.hip; Rauch,
  * Tung & Striebel 1965): the backward pass over the states the filter left behind, so that the answer for frame k uses the frames
  * after it too.  New, no reference counterpart.  One thread per row, sequential in the frame: a latency-bound recurrence of T
