@@ -25,6 +25,7 @@ import torch.utils.data as data
 
 from .. import synth
 from ..misc.oks_eval import evaluate_keypoints
+from ..preprocessing.interference import INTERFERENCE_NEEDS_ADC, adc_interference, interference_setting
 from ..preprocessing.process_iwr1843 import dca1000_frames, loader_normalize
 from ..tools.augment import TDM_NEEDS_RANGE_DOPPLER, tdm_setting
 from .base import generateGTAnnot
@@ -56,15 +57,21 @@ class SequenceFFTCache:
 
     ``adc_hori`` / ``adc_vert``: int16 GPU tensors (duration, 4, 192, 256, 2) of one sequence.  ``window(index)`` returns
     the two (G, 8, 2, 64, 64, 8) fp32 network inputs of sample ``index`` (position inside the sequence), with the
-    reference's edge clamping (``window_indices``).  Memory: 2.1 MB per cached sensor-frame (600 frames x 2 = 2.5 GB)."""
+    reference's edge clamping (``window_indices``).  Memory: 2.1 MB per cached sensor-frame (600 frames x 2 = 2.5 GB).
+    ``interference``: an ``InterferenceFilter`` (``DATASET.interference``) blanks interference in both sequences first;
+    ``interference_frames`` then holds the filter's int32 (2 sensors, duration, 2) counts per frame, None otherwise."""
 
-    def __init__(self, adc_hori, adc_vert, num_group_frames, tdm_compensation=False):
+    def __init__(self, adc_hori, adc_vert, num_group_frames, tdm_compensation=False, interference=None):
         from ..preprocessing.process_iwr1843 import fft_chain_loader
         if adc_hori.shape != adc_vert.shape:
             raise ValueError("hori / vert sequences must have the same number of frames")
         self.duration = adc_hori.shape[0]
         self.G = num_group_frames
         kw = {"tdm_compensation": True} if tdm_compensation else {}      # DATASET.tdmCompensation (tools/augment.py: tdm_setting)
+        self.interference_frames = None
+        if interference is not None:
+            (adc_hori, sh, _), (adc_vert, sv, _) = adc_interference(adc_hori, interference), adc_interference(adc_vert, interference)
+            self.interference_frames = torch.stack([sh.frames, sv.frames])
         self.hori = fft_chain_loader(adc_hori, **kw)    # (duration, 8, 2, 64, 64, 8)
         self.vert = fft_chain_loader(adc_vert, **kw)
 
@@ -177,6 +184,8 @@ class HuPR3D_horivert(_AnnotatedHuPR):
     def __init__(self, phase, cfg, args, random=True, device="cuda"):
         if tdm_setting(cfg):
             raise RuntimeError(TDM_NEEDS_RANGE_DOPPLER)
+        if interference_setting(cfg) is not None:
+            raise RuntimeError(INTERFERENCE_NEEDS_ADC)
         super().__init__(phase, cfg, args, random)
         self.device = device
         self.VRDAEPaths_hori = [os.path.join(self.dirRoot, "single_%d/hori/%09d.npy" % (it["seq"], it["frame"])) for it in self.items]
@@ -205,6 +214,7 @@ class HuPRRawADC(_AnnotatedHuPR):
         self.device = device
         self.rawRoot = getattr(cfg.DATASET, "rawDir", None) or self.dirRoot
         self.tdm = tdm_setting(cfg)
+        self.interference = interference_setting(cfg)
         self.cache_sequences = cache_sequences
         self._cache = OrderedDict()
         self._seq_start = {}
@@ -219,7 +229,7 @@ class HuPRRawADC(_AnnotatedHuPR):
                 path = os.path.join(self.rawRoot, "single_%d" % seq, sensor, "adc_data.bin")
                 raw = torch.from_numpy(np.fromfile(path, dtype=np.int16)).to(self.device)
                 streams.append(dca1000_frames(raw))            # (frames, 4, 192, 256, 2) int16
-            c = SequenceFFTCache(streams[0], streams[1], self.G, tdm_compensation=self.tdm)
+            c = SequenceFFTCache(streams[0], streams[1], self.G, tdm_compensation=self.tdm, interference=self.interference)
             self._cache[seq] = c
             while len(self._cache) > self.cache_sequences:
                 self._cache.popitem(last=False)
@@ -236,6 +246,8 @@ class HuPRRawADC(_AnnotatedHuPR):
             raise ValueError("single_%d holds %d frames, cfg.DATASET.duration is %d" % (it["seq"], cache.duration, self.duration))
         h, v = cache.window(pos)
         out = {"VRDAEmap_hori": h, "VRDAEmap_vert": v}
+        if cache.interference_frames is not None:              # DATASET.interference: the filter's counts on the labelled frame
+            out["interference"] = cache.interference_frames[:, pos]
         out.update(self._labels(index))
         return out
 

@@ -2234,3 +2234,40 @@ def presence_update(summary, gate_state, min_cells=3, confirm=2, hold=20):
         rt.check(rt.lib().hupr_presence_update(rt.ptr(_c(summary)), lanes, int(min_cells), int(confirm), int(hold), rt.ptr(gate_state),
                                                rt.ptr(present), rt.stream()))
     return present
+
+
+# ---- interference blanking of the raw ADC cube in front of the FFT chain (csrc/interference.hip) ----------------------------------------
+class InterferenceStats:
+    """The counts ``adc_interference`` returns: ``frames`` int32 (n, 2) = (samples replaced, chirps touched) per sensor-frame, the sums
+    of ``groups`` int32 (n, 12, 2), the same pair per (rx, tx) group, index 3 rx + tx.  Device tensors."""
+    __slots__ = ("frames", "groups")
+
+    def __init__(self, frames, groups):
+        self.frames, self.groups = frames, groups
+
+
+def adc_interference(adc, K=32, guard=2, fill="clutter", out=None, want_mask=False):
+    """Time-domain interference detection and blanking on int16 GPU cubes ``adc`` (n, 4, 192, 256, 2), in two launches (the rule is
+    stated beside hupr_adc_interference_i16 in include/hupr.h) -> ``(cube, stats, mask)``: the filtered cube (``out``: a tensor like
+    ``adc`` to write, ``adc`` itself for in place, None for a new one), an ``InterferenceStats`` and the bit mask uint8
+    (n, 4, 192, 32) of the replaced samples (bit ``s % 8`` of byte ``s / 8``; None unless ``want_mask``).  Device tensors, no sync."""
+    from .preprocessing.interference import FILLS, check_interference
+    K, guard, fill = check_interference(K, guard, fill)
+    if not isinstance(adc, torch.Tensor) or adc.dtype != torch.int16 or adc.dim() != 5 or tuple(adc.shape[1:]) != (4, 192, 256, 2):
+        raise ValueError("adc must be int16 (n,4,192,256,2), got %s %r" % (getattr(adc, "dtype", type(adc).__name__),
+                                                                           tuple(getattr(adc, "shape", ()))))
+    if not adc.is_cuda:
+        raise rt.HuprError("adc_interference needs GPU cubes (no CPU fallback), got %s" % adc.device)
+    if out is not None and (out.dtype != adc.dtype or out.shape != adc.shape or out.device != adc.device):
+        raise ValueError("out must be a tensor like adc, got %s %r on %s" % (out.dtype, tuple(out.shape), out.device))
+    n, dev = adc.shape[0], adc.device
+    with torch.cuda.device(dev):
+        if out is None:
+            out = torch.empty_like(adc, memory_format=torch.contiguous_format)
+        groups = torch.empty((n, 12, 2), dtype=torch.int32, device=dev)
+        frames = torch.empty((n, 2), dtype=torch.int32, device=dev)
+        mask = torch.empty((n, 4, 192, 32), dtype=torch.uint8, device=dev) if want_mask else None
+        L = rt.lib()
+        rt.check(L.hupr_adc_interference_i16(rt.ptr(adc), rt.ptr(out), n, K, guard, FILLS[fill], rt.ptr(mask), rt.ptr(groups), rt.stream()))
+        rt.check(L.hupr_adc_interference_stats(rt.ptr(groups), n, rt.ptr(frames), rt.stream()))
+    return out, InterferenceStats(frames, groups), mask

@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from .. import runtime as rt
+from .interference import filtered as _interference_filtered
 
 NUM_RX, NUM_CHIRP, NUM_SAMPLE = 4, 192, 256
 
@@ -99,16 +100,18 @@ def _refuse_swap_without_tdm(tdm_compensation, tx_swapped):
 
 
 def fft_chain(adc_iq, ws=None, window=None, magnitude=False, zero_doppler=None, tdm_compensation=False, tx_swapped=None,
-              frames_per_flag=1):
+              frames_per_flag=1, interference=None):
     """adc_iq: int16 GPU tensor (n,4,192,256,2) -> complex64 GPU tensor (n,16,64,64,8).
     Opt-in (defaults = the reference: no window, complex output): ``window="hann"`` applies np.hanning windows over the
     range samples and the chirp loops, ``magnitude=True`` returns |X| as fp32.  ``zero_doppler``: see ZERO_DOPPLER_MODES.
     ``tdm_compensation=True`` multiplies the range-Doppler map by ``tdm_phase_table`` in front of the angle transform
     (hupr_fft_chain_tdm); ``tx_swapped``: uint8 device tensor, one flag per ``frames_per_flag`` sensor-frames, non-zero = that
     group's transmitters 0 and 2 were exchanged (``tools.augment.adc_mirror``); None = none.  Reference-trained weights expect the
-    default, off."""
+    default, off.  ``interference``: an ``InterferenceFilter`` runs the interference blanking of preprocessing/interference.py on the
+    cube first (two more launches, into a new buffer: ``adc_iq`` is left as it is); None, the default, is today's launches."""
     _check_adc(adc_iq)
     _refuse_swap_without_tdm(tdm_compensation, tx_swapped)
+    adc_iq = _interference_filtered(adc_iq, interference)
     n = adc_iq.shape[0]
     flags = _flags(window, magnitude, zero_doppler)
     out = torch.empty((n, 16, 64, 64, 8), dtype=torch.float32 if magnitude else torch.complex64, device=adc_iq.device)
@@ -126,12 +129,14 @@ def fft_chain(adc_iq, ws=None, window=None, magnitude=False, zero_doppler=None, 
 
 
 def fft_chain_loader(adc_iq, ws=None, out=None, window=None, zero_doppler=None, tdm_compensation=False, tx_swapped=None,
-                     frames_per_flag=1):
+                     frames_per_flag=1, interference=None):
     """adc_iq: int16 GPU tensor (n,4,192,256,2) -> fp32 GPU tensor (n, 8, 2, 64, 64, 8):
     Doppler bins 4..11, re/im split, per-elevation Normalize (datasets glue fused in).  ``window`` / ``zero_doppler`` /
-    ``tdm_compensation`` / ``tx_swapped`` / ``frames_per_flag``: see fft_chain (the statistics are those of the compensated values)."""
+    ``tdm_compensation`` / ``tx_swapped`` / ``frames_per_flag`` / ``interference``: see fft_chain (the statistics are those of the
+    compensated values)."""
     _check_adc(adc_iq)
     _refuse_swap_without_tdm(tdm_compensation, tx_swapped)
+    adc_iq = _interference_filtered(adc_iq, interference)
     n = adc_iq.shape[0]
     if out is None:
         out = torch.empty((n, 8, 2, 64, 64, 8), dtype=torch.float32, device=adc_iq.device)
@@ -149,13 +154,15 @@ def fft_chain_loader(adc_iq, ws=None, out=None, window=None, zero_doppler=None, 
     return out
 
 
-def fft_chain_loader_means(adc_iq, ws=None, zero_doppler=None, tdm_compensation=False, tx_swapped=None, frames_per_flag=1):
+def fft_chain_loader_means(adc_iq, ws=None, zero_doppler=None, tdm_compensation=False, tx_swapped=None, frames_per_flag=1,
+                           interference=None):
     """adc_iq: int16 GPU tensor (n,4,192,256,2) -> fp32 GPU tensor (n, 16, 64, 64): the loader tensor of ``fft_chain_loader``
     averaged over its elevation axis, plane index 2 f + c — what ``HuPRNet.forward`` computes first (models/networks.py:26-27).
     The fused training loader hands these planes to the model instead of the 8x larger (n,8,2,64,64,8) tensor.
-    ``tdm_compensation`` / ``tx_swapped`` / ``frames_per_flag``: see fft_chain."""
+    ``tdm_compensation`` / ``tx_swapped`` / ``frames_per_flag`` / ``interference``: see fft_chain."""
     _check_adc(adc_iq)
     _refuse_swap_without_tdm(tdm_compensation, tx_swapped)
+    adc_iq = _interference_filtered(adc_iq, interference)
     n = adc_iq.shape[0]
     out = torch.empty((n, 16, 64, 64), dtype=torch.float32, device=adc_iq.device)
     if ws is None:
@@ -231,13 +238,14 @@ class RadarObject:
         """``<dirName>/<idxFrame:09d>.npy`` (reference :180-182)."""
         np.save(os.path.join(dirName, "%09d.npy" % idxFrame), matrix)
 
-    def processRadarDataHoriVert(self, frames_per_call=64, tdm_compensation=False):
+    def processRadarDataHoriVert(self, frames_per_call=64, tdm_compensation=False, interference=None):
         """The reference's offline driver (:184-196): every sequence's two captures -> one complex128 ``(16,64,64,8)`` cube per
         frame and sensor under ``<saveDir>/{hori,vert}/%09d.npy``.  Here a capture goes to the GPU once, is de-interleaved there
         and transformed ``frames_per_call`` frames at a time (the reference parses 115 200 chirps and runs ~200 000 tiny FFT calls
         per frame in Python).  Training does not need these files: ``datasets.HuPRRawADC`` feeds the network straight from
         the captures.  ``tdm_compensation=True`` writes Doppler-compensated cubes (see ``fft_chain``); a dataset that reads them runs with
-        ``DATASET.tdmCompensation`` off, since the cubes already are."""
+        ``DATASET.tdmCompensation`` off, since the cubes already are.  ``interference``: an ``InterferenceFilter`` blanks interference in the
+        raw cubes first (see ``fft_chain``); a dataset that reads such cubes runs with ``DATASET.interference`` off."""
         for names, save_dir in zip(self.radarDataFileNameGroup, self.saveDirNameGroup):
             for sensor, name in zip(("hori", "vert"), names):
                 out_dir = os.path.join(save_dir, sensor)
@@ -246,14 +254,15 @@ class RadarObject:
                 frames = dca1000_frames(torch.from_numpy(raw).to(self.device))
                 n = min(frames.shape[0], self.numFrame)
                 for f0 in range(0, n, frames_per_call):
-                    cubes = fft_chain(frames[f0:min(n, f0 + frames_per_call)], tdm_compensation=tdm_compensation).cpu().numpy().astype(np.complex128)
+                    cubes = fft_chain(frames[f0:min(n, f0 + frames_per_call)], tdm_compensation=tdm_compensation,
+                                      interference=interference).cpu().numpy().astype(np.complex128)
                     for k, cube in enumerate(cubes):
                         self.saveRadarData(cube, out_dir, f0 + k)
                 print("%s, finished %d frames" % (name, n))
 
-    def generateHeatmap(self, frame, window=None, magnitude=False, tdm_compensation=False):
+    def generateHeatmap(self, frame, window=None, magnitude=False, tdm_compensation=False, interference=None):
         """frame: complex ndarray (4,192,256) -> complex128 ndarray (16,64,64,8) (float64 with ``magnitude``).
-        ``window`` / ``magnitude`` / ``tdm_compensation`` are opt-in extras (see ``fft_chain``); the defaults are the reference's
+        ``window`` / ``magnitude`` / ``tdm_compensation`` / ``interference`` are opt-in extras (see ``fft_chain``); the defaults are the reference's
         arithmetic."""
         frame = np.asarray(frame)
         if frame.shape != (self.numRX, self.numChirp, self.numADCSamples):
@@ -262,5 +271,5 @@ class RadarObject:
         if not np.all(np.abs(iq) <= 32767) or not np.array_equal(iq, np.rint(iq)):
             raise ValueError("generateHeatmap expects integer-valued 16-bit ADC samples")
         dev = torch.from_numpy(iq.astype(np.int16)[None]).to(self.device)
-        out = fft_chain(dev, window=window, magnitude=magnitude, tdm_compensation=tdm_compensation)
+        out = fft_chain(dev, window=window, magnitude=magnitude, tdm_compensation=tdm_compensation, interference=interference)
         return out[0].cpu().numpy().astype(np.float64 if magnitude else np.complex128)

@@ -223,6 +223,9 @@ SIGNATURES = {
     "hupr_augment_apply_f32": (c_int, [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p, c_int, c_void_p, ctypes.c_uint, c_int, c_void_p]),
     "hupr_augment_joints": (c_int, [c_void_p, c_void_p, c_long, c_int, c_int, c_void_p, ctypes.POINTER(c_int), c_long, c_void_p]),
     "hupr_flip_merge_f32": (c_int, [c_void_p] * 3 + [c_long] + [c_int] * 3 + [ctypes.POINTER(c_int), c_void_p]),
+    # interference blanking of the raw cube in front of the FFT chain (csrc/interference.hip)
+    "hupr_adc_interference_i16": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "hupr_adc_interference_stats": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
     # bf16-activation variants (same argument lists as their fp32-activation counterparts)
     "hupr_conv3x3_halo_bf16act": (c_int, [c_void_p] * 5 + [c_int] * 10 + [c_void_p]),
     "hupr_conv3x3_halo_splitk_ws_bytes": (c_size_t, [c_int] * 7),

@@ -135,6 +135,42 @@ def point_target_cube(targets, noise=0.0, seed=0, tdm=False):
     return iq[None]
 
 
+def interference_bursts(cube, chirps, amp=4000.0, length=(8, 24), seed=0):
+    """What a second FMCW radar in the band leaves in an int16 cube ``(..., 4, 192, 256, 2)``: one linear-FM burst of amplitude ``amp``
+    in each chirp of ``chirps`` (indices into the 192 chirps of a frame, the same in every frame of the cube), on all four
+    receivers with a receiver-dependent phase.  ``length``: the burst's samples, an int or an inclusive ``(lo, hi)`` range drawn per
+    chirp and frame; its start, start frequency and sweep rate are drawn too (a ramp crossing passes through the IF band once).  The
+    sum is clipped to int16.  -> (a new cube, the boolean mask ``(..., 4, 192, 256)`` of the injected samples)."""
+    cube = np.asarray(cube)
+    if cube.dtype != np.int16 or cube.shape[-4:] != (NUM_RX, NUM_CHIRP, NUM_SAMPLE, 2):
+        raise ValueError("cube must be int16 (..., 4, 192, 256, 2), got %s %r" % (cube.dtype, cube.shape))
+    lo, hi = (length, length) if isinstance(length, (int, np.integer)) else length
+    if not 1 <= lo <= hi <= NUM_SAMPLE:
+        raise ValueError("length must lie in [1, 256], got %r" % (length,))
+    chirps = [int(c) for c in chirps]
+    if any(not 0 <= c < NUM_CHIRP for c in chirps) or len(set(chirps)) != len(chirps):
+        raise ValueError("chirps must be distinct indices in [0, 192)")
+    lead = cube.shape[:-4]
+    out = cube.reshape((-1,) + cube.shape[-4:]).astype(np.float64)
+    mask = np.zeros(out.shape[:-1], dtype=bool)
+    n = len(chirps)
+    for f in range(out.shape[0]):
+        ln = randint((n,), lo, hi + 1, "ifb_len", seed, f) if n else []
+        u = uniform01(5 * n, "ifb_par", seed, f).reshape(n, 5) if n else []
+        for i, c in enumerate(chirps):
+            start = int(u[i, 0] * (NUM_SAMPLE - ln[i] + 1))
+            t = np.arange(ln[i], dtype=np.float64)
+            f0, rate = u[i, 1] - 0.5, (u[i, 2] - 0.5) / ln[i]            # cycles per sample, within the IF band over the burst
+            ph = 2.0 * np.pi * (u[i, 3] + f0 * t + 0.5 * rate * t * t)
+            for rx in range(NUM_RX):
+                z = amp * np.exp(1j * (ph + 2.0 * np.pi * u[i, 4] * rx))
+                out[f, rx, c, start:start + ln[i], 0] += z.real
+                out[f, rx, c, start:start + ln[i], 1] += z.imag
+            mask[f, :, c, start:start + ln[i]] = True
+    out = np.clip(np.rint(out), -32768, 32767).astype(np.int16)
+    return out.reshape(cube.shape), mask.reshape(lead + mask.shape[1:])
+
+
 def dca1000_encode(frames):
     """int16 (n_frames, 4, 192, 256, 2) cube -> the flat int16 stream a DCA1000 capture of those frames would hold
     (inverse of the layout getadcDataFromDCA1000 parses, process_iwr1843.py:54-83): per chirp the complex samples run

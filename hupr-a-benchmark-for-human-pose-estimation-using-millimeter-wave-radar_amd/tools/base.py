@@ -21,12 +21,16 @@ from ..misc.logger import Logger
 def preprocess_sidecar(cfg):
     """What ``preprocess.json`` records beside the checkpoints of a run the GPU FFT loader fed: the zero-Doppler convention, and
     ``"fft_tdm_compensation": true`` only when ``DATASET.tdmCompensation`` is on (a run without the key writes the file it always
-    wrote)."""
+    wrote), and ``"adc_interference": {"threshold", "guard", "fill"}`` only when ``DATASET.interference`` is on."""
     from ..preprocessing import process_iwr1843 as _pre
+    from ..preprocessing.interference import interference_setting
     from .augment import tdm_setting
     side = {"fft_zero_doppler": _pre.ZERO_DOPPLER}
     if tdm_setting(cfg):
         side["fft_tdm_compensation"] = True
+    interference = interference_setting(cfg)
+    if interference is not None:
+        side["adc_interference"] = interference.sidecar()
     return side
 
 
@@ -163,6 +167,10 @@ class BaseRunner():
             if trained and trained != _pre.ZERO_DOPPLER:
                 print("==========>WARNING: these weights were trained with HUPR_FFT_ZERO_DOPPLER=%s, this process runs %s" % (trained, _pre.ZERO_DOPPLER))
             warn = tdm_mismatch_warning(recorded, tdm_setting(self.cfg))
+            if warn:
+                print(warn)
+            from ..preprocessing.interference import interference_mismatch_warning, interference_setting
+            warn = interference_mismatch_warning(recorded, interference_setting(self.cfg))
             if warn:
                 print(warn)
         elif getattr(self, "uses_gpu_fft_loader", False):

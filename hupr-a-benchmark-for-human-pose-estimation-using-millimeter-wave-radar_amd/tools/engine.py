@@ -10,6 +10,7 @@ import torch.distributed as dist
 
 from ..misc.losses import LossComputer
 from ..models import HuPRNet
+from ..preprocessing.interference import adc_interference, interference_setting
 from ..preprocessing.process_iwr1843 import fft_chain_loader, fft_chain_loader_means
 from . import augment as aug
 from .distributed import GradientBuckets
@@ -23,7 +24,12 @@ class TrainEngine:
         # DATASET.tdmCompensation: the FFT chain compensates the Doppler phase between the transmitters' slots (preprocessing,
         # hupr_fft_chain_tdm); off = today's launches.  A mirrored horizontal cube is compensated with the slots of TX0 and TX2 exchanged
         self.tdm = aug.tdm_setting(cfg)
+        # DATASET.interference: interference blanking of both raw cubes in front of the FFT chain (preprocessing/interference.py; two
+        # launches per cube); off = today's launches.  It runs in front of the mirror, with which it commutes
+        self.interference = interference_setting(cfg)
         self.device = torch.device(device)
+        self._if_acc = torch.zeros((2, 3), dtype=torch.int64, device=self.device) if self.interference is not None else None
+        self.last_interference = None      # the (n, 2) int32 counts per sensor-frame of the cubes filtered last: (hori, vert)
         torch.manual_seed(seed)
         self.model = HuPRNet(cfg).to(self.device)
         self.lossComputer = LossComputer(cfg, self.device)
@@ -74,12 +80,31 @@ class TrainEngine:
         self.buckets.close()
 
     # -- data -------------------------------------------------------------------------------------
-    def preprocess(self, adc_hori, adc_vert, hori_swapped=None):
+    def _blank(self, adc_hori, adc_vert):
+        """DATASET.interference: both cubes through the filter, into new buffers (callers reuse their cubes, and a captured step's
+        static inputs are refilled, not regenerated); the counters of ``interference_stats`` move on the device, so a replayed step
+        counts too."""
+        out, last = [], []
+        for sensor, adc in enumerate((adc_hori, adc_vert)):
+            cube, stats, _ = adc_interference(adc, self.interference)
+            replaced = stats.frames[:, 0]
+            self._if_acc[sensor] += torch.stack([torch.full_like(replaced[0], adc.shape[0], dtype=torch.int64), (replaced > 0).sum(),
+                                                 replaced.sum()])
+            out.append(cube)
+            last.append(stats.frames)
+        self.last_interference = tuple(last)
+        return out
+
+    def preprocess(self, adc_hori, adc_vert, hori_swapped=None, _blanked=False):
         """int16 ADC cubes (B*G, 4, 192, 256, 2) per sensor -> the two network inputs.  Default (``fuse_elevation_mean``): the
         loader tensor already averaged over its elevation axis, (B, G, 16, R, A) planes — 1/8 of the bytes written by the FFT
         chain and read back by the MNet front end, bit-identical results; ``HUPR_NO_FUSED_MEAN=1`` keeps the reference-shaped
         (B,G,F,2,R,A,E) hand-over.  With ``DATASET.tdmCompensation`` both chains compensate the TDM Doppler phase; ``hori_swapped``:
-        (B,) uint8 on the device, the samples whose horizontal cube was mirrored (the vertical cube never is)."""
+        (B,) uint8 on the device, the samples whose horizontal cube was mirrored (the vertical cube never is).  With
+        ``DATASET.interference`` both cubes go through the interference filter first (``_blanked``: the caller already did that, in
+        front of its mirror)."""
+        if self.interference is not None and not _blanked:
+            adc_hori, adc_vert = self._blank(adc_hori, adc_vert)
         n = adc_hori.shape[0]
         B = n // self.G
         if self.tdm:
@@ -103,7 +128,9 @@ class TrainEngine:
         by the labels."""
         a = self.augment
         a.plan(adc_hori.shape[0] // self.G)
-        hori, vert = self.preprocess(a.adc(adc_hori), adc_vert, hori_swapped=a.flags if self.tdm and a.mirrors else None)
+        if self.interference is not None:            # the filter runs in front of the mirror (it commutes with it: whole groups move)
+            adc_hori, adc_vert = self._blank(adc_hori, adc_vert)
+        hori, vert = self.preprocess(a.adc(adc_hori), adc_vert, hori_swapped=a.flags if self.tdm and a.mirrors else None, _blanked=True)
         return a.apply(hori, 0), a.apply(vert, 1), a.labels(joints)
 
     # -- steps ------------------------------------------------------------------------------------
@@ -283,6 +310,19 @@ class TrainEngine:
         Synchronises the device: per epoch, not per step."""
         return self.augment.stats() if self.augment is not None else None
 
+    def interference_stats(self):
+        """With ``DATASET.interference`` set: {"filter": the InterferenceFilter, "hori" and "vert": {"frames": sensor-frames the filter
+        has seen so far (training and inference, every frame of every window), "touched": how many of them had a sample replaced,
+        "samples": samples replaced}}; None otherwise.  The counters live on the device and replay with a captured step; they are
+        diagnostics, not part of a checkpoint.  Synchronises the device: per epoch, not per step."""
+        if self.interference is None:
+            return None
+        acc = self._if_acc.cpu().numpy()
+        out = {"filter": self.interference}
+        for i, name in enumerate(("hori", "vert")):
+            out[name] = {"frames": int(acc[i, 0]), "touched": int(acc[i, 1]), "samples": int(acc[i, 2])}
+        return out
+
     def bone_stats(self):
         """With ``TRAINING.boneLoss`` set: {"weight": mu, "sum": (sum of B_0, sum of B_1) over the training losses so far — B_h the
         bone-vector loss of the first head and of the PRGCN head in heat-map pixels, before mu and the head weights —, "steps": how
@@ -354,8 +394,11 @@ class TrainEngine:
         """Inference from raw cubes; never augmented.  ``flip``: the flip test — one forward on the input, one on the horizontal cube
         with every frame mirrored (``hupr_adc_mirror_i16``; the same batch size, so the kernels route identically; the vertical
         input is the same tensor, tools/augment.py), and both heads merged with the mirrored, left/right-exchanged maps of the
-        second pass (``hupr_flip_merge_f32``).  Twice the work of a plain call."""
-        hori, vert = self.preprocess(adc_hori, adc_vert)
+        second pass (``hupr_flip_merge_f32``).  Twice the work of a plain call.  ``DATASET.interference`` filters both cubes once,
+        in front of the mirror."""
+        if self.interference is not None:
+            adc_hori, adc_vert = self._blank(adc_hori, adc_vert)
+        hori, vert = self.preprocess(adc_hori, adc_vert, _blanked=True)
         preds = self.infer(hori, vert)
         if not flip:
             return preds

@@ -47,6 +47,17 @@ def loss_labels(batch, mode):
     return batch["jointsFloat"].float()
 
 
+def interference_line(what, counts):
+    """DATASET.interference — the line ``Runner.train`` prints per epoch and ``Runner.eval`` per evaluation: per sensor, the share of
+    the labelled frames (window position G / 2) in which the filter replaced a sample, and the samples it replaced there.
+    ``counts``: a list of int32 (B, 2 sensors, 2) tensors, one per batch."""
+    c = torch.cat(counts).cpu().numpy().astype(np.int64) if counts else np.zeros((0, 2, 2), np.int64)
+    n = c.shape[0]
+    parts = ["%s %.3f (%d samples replaced)" % (name, float((c[:, i, 0] > 0).mean()) if n else float("nan"), int(c[:, i, 0].sum()))
+             for i, name in enumerate(("hori", "vert"))]
+    return "%s: share of %d labelled frames touched: %s" % (what, n, "  ".join(parts))
+
+
 def trust_ratio_line(epoch, stats, params):
     """TRAINING.optimizer: lamb — the epoch's line: minimum, median and maximum trust ratio of the last step over the adapted
     tensors (``ndim > 1``; the others have ratio 1 by rule) and the names of the two extremes."""
@@ -115,6 +126,14 @@ class Runner(BaseRunner):
             return self.engine.preprocess(*self._adc(batch))
         return batch["VRDAEmap_hori"].float().to(dev), batch["VRDAEmap_vert"].float().to(dev)
 
+    def _labelled_interference(self, batch):
+        """DATASET.interference: the filter's int32 (B, 2 sensors, 2) counts on the labelled frame of every sample of the batch that
+        just went through the engine (raw cubes) or through the dataset's sequence cache (``batch["interference"]``)."""
+        if "interference" in batch:
+            return batch["interference"].to(self.engine.device)
+        G = self.F
+        return torch.stack([f.view(-1, G, 2)[:, G // 2] for f in self.engine.last_interference], dim=1)
+
     def _centre_planes(self, hori):
         """The horizontal network input of a batch, (B, G, 16, R, A) mean planes or the (B, G, F, 2, R, A, E) cube (averaged over its
         elevation axis here, as HuPRNet.forward does first) -> the (B, 16, R, A) mean planes of window position G / 2, the labelled frame."""
@@ -141,9 +160,13 @@ class Runner(BaseRunner):
         detector (``functional.cfar_ra``) runs on the horizontal mean planes of every sample's labelled frame (window position G / 2)
         and the presence gate across each sequence, and one more line is printed: ``Presence: <share> of <n> labelled frames present,
         median <m> detections``.  Every labelled frame has a person in it, so the share's complement is the gate's miss rate.  Raw
-        ADC batches and stored cubes both work.  Keypoints and AP are what they are without the key."""
+        ADC batches and stored cubes both work.  Keypoints and AP are what they are without the key.
+        ``DATASET.interference`` (``preprocessing.interference_setting``): both raw cubes go through the interference filter in front
+        of the FFT chain, and one more line is printed, the share of the labelled frames in which it replaced a sample, per sensor
+        (this rank's share of the test set): nobody knows yet whether the published captures carry interference."""
         self.logger.clear(len(self.testLoader.dataset))
         savePreds, gts = [], []
+        blanked = [] if self.engine.interference is not None else None
         temporal = self.temporal
         if temporal is not None:
             smoother = SequenceSmoother(temporal.tracking, self.numKeypoints, self.engine.device)
@@ -164,6 +187,8 @@ class Runner(BaseRunner):
             else:
                 hori, vert = self._inputs(batch)
                 preds = self.engine.infer(hori, vert)
+            if blanked is not None:
+                blanked.append(self._labelled_interference(batch))
             if gate is not None:
                 if hori is None:                    # the flip test ran from the raw cubes
                     hori = self._inputs(batch)[0]
@@ -231,6 +256,8 @@ class Runner(BaseRunner):
                     print("MPJPE %s: %.3f px (n = %d)" % ((name,) + mean_position_error(gts, self.saveKeypoints([], kp, boxes, ids))[::2]))
                 for name, kp in list(tracks.items()) + [("truth", visited)]:
                     print("Jitter %s: %.3f px" % (name, jitter([kp[a:b] for a, b in walker.segments()])))
+            if blanked is not None:
+                print(interference_line("Interference", blanked))
             if gate is not None:
                 present = torch.cat(gate_present).cpu().numpy() if gate_present else np.zeros(0, np.int32)
                 counts = torch.cat(gate_counts).cpu().numpy() if gate_counts else np.zeros(0, np.float32)
@@ -255,6 +282,7 @@ class Runner(BaseRunner):
             coord0 = self.engine.coord_stats()
             bone0 = self.engine.bone_stats()
             aug0 = self.engine.augment_stats()
+            blanked = [] if self.engine.interference is not None else None
             self.logger.clear(len(self.trainLoader.dataset))
             if hasattr(self.trainLoader.sampler, "set_epoch"):
                 self.trainLoader.sampler.set_epoch(epoch)
@@ -266,6 +294,8 @@ class Runner(BaseRunner):
                 else:
                     hori, vert = self._inputs(batch)
                     loss, loss2 = self.engine.train_step(hori, vert, labels)
+                if blanked is not None:
+                    blanked.append(self._labelled_interference(batch))
                 self.logger.display(loss, loss2, batch["jointsGroup"].size(0), epoch)
                 if idxBatch % self.cfg.TRAINING.lrDecayIter == 0:
                     self.adjustLR(epoch)
@@ -304,6 +334,9 @@ class Runner(BaseRunner):
                 sig = st["mean_sigma"] * st["samples"] - aug0["mean_sigma"] * aug0["samples"]
                 print("==========>Augmentation in epoch %d: %d of %d samples mirrored, mean noise sigma %.4f (%d steps)" % (
                     epoch, st["mirrored"] - aug0["mirrored"], n, sig / max(n, 1), st["steps"] - aug0["steps"]))
+            if blanked is not None and self.rank == 0:
+                # DATASET.interference: in which share of this epoch's labelled frames the filter replaced a sample (this rank's)
+                print("==========>" + interference_line("Interference in epoch %d" % epoch, blanked))
             lamb = self.engine.lamb_stats()
             if lamb is not None and self.rank == 0:
                 print(trust_ratio_line(epoch, lamb, dict(self.model.named_parameters())))

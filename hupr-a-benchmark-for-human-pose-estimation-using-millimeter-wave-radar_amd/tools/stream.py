@@ -90,6 +90,10 @@ class TrackingError(StreamError):
     ``decode="integral"``, or ``predict_now`` without ``track``."""
 
 
+class InterferenceError(StreamError):
+    """``interference`` is not an ``InterferenceFilter``, or one of its settings is out of range."""
+
+
 class PresenceError(StreamError):
     """A ``PresenceGate`` parameter out of range, or ``presence`` is not a ``PresenceGate``."""
 
@@ -234,6 +238,14 @@ class PresenceGate:
     __repr__ = _settings_repr
 
 
+def check_interference(interference):
+    """The session's ``interference`` argument: None or an InterferenceFilter."""
+    from ..preprocessing.interference import InterferenceFilter
+    if interference is not None and not isinstance(interference, InterferenceFilter):
+        raise InterferenceError("interference must be an InterferenceFilter or None, got %r" % (interference,))
+    return interference
+
+
 def check_presence(presence):
     """The session's ``presence`` argument: None or a PresenceGate."""
     if presence is not None and not isinstance(presence, PresenceGate):
@@ -368,7 +380,13 @@ class StreamSchedule:
         return out
 
 
-class _OccupancyFields:
+class _InterferenceFields:
+    """The field a session with ``interference`` adds to every frame it emits (a base class of its own, for the same reason as the
+    next one)."""
+    __slots__ = ("interference",)
+
+
+class _OccupancyFields(_InterferenceFields):
     """The two fields a session with ``presence`` adds to every frame it emits (a base class of their own, so that ``PoseFrame.__slots__``
     and ``TrackedPoseFrame.__slots__`` list what they always listed)."""
     __slots__ = ("present", "occupancy")
@@ -380,21 +398,25 @@ class PoseFrame(_OccupancyFields):
     positions; ``heatmap`` (lanes, K, 1, H, W) and ``gcn_heatmap`` (lanes, 1, K, H, W); ``raw_keypoints`` the decoded keypoints in
     front of the filter (``keypoints`` itself without one); ``velocity`` (lanes, K, 2) image pixels per second, None without a
     filter; ``present`` (lanes,) int32, the presence gate's verdict on this frame, and ``occupancy`` (lanes, 8) fp32, the detector's
-    summary of it (``functional.CFAR_SUMMARY``), both None in a session without ``presence``.  Device tensors owned by the session,
-    valid until its next push / flush / reset."""
+    summary of it (``functional.CFAR_SUMMARY``), both None in a session without ``presence``; ``interference`` (2 sensors, lanes, 2)
+    int32, the samples the interference filter replaced and the chirps it touched in the frame PUSHED by the call that returned this
+    pose — the newest frame of the window, ``lookahead`` frames after the emitted centre —, None in a session without
+    ``interference`` and in the frames of a ``flush()``, which pushes nothing.  Device tensors owned by the session, valid until its
+    next push / flush / reset."""
     __slots__ = ("frame", "keypoints", "scores", "indices", "heatmap", "gcn_heatmap", "raw_keypoints", "velocity")
 
     def __init__(self, frame, keypoints, scores, indices, heatmap, gcn_heatmap, raw_keypoints=None, velocity=None, present=None,
-                 occupancy=None):
+                 occupancy=None, interference=None):
         self.frame, self.keypoints, self.scores, self.indices = frame, keypoints, scores, indices
         self.heatmap, self.gcn_heatmap = heatmap, gcn_heatmap
         self.raw_keypoints = keypoints if raw_keypoints is None else raw_keypoints
         self.velocity = velocity
         self.present, self.occupancy = present, occupancy
+        self.interference = interference
 
     def _map(self, fn):
         return PoseFrame(self.frame, *[None if getattr(self, k) is None else fn(getattr(self, k))
-                                       for k in PoseFrame.__slots__[1:] + _OccupancyFields.__slots__])
+                                       for k in PoseFrame.__slots__[1:] + _OccupancyFields.__slots__ + _InterferenceFields.__slots__])
 
     def clone(self):
         return self._map(torch.clone)
@@ -421,15 +443,15 @@ class TrackedPoseFrame(_CandidateFields):
     STATUS = ("UPDATED", "COASTED_MISSING", "COASTED_GATED", "STARTED", "LOST")
 
     def __init__(self, frame, keypoints, scores, indices, heatmap, gcn_heatmap, raw_keypoints, velocity, covariance, forecast, status,
-                 present=None, occupancy=None, candidates=None, candidate_scores=None, candidate_count=None, chosen=None):
-        super().__init__(frame, keypoints, scores, indices, heatmap, gcn_heatmap, raw_keypoints, velocity, present, occupancy)
+                 present=None, occupancy=None, candidates=None, candidate_scores=None, candidate_count=None, chosen=None, interference=None):
+        super().__init__(frame, keypoints, scores, indices, heatmap, gcn_heatmap, raw_keypoints, velocity, present, occupancy, interference)
         self.covariance, self.forecast, self.status = covariance, forecast, status
         self.candidates, self.candidate_scores, self.candidate_count, self.chosen = candidates, candidate_scores, candidate_count, chosen
 
     def _map(self, fn):
         return TrackedPoseFrame(self.frame, *[None if getattr(self, k) is None else fn(getattr(self, k))
                                               for k in PoseFrame.__slots__[1:] + self.__slots__ + _OccupancyFields.__slots__
-                                              + _CandidateFields.__slots__])
+                                              + _CandidateFields.__slots__ + _InterferenceFields.__slots__])
 
 
 class PoseStream:
@@ -466,10 +488,14 @@ class PoseStream:
     heat-map (csrc/pose_assoc.hip: one launch in place of the tracker's, inside the same graph replay), and the emitted frame gains
     ``candidates``, ``candidate_scores``, ``candidate_count`` and ``chosen``.  ``PoseTracking(gate_on_presence=True)`` (needs
     ``presence``) hands that launch the gate's verdict on the emitted frame: a lane the gate calls empty has no measurement, its tracks
-    coast and then report LOST.  With ``candidates=1`` and no coupling the session launches the plain tracker, as before."""
+    coast and then report LOST.  With ``candidates=1`` and no coupling the session launches the plain tracker, as before.
+    ``interference=InterferenceFilter(...)``: interference blanking of the pushed frames (preprocessing/interference.py,
+    csrc/interference.hip: two launches between the upload and the FFT chain, inside the same graph replay, in place on the session's
+    device copy of the frames — a caller's device tensors are left as they are).  Every frame a push emits gains ``interference``,
+    the filter's counts on the frame that push brought in.  It composes with every other setting; the default adds nothing."""
 
     def __init__(self, model, cfg, lanes=1, lookahead=None, graph=True, device=None, decode="argmax", smooth=None, track=None,
-                 predict_now=False, decode_radius=None, tdm_compensation=False, history=False, presence=None):
+                 predict_now=False, decode_radius=None, tdm_compensation=False, history=False, presence=None, interference=None):
         D = cfg.DATASET
         self.G = D.numGroupFrames
         self.schedule = StreamSchedule(self.G, lookahead)
@@ -486,6 +512,7 @@ class PoseStream:
             raise TrackingError("history needs track: it records the tracker's states for smoothed()")
         self.track = track.with_horizon(self.lookahead / track.rate_hz) if predict_now else track
         self.presence = check_presence(presence)
+        self.interference = check_interference(interference)
         if not isinstance(lanes, int) or lanes < 1:
             raise StreamError("lanes must be a positive integer, got %r" % (lanes,))
         self.device = torch.device(device) if device is not None else next(model.parameters()).device
@@ -550,6 +577,11 @@ class PoseStream:
                 self._occ = torch.zeros((lanes, 8), dtype=torch.float32, device=dev)
                 self._gstate = F_.presence_state(lanes, dev)
                 self._present = torch.zeros(lanes, dtype=torch.int32, device=dev)
+            # interference blanking (csrc/interference.hip): the counts per group and their sums per sensor-frame
+            self._if_groups = self._if_stats = None
+            if interference is not None:
+                self._if_groups = torch.zeros((2 * lanes, 12, 2), dtype=torch.int32, device=dev)
+                self._if_stats = torch.zeros((2, lanes, 2), dtype=torch.int32, device=dev)
             self._done = torch.cuda.Event()
         self._graphs = {}              # "host" / "device" input -> (CUDAGraph, (heatmap, gcn_heatmap))
         self._eager_emits = 0
@@ -571,6 +603,12 @@ class PoseStream:
         from ..preprocessing import process_iwr1843 as pre
         L, s = rt.lib(), rt.stream()
         if not flush:
+            f = self.interference
+            if f is not None:                      # in place on the session's copy of the frames: a workgroup holds its group before it writes
+                from ..preprocessing.interference import FILLS
+                rt.check(L.hupr_adc_interference_i16(rt.ptr(self._adc), rt.ptr(self._adc), 2 * self.lanes, f.K, f.guard, FILLS[f.fill], None,
+                                                     rt.ptr(self._if_groups), s))
+                rt.check(L.hupr_adc_interference_stats(rt.ptr(self._if_groups), 2 * self.lanes, rt.ptr(self._if_stats), s))
             flags = pre._flags(None, False, None)
             if self.tdm_compensation:
                 rt.check(L.hupr_fft_chain_tdm(rt.ptr(self._adc), 2 * self.lanes, rt.ptr(self._staging), flags, 2, None, 0, 1,
@@ -644,13 +682,15 @@ class PoseStream:
             self._done.synchronize()
             self._busy = False
 
-    def _frame(self, center, out):
+    def _frame(self, center, out, pushed=True):
         if self._history is not None:                          # the emitted pose into the history: eager copies behind the launches
             self._history.append(self._tstate, self._status, self._kp, self._raw, self._mx)
         if self.track is not None:
             return TrackedPoseFrame(center, self._kp, self._mx, self._idx, out[0], out[1], self._raw, self._vel, self._cov, self._fc,
-                                    self._status, self._present, self._occ, self._cxy, self._cscore, self._ccount, self._chosen)
-        return PoseFrame(center, self._kp, self._mx, self._idx, out[0], out[1], self._raw, self._vel, self._present, self._occ)
+                                    self._status, self._present, self._occ, self._cxy, self._cscore, self._ccount, self._chosen,
+                                    self._if_stats if pushed else None)
+        return PoseFrame(center, self._kp, self._mx, self._idx, out[0], out[1], self._raw, self._vel, self._present, self._occ,
+                         self._if_stats if pushed else None)
 
     # -- public ---------------------------------------------------------------------------------------------------------------
     def push(self, adc_hori, adc_vert):
@@ -695,7 +735,7 @@ class PoseStream:
         with torch.cuda.device(self.device), torch.no_grad(), F_.math_mode(self.mode):
             for center, _ in self.schedule.flush():
                 self._front(True)
-                frames.append(self._frame(center, self._back()).clone())
+                frames.append(self._frame(center, self._back(), pushed=False).clone())
         return frames
 
     def reset(self):
@@ -763,6 +803,14 @@ def parse(argv=None):
     p.add_argument("--min-cells", type=int, default=None, help="with --presence: detections that make a frame a hit (default 3)")
     p.add_argument("--confirm", type=int, default=None, help="with --presence: consecutive hits until present (default 2)")
     p.add_argument("--hold", type=int, default=None, help="with --presence: consecutive misses that are bridged (default 20)")
+    p.add_argument("--interference", action="store_true", help="interference blanking of every pushed frame in front of the FFT chain; "
+                   "every record gains interference")
+    p.add_argument("--interference-threshold", type=int, default=None, help="with --interference: power ratio K over the chirp's median "
+                   "residual power, in [2, 1024] (default 32)")
+    p.add_argument("--interference-guard", type=int, default=None, help="with --interference: samples flagged on each side of a flagged "
+                   "one, in [0, 8] (default 2)")
+    p.add_argument("--interference-fill", choices=("clutter", "zero"), default=None, help="with --interference: what replaces a flagged "
+                   "sample (default clutter)")
     p.add_argument("--weights", choices=WEIGHTS, default="live", help="live: model_state_dict as trained; averaged: ema_state_dict "
                    "(a run with TRAINING.emaDecay)")
     args = p.parse_args(argv)
@@ -802,7 +850,32 @@ def parse(argv=None):
             presence_from_args(args)
         except PresenceError as e:
             p.error(str(e))
+    if not args.interference:
+        for flag, dest in INTERFERENCE_FLAGS:
+            if getattr(args, dest) is not None:
+                p.error("%s needs --interference" % flag)
+    else:
+        try:
+            interference_from_args(args)
+        except ValueError as e:
+            p.error(str(e))
     return args
+
+
+INTERFERENCE_FLAGS = (("--interference-threshold", "interference_threshold"), ("--interference-guard", "interference_guard"),
+                      ("--interference-fill", "interference_fill"))
+
+
+def interference_from_args(args):
+    """The InterferenceFilter of a parsed command line (None without --interference)."""
+    if not args.interference:
+        return None
+    from ..preprocessing.interference import InterferenceFilter
+    names = {"interference_threshold": "K", "interference_guard": "guard", "interference_fill": "fill"}
+    try:
+        return InterferenceFilter(**{names[dest]: getattr(args, dest) for _, dest in INTERFERENCE_FLAGS if getattr(args, dest) is not None})
+    except ValueError as e:
+        raise InterferenceError("--interference: %s" % e) from None
 
 
 PRESENCE_FLAGS = (("--pfa", "pfa"), ("--cfar-guard", "cfar_guard"), ("--cfar-train", "cfar_train"), ("--min-cells", "min_cells"),
@@ -841,11 +914,11 @@ def add_smoothed(records, seq, lane=0):
     return records
 
 
-def load_model_best(model, log_dir, device, weights="live", tdm_compensation=False):
+def load_model_best(model, log_dir, device, weights="live", tdm_compensation=False, interference=None):
     """``model_best.pth`` of ``log_dir`` into ``model``, the way Runner.loadModelWeight reads it for evaluation.  ``weights``:
     ``"live"`` = ``model_state_dict``, the parameters as trained; ``"averaged"`` = ``ema_state_dict``, their moving average, which
     only a run with ``TRAINING.emaDecay`` saved.  ``tdm_compensation``: what the session will run, compared with what
-    ``preprocess.json`` says the weights were trained with."""
+    ``preprocess.json`` says the weights were trained with; ``interference`` (None or an InterferenceFilter) likewise."""
     if weights not in WEIGHTS:
         raise ValueError("weights must be one of %s, got %r" % (", ".join(WEIGHTS), weights))
     from ..preprocessing import process_iwr1843 as pre
@@ -872,6 +945,10 @@ def load_model_best(model, log_dir, device, weights="live", tdm_compensation=Fal
         warn = tdm_mismatch_warning(recorded, tdm_compensation)
         if warn:
             print(warn)
+        from ..preprocessing.interference import interference_mismatch_warning
+        warn = interference_mismatch_warning(recorded, interference)
+        if warn:
+            print(warn)
     print("==========>Load the model weight from %s, saved at epoch %d" % (log_dir, ck["epoch"]))
 
 
@@ -885,7 +962,8 @@ def main(argv=None):
     dev = torch.device("cuda", torch.cuda.current_device())
     cfg = load_config(args.config, "./config" if os.path.isdir("./config") else None)
     model = HuPRNet(cfg).to(dev).eval()
-    load_model_best(model, os.path.join("./logs", args.dir), dev, weights=args.weights, tdm_compensation=args.tdm_compensation)
+    load_model_best(model, os.path.join("./logs", args.dir), dev, weights=args.weights, tdm_compensation=args.tdm_compensation,
+                    interference=interference_from_args(args))
     if args.math is not None:
         model.math_mode = args.math
     frames = []
@@ -896,7 +974,7 @@ def main(argv=None):
     session = PoseStream(model, cfg, lanes=1, lookahead=args.lookahead, graph=not args.no_graph, device=dev, decode=args.decode,
                          smooth=PoseSmoothing(args.rate) if args.smooth else None, track=tracking_from_args(args),
                          predict_now=args.predict_now, decode_radius=args.decode_radius, tdm_compensation=args.tdm_compensation,
-                         history=args.rts, presence=presence_from_args(args))
+                         history=args.rts, presence=presence_from_args(args), interference=interference_from_args(args))
     records = []
 
     def record(pf):
@@ -916,6 +994,8 @@ def main(argv=None):
         if pf.present is not None:
             records[-1]["present"] = int(pf.present.cpu().numpy()[0])
             records[-1]["occupancy"] = [float(v) for v in pf.occupancy.cpu().numpy()[0]]
+        if pf.interference is not None:              # (sensor, {samples replaced, chirps touched}) of the frame this push brought in
+            records[-1]["interference"] = [[int(v) for v in row] for row in pf.interference.cpu().numpy()[:, 0]]
 
     for i in range(n):
         pf = session.push(frames[0][i:i + 1], frames[1][i:i + 1])

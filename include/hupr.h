@@ -992,6 +992,39 @@ int hupr_augment_joints(const void* joints, void* out, long B, int K, int is_flo
 int hupr_flip_merge_f32(const float* p, const float* pm, float* out, long B, int K, int H, int W, const int* pair_host,
                         hupr_stream_t stream);
 
+/* (a15) Interference blanking of the raw cube in front of the FFT chain (csrc/interference.hip; DATASET.interference, the live
+ * stream's `interference=`).  New, no reference counterpart: the reference transforms the cube as it comes.  A second FMCW radar in
+ * the band (every HuPR capture runs two) leaves short high-amplitude bursts in single chirps wherever the ramps cross inside the IF
+ * bandwidth; the range transform smears one over all 64 range bins.  The rule is integer arithmetic on the int16 samples: every
+ * output is exact, repeats bit for bit, and no launch uses an atomic.  Stream-ordered and capturable in a hipGraph.
+ *
+ * adc[n_sf][4 rx][192 = 3 cc + tx][256][2] int16.  A group is one (sensor-frame, rx, tx): 64 chirp loops cc of 256 complex samples,
+ * 64 rows of 1 KiB, 3 KiB apart; group index 3 rx + tx.  Groups are independent.  Per group:
+ *   1. S[s] = sum over the 64 loops of x[cc][s], per component, int32.
+ *   2. r[cc][s] = 64 x[cc][s] - S[s] per component (64 times the clutter-removed sample, |r| < 2^22) and p[cc][s] = r_I^2 + r_Q^2 as an
+ *      unsigned 64-bit integer (< 2^45).
+ *   3. med[cc] = the lower median of the loop's 256 values of p: the 128th smallest, sorted index 127.
+ *   4. sample (cc, s) is flagged when p > K max(med, 1), compared in 64 bits; K is a power ratio, an integer in [2, 1024].
+ *   5. the flags are dilated along s by `guard` samples on each side (guard in [0, 8]), clipped at samples 0 and 255; never into
+ *      another loop.
+ *   6. an unflagged sample is copied.  A flagged one is replaced, per component, by
+ *        fill = HUPR_INTERFERENCE_FILL_CLUTTER: floor((2 Sc + n) / (2 n)), Sc the sum of x[cc'][s] over the n loops cc' NOT flagged at s
+ *               (the clutter estimate rounded half up; 0 when n = 0) - behind the chain's clutter null that is a zero in the
+ *               clutter-removed domain;
+ *        fill = HUPR_INTERFERENCE_FILL_ZERO: 0.
+ * Under complex Gaussian noise alone the flag rate is close to 2^-K, a little above it because the 256-sample median is itself noisy.
+ * mask_or_null: uint8 [n_sf][4][192][32], bit s % 8 of byte s / 8 of a row = sample s flagged (after dilation), 4-byte aligned.
+ * group_counts: int32 [n_sf][12][2] = {samples replaced, loops touched} per group.  out == adc exactly is allowed (a workgroup holds
+ * its whole group before it writes); any other overlap between the buffers is refused.  adc and out 16-byte aligned.  One launch,
+ * one workgroup per group; 786 432 B per sensor-frame each way.  n_sf == 0 is a no-op; n_sf at most 2^20. */
+#define HUPR_INTERFERENCE_FILL_CLUTTER 0
+#define HUPR_INTERFERENCE_FILL_ZERO 1
+int hupr_adc_interference_i16(const void* adc, void* out, int n_sf, int K, int guard, int fill, unsigned char* mask_or_null,
+                              int* group_counts, hupr_stream_t stream);
+/* stats[n_sf][2] int32 = the sums of group_counts over a sensor-frame's 12 groups, in group order: {samples replaced, chirps touched}.
+ * One small launch.  stats does not overlap group_counts. */
+int hupr_adc_interference_stats(const int* group_counts, int n_sf, int* stats, hupr_stream_t stream);
+
 /* ---- bf16-activation variants ("bf16act") -------------------------------------------------------------
  * Same operators with the ACTIVATION tensors (x, y, dy, dx, residual) stored as bf16 in HBM; parameters,
  * statistics, weight gradients and all arithmetic stay fp32 (fp32 accumulate on the matrix pipe).  The
