@@ -1944,12 +1944,31 @@ def gaussian_targets_subpixel(joints, hsize=64, isize=256, sigma=2):
     return t
 
 
-def argmax_rows(p):
-    """p (rows, n) GPU -> (idx int32 (rows,), maxval (rows,)) with first-max tie-break."""
+_I32, _F32 = torch.int32, torch.float32
+
+
+def _outputs(name, out, lead, device, slots):
+    """``name``'s outputs, one per slot — (tail shape, dtype), or None where the call returns None: new ``lead + tail`` tensors on
+    ``device`` or, nothing allocated, the caller's own tuple ``out`` once each entry fits its slot (a ValueError before any launch)."""
+    if out is None:
+        return tuple(s and torch.empty(lead + s[0], dtype=s[1], device=device) for s in slots)
+    if not isinstance(out, (tuple, list)) or len(out) != len(slots):
+        raise ValueError("%s: out must be a tuple of %d entries, got %s" % (name, len(slots), type(out).__name__))
+    for k, (t, s) in enumerate(zip(out, slots)):
+        fits = t is None if s is None else (isinstance(t, torch.Tensor) and tuple(t.shape) == lead + s[0] and t.dtype == s[1]
+                                            and t.device == device and t.is_contiguous())
+        if not fits:
+            want = "None" if s is None else "a contiguous %s tensor of shape %r on %s" % (s[1], lead + s[0], device)
+            got = "%s %r with strides %r on %s" % (t.dtype, tuple(t.shape), t.stride(), t.device) if isinstance(t, torch.Tensor) else repr(t)
+            raise ValueError("%s: out[%d] must be %s, got %s" % (name, k, want, got))
+    return tuple(out)
+
+
+def argmax_rows(p, out=None):
+    """p (rows, n) GPU -> (idx int32 (rows,), maxval (rows,)) with first-max tie-break.  ``out``: that tuple, to write (``_outputs``)."""
     p = _c(p)
     rows, n = p.shape
-    idx = torch.empty(rows, dtype=torch.int32, device=p.device)
-    mx = torch.empty(rows, dtype=torch.float32, device=p.device)
+    idx, mx = _outputs("argmax_rows", out, (rows,), p.device, (((), _I32), ((), _F32)))
     rt.check(rt.lib().hupr_argmax_rows_f32(rt.ptr(p), rows, n, rt.ptr(idx), rt.ptr(mx), rt.stream()))
     return idx, mx
 
@@ -1971,25 +1990,21 @@ def _pose_heat(name, heat):
     return heat, lead, int(np.prod(lead, dtype=np.int64)), H, W
 
 
-def _pose_decode(entry, checked, mode, ratio, filter_state, smoothing):
-    """Allocate and launch for the two plain decodes: ``entry`` is the library's function, ``checked`` what ``_pose_heat`` returned,
-    ``mode`` the one argument in which the two differ (refine / radius)."""
+def _pose_decode(name, checked, mode, ratio, filter_state, smoothing, out):
+    """Launch for the two plain decodes: ``name`` is the function's and, as hupr_<name>_f32, its library entry's, ``checked`` what
+    ``_pose_heat`` returned, ``mode`` the one argument in which the two differ (refine / radius), ``out`` see ``_outputs``."""
     if (filter_state is None) != (smoothing is None):
         raise ValueError("filter_state and smoothing go together")
     heat, lead, rows, H, W = checked
-    idx = torch.empty(lead, dtype=torch.int32, device=heat.device)
-    mx = torch.empty(lead, dtype=torch.float32, device=heat.device)
-    raw = torch.empty(lead + (2,), dtype=torch.float32, device=heat.device)
-    kp = vel = None
-    params = (0.0,) * 5
+    params, xy = (0.0,) * 5, None                                     # without a filter: no filtered keypoints, no velocity
     if filter_state is not None:
         if filter_state.dtype != torch.float32 or filter_state.numel() * 4 != int(rt.lib().hupr_pose_filter_state_bytes(rows)):
             raise ValueError("filter_state must be the fp32 tensor pose_filter_state(%d, device) returns" % rows)
-        kp, vel = torch.empty_like(raw), torch.empty_like(raw)
-        params = tuple(float(getattr(smoothing, k)) for k in ("rate_hz", "min_cutoff", "beta", "d_cutoff", "min_score"))
-    rt.check(entry(rt.ptr(heat), rows, H, W, float(ratio), mode, rt.ptr(filter_state), *params, rt.ptr(idx), rt.ptr(mx), rt.ptr(raw),
-                   rt.ptr(kp), rt.ptr(vel), rt.stream()))
-    return idx, mx, raw, kp, vel
+        params, xy = tuple(float(getattr(smoothing, k)) for k in ("rate_hz", "min_cutoff", "beta", "d_cutoff", "min_score")), ((2,), _F32)
+    out = _outputs(name, out, lead, heat.device, (((), _I32), ((), _F32), ((2,), _F32), xy, xy))
+    entry = getattr(rt.lib(), "hupr_%s_f32" % name)
+    rt.check(entry(rt.ptr(heat), rows, H, W, float(ratio), mode, rt.ptr(filter_state), *params, *map(rt.ptr, out), rt.stream()))
+    return out
 
 
 def pose_filter_state(rows, device):
@@ -1997,27 +2012,28 @@ def pose_filter_state(rows, device):
     return _pose_state(rt.lib().hupr_pose_filter_state_bytes, rows, device)
 
 
-def pose_decode(heat, ratio, refine=True, filter_state=None, smoothing=None):
+def pose_decode(heat, ratio, refine=True, filter_state=None, smoothing=None, out=None):
     """heat (..., H, W) fp32 GPU -> (idx int32 (...), maxval (...), raw keypoints (..., 2), filtered keypoints, velocity) in one launch
     (csrc/pose_decode.hip; the rule is stated beside hupr_pose_decode_f32 in include/hupr.h).  ``idx`` / ``maxval`` are
     ``argmax_rows``' bits; the keypoints are (x, y) in heat-map pixels times ``ratio``, refined to sub-pixel position unless
     ``refine`` is false.  ``filter_state`` (``pose_filter_state``, advanced in place) together with ``smoothing`` (an object with
     ``rate_hz``, ``min_cutoff``, ``beta``, ``d_cutoff``, ``min_score``: tools.stream.PoseSmoothing) adds the One-Euro filter: the
-    filtered keypoints and the velocity in pixels per second, both None without it.  Device tensors, no sync."""
+    filtered keypoints and the velocity in pixels per second, both None without it.  ``out``: that 5-tuple, to write
+    (``_outputs``).  Device tensors, no sync."""
     checked = _pose_heat("pose_decode", heat)
-    return _pose_decode(rt.lib().hupr_pose_decode_f32, checked, int(bool(refine)), ratio, filter_state, smoothing)
+    return _pose_decode("pose_decode", checked, int(bool(refine)), ratio, filter_state, smoothing, out)
 
 
-def pose_decode_integral(heat, ratio, radius, filter_state=None, smoothing=None):
+def pose_decode_integral(heat, ratio, radius, filter_state=None, smoothing=None, out=None):
     """heat (..., H, W) fp32 GPU -> ``pose_decode``'s 5-tuple in one launch (csrc/pose_integral.hip; the rule is stated beside
     hupr_pose_decode_integral_f32 in include/hupr.h): the raw keypoint is the mass centroid of the weights max(h, 0) over the window
     of ``radius`` pixels around the arg-max, clipped to the map, times ``ratio``; ``radius`` 0 is the whole map, the centroid the
-    integral coordinate loss trains.  ``idx`` / ``maxval`` are ``argmax_rows``' bits.  ``filter_state`` and ``smoothing`` are
+    integral coordinate loss trains.  ``idx`` / ``maxval`` are ``argmax_rows``' bits.  ``filter_state``, ``smoothing`` and ``out`` are
     ``pose_decode``'s: the same state tensor, the same One-Euro filter (csrc/pose_filter.h).  Device tensors, no sync."""
     checked = _pose_heat("pose_decode_integral", heat)
     if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 0 <= radius < 2 ** 31:
         raise ValueError("pose_decode_integral needs an integer radius >= 0 (0 = the whole map), got %r" % (radius,))
-    return _pose_decode(rt.lib().hupr_pose_decode_integral_f32, checked, int(radius), ratio, filter_state, smoothing)
+    return _pose_decode("pose_decode_integral", checked, int(radius), ratio, filter_state, smoothing, out)
 
 
 TRACK_UPDATED, TRACK_COASTED_MISSING, TRACK_COASTED_GATED, TRACK_STARTED, TRACK_LOST = range(5)      # pose_track's status codes
@@ -2048,12 +2064,6 @@ def check_peaks(K, min_separation, peak_ratio, name="pose_peaks"):
     return int(K), int(min_separation), float(peak_ratio)
 
 
-def _pose_candidates(lead, K, device):
-    """The four candidate outputs for ``lead`` rows of K slots: positions, scores, indices, counts."""
-    return (torch.empty(lead + (K, 2), dtype=torch.float32, device=device), torch.empty(lead + (K,), dtype=torch.float32, device=device),
-            torch.empty(lead + (K,), dtype=torch.int32, device=device), torch.empty(lead, dtype=torch.int32, device=device))
-
-
 def pose_peaks(heat, ratio, K, min_separation=3, peak_ratio=0.25, refine=True):
     """heat (..., H, W) fp32 GPU -> (positions (..., K, 2) in image pixels, scores (..., K), pixel indices int32 (..., K), count int32
     (...)): the up to ``K`` <= 4 peaks of every map that the associating tracker chooses among, in one launch and without a tracker
@@ -2062,13 +2072,13 @@ def pose_peaks(heat, ratio, K, min_separation=3, peak_ratio=0.25, refine=True):
     ``min_separation`` heat-map pixels (Chebyshev) from every peak taken; slots past the count hold zeros.  Device tensors, no sync."""
     heat, lead, rows, H, W = _pose_heat("pose_peaks", heat)
     K, min_separation, peak_ratio = check_peaks(K, min_separation, peak_ratio)
-    xy, score, index, count = _pose_candidates(lead, K, heat.device)
+    xy, score, index, count = _outputs("pose_peaks", None, lead, heat.device, (((K, 2), _F32), ((K,), _F32), ((K,), _I32), ((), _I32)))
     rt.check(rt.lib().hupr_pose_peaks_f32(rt.ptr(heat), rows, H, W, float(ratio), int(bool(refine)), K, min_separation, peak_ratio,
                                           rt.ptr(xy), rt.ptr(score), rt.ptr(index), rt.ptr(count), rt.stream()))
     return xy, score, index, count
 
 
-def pose_track(heat, ratio, refine=True, track_state=None, tracking=None, present=None):
+def pose_track(heat, ratio, refine=True, track_state=None, tracking=None, present=None, out=None):
     """heat (..., H, W) fp32 GPU -> (idx int32 (...), maxval (...), raw keypoints (..., 2), filtered keypoints (..., 2), velocity
     (..., 2), position covariance (..., 3) = (Pxx, Pxy, Pyy), forecast (..., 2), status int32 (...)) in one launch
     (csrc/pose_track.hip; the rule is stated beside hupr_pose_track_f32 in include/hupr.h).  ``idx`` / ``maxval`` / raw keypoints are
@@ -2079,7 +2089,7 @@ def pose_track(heat, ratio, refine=True, track_state=None, tracking=None, presen
     group of joints, 0 = nobody there, the group has no measurement in this frame), the launch is the associating tracker's
     (csrc/pose_assoc.hip, hupr_pose_track_assoc_f32): it reads ``tracking.candidates``, ``min_separation`` and ``peak_ratio`` too and
     returns the eight outputs plus (candidate positions (..., K, 2), candidate scores (..., K), candidate count int32 (...), chosen
-    int32 (...), -1 where no measurement went into the state)."""
+    int32 (...), -1 where no measurement went into the state).  ``out``: the returned 8- or 12-tuple, to write (``_outputs``)."""
     heat, lead, rows, H, W = _pose_heat("pose_track", heat)
     if track_state is None or tracking is None:
         raise ValueError("pose_track needs its track_state and its tracking parameters")
@@ -2089,17 +2099,13 @@ def pose_track(heat, ratio, refine=True, track_state=None, tracking=None, presen
     if track_state.device != heat.device:
         raise ValueError("track_state is on %s, the heat-maps on %s" % (track_state.device, heat.device))
     params = tuple(int(getattr(tracking, k)) if k == "max_coast" else float(getattr(tracking, k)) for k in _TRACK_PARAMS)
-    idx = torch.empty(lead, dtype=torch.int32, device=heat.device)
-    mx = torch.empty(lead, dtype=torch.float32, device=heat.device)
-    raw, kp, vel, fc = (torch.empty(lead + (2,), dtype=torch.float32, device=heat.device) for _ in range(4))
-    cov = torch.empty(lead + (3,), dtype=torch.float32, device=heat.device)
-    status = torch.empty(lead, dtype=torch.int32, device=heat.device)
+    slots = (((), _I32), ((), _F32)) + (((2,), _F32),) * 3 + (((3,), _F32), ((2,), _F32), ((), _I32))
     K = getattr(tracking, "candidates", 1)
     if K == 1 and present is None:
+        out = _outputs("pose_track", out, lead, heat.device, slots)
         rt.check(rt.lib().hupr_pose_track_f32(rt.ptr(heat), rows, H, W, float(ratio), int(bool(refine)), rt.ptr(track_state), *params,
-                                              rt.ptr(idx), rt.ptr(mx), rt.ptr(raw), rt.ptr(kp), rt.ptr(vel), rt.ptr(cov), rt.ptr(fc),
-                                              rt.ptr(status), rt.stream()))
-        return idx, mx, raw, kp, vel, cov, fc, status
+                                              *map(rt.ptr, out), rt.stream()))
+        return out
     K, sep, floor = check_peaks(K, getattr(tracking, "min_separation", 3), getattr(tracking, "peak_ratio", 0.25), "pose_track")
     group = 1
     if present is not None:
@@ -2110,13 +2116,10 @@ def pose_track(heat, ratio, refine=True, track_state=None, tracking=None, presen
         if present.device != heat.device:
             raise ValueError("present is on %s, the heat-maps on %s" % (present.device, heat.device))
         group = lead[-1] if lead else 1
-    xy, score, _, count = _pose_candidates(lead, K, heat.device)
-    chosen = torch.empty(lead, dtype=torch.int32, device=heat.device)
+    out = _outputs("pose_track", out, lead, heat.device, slots + (((K, 2), _F32), ((K,), _F32), ((), _I32), ((), _I32)))
     rt.check(rt.lib().hupr_pose_track_assoc_f32(rt.ptr(heat), rows, H, W, float(ratio), int(bool(refine)), rt.ptr(track_state), *params,
-                                                K, sep, floor, rt.ptr(present), group, rt.ptr(idx), rt.ptr(mx), rt.ptr(raw),
-                                                rt.ptr(kp), rt.ptr(vel), rt.ptr(cov), rt.ptr(fc), rt.ptr(status), rt.ptr(xy),
-                                                rt.ptr(score), rt.ptr(count), rt.ptr(chosen), rt.stream()))
-    return idx, mx, raw, kp, vel, cov, fc, status, xy, score, count, chosen
+                                                K, sep, floor, rt.ptr(present), group, *map(rt.ptr, out), rt.stream()))
+    return out
 
 
 SMOOTH_SMOOTHED, SMOOTH_END, SMOOTH_PASSTHROUGH, SMOOTH_DEGENERATE = range(4)                   # pose_smooth_rts's flags
@@ -2221,15 +2224,15 @@ def presence_state(lanes, device):
     return torch.zeros((lanes, 4), dtype=torch.int32, device=device)
 
 
-def presence_update(summary, gate_state, min_cells=3, confirm=2, hold=20):
+def presence_update(summary, gate_state, min_cells=3, confirm=2, hold=20, out=None):
     """One frame of the presence gate (hupr_presence_update in include/hupr.h): ``summary`` (lanes, 8) fp32 of ``cfar_ra``,
-    ``gate_state`` (``presence_state``, advanced in place) -> present int32 (lanes,).  Device tensors, no sync."""
+    ``gate_state`` (``presence_state``, advanced in place) -> present int32 (lanes,), ``out`` if given.  Device tensors, no sync."""
     if summary.dtype != torch.float32 or summary.dim() != 2 or summary.shape[1] != 8:
         raise ValueError("presence_update needs the (lanes, 8) fp32 summary of cfar_ra, got %s %r" % (summary.dtype, tuple(summary.shape)))
     lanes = summary.shape[0]
     if gate_state.dtype != torch.int32 or tuple(gate_state.shape) != (lanes, 4) or gate_state.device != summary.device:
         raise ValueError("gate_state must be the int32 tensor presence_state(%d, device) returns" % lanes)
-    present = torch.empty(lanes, dtype=torch.int32, device=summary.device)
+    present, = _outputs("presence_update", None if out is None else (out,), (lanes,), summary.device, (((), _I32),))
     with torch.cuda.device(summary.device):
         rt.check(rt.lib().hupr_presence_update(rt.ptr(_c(summary)), lanes, int(min_cells), int(confirm), int(hold), rt.ptr(gate_state),
                                                rt.ptr(present), rt.stream()))
@@ -2246,28 +2249,25 @@ class InterferenceStats:
         self.frames, self.groups = frames, groups
 
 
-def adc_interference(adc, K=32, guard=2, fill="clutter", out=None, want_mask=False):
+def adc_interference(adc, K=32, guard=2, fill="clutter", out=None, want_mask=False, stats=None):
     """Time-domain interference detection and blanking on int16 GPU cubes ``adc`` (n, 4, 192, 256, 2), in two launches (the rule is
     stated beside hupr_adc_interference_i16 in include/hupr.h) -> ``(cube, stats, mask)``: the filtered cube (``out``: a tensor like
-    ``adc`` to write, ``adc`` itself for in place, None for a new one), an ``InterferenceStats`` and the bit mask uint8
-    (n, 4, 192, 32) of the replaced samples (bit ``s % 8`` of byte ``s / 8``; None unless ``want_mask``).  Device tensors, no sync."""
+    ``adc`` to write, ``adc`` itself for in place, None for a new one), an ``InterferenceStats`` (``stats``: one to reuse) and the bit mask
+    uint8 (n, 4, 192, 32) of the replaced samples (bit ``s % 8`` of byte ``s / 8``; None unless ``want_mask``).  Device tensors, no sync."""
     from .preprocessing.interference import FILLS, check_interference
     K, guard, fill = check_interference(K, guard, fill)
     if not isinstance(adc, torch.Tensor) or adc.dtype != torch.int16 or adc.dim() != 5 or tuple(adc.shape[1:]) != (4, 192, 256, 2):
         raise ValueError("adc must be int16 (n,4,192,256,2), got %s %r" % (getattr(adc, "dtype", type(adc).__name__),
                                                                            tuple(getattr(adc, "shape", ()))))
+    if stats is not None and not isinstance(stats, InterferenceStats):
+        raise ValueError("stats must be an InterferenceStats or None, got %s" % type(stats).__name__)
+    n, dev = adc.shape[0], adc.device
+    out, = _outputs("adc_interference", None if out is None else (out,), (n,), dev, (((4, 192, 256, 2), torch.int16),))
+    frames, groups = _outputs("adc_interference: stats", stats and (stats.frames, stats.groups), (n,), dev, (((2,), _I32), ((12, 2), _I32)))
     if not adc.is_cuda:
         raise rt.HuprError("adc_interference needs GPU cubes (no CPU fallback), got %s" % adc.device)
-    if out is not None and (out.dtype != adc.dtype or out.shape != adc.shape or out.device != adc.device):
-        raise ValueError("out must be a tensor like adc, got %s %r on %s" % (out.dtype, tuple(out.shape), out.device))
-    n, dev = adc.shape[0], adc.device
     with torch.cuda.device(dev):
-        if out is None:
-            out = torch.empty_like(adc, memory_format=torch.contiguous_format)
-        groups = torch.empty((n, 12, 2), dtype=torch.int32, device=dev)
-        frames = torch.empty((n, 2), dtype=torch.int32, device=dev)
         mask = torch.empty((n, 4, 192, 32), dtype=torch.uint8, device=dev) if want_mask else None
-        L = rt.lib()
-        rt.check(L.hupr_adc_interference_i16(rt.ptr(adc), rt.ptr(out), n, K, guard, FILLS[fill], rt.ptr(mask), rt.ptr(groups), rt.stream()))
-        rt.check(L.hupr_adc_interference_stats(rt.ptr(groups), n, rt.ptr(frames), rt.stream()))
-    return out, InterferenceStats(frames, groups), mask
+        rt.check(rt.lib().hupr_adc_interference_i16(rt.ptr(adc), rt.ptr(out), n, K, guard, FILLS[fill], rt.ptr(mask), rt.ptr(groups), rt.stream()))
+        rt.check(rt.lib().hupr_adc_interference_stats(rt.ptr(groups), n, rt.ptr(frames), rt.stream()))
+    return out, stats or InterferenceStats(frames, groups), mask

@@ -88,15 +88,38 @@ def _tdm_table(tx_swapped, frames_per_flag, n):
     return rt.ptr(tx_swapped), tx_swapped.numel(), frames_per_flag
 
 
-def _launch_tdm(adc_iq, n, out, flags, loader, tx_swapped, frames_per_flag, ws, nbytes):
-    tbl, n_swapped, fpf = _tdm_table(tx_swapped, frames_per_flag, n)
-    rt.check(rt.lib().hupr_fft_chain_tdm(rt.ptr(adc_iq), n, rt.ptr(out), flags, loader, tbl, n_swapped, fpf, rt.ptr(ws), nbytes,
-                                         rt.stream()))
-
-
 def _refuse_swap_without_tdm(tdm_compensation, tx_swapped):
     if tx_swapped is not None and not tdm_compensation:
         raise ValueError("tx_swapped only means something with tdm_compensation=True")
+
+
+_PLAIN_ENTRIES = ("hupr_fft_chain_c64", "hupr_fft_chain_loader_f32", "hupr_fft_chain_loader_means_f32")       # by loader code
+
+
+def _chain(adc_iq, loader, shape, dtype, flags, ws, out, tdm_compensation, tx_swapped, frames_per_flag, interference):
+    """The launch behind the three public functions.  ``loader``: 0 the complex cube, 1 the loader tensor, 2 its elevation means;
+    ``shape`` and ``dtype``: the output behind the sensor-frame axis, for a new tensor or to hold a given ``out`` to before any launch
+    (functional._outputs).  With TDM compensation the entry is hupr_fft_chain_tdm, with ``flags == 0`` the plain one of ``loader``,
+    otherwise hupr_fft_chain_opts."""
+    from ..functional import _outputs
+    _check_adc(adc_iq)
+    _refuse_swap_without_tdm(tdm_compensation, tx_swapped)
+    n, dev = adc_iq.shape[0], adc_iq.device
+    out, = _outputs("fft_chain", None if out is None else (out,), (n,), dev, ((shape, dtype),))
+    adc_iq = _interference_filtered(adc_iq, interference)
+    if ws is None:
+        ws = _workspace(n, dev)[0]
+    table = _tdm_table(tx_swapped, frames_per_flag, n) if tdm_compensation else None
+    head = (rt.ptr(adc_iq), n, rt.ptr(out))
+    tail = (rt.ptr(ws), ws.numel() * ws.element_size(), rt.stream())        # the library asks only that the buffer is large enough
+    L = rt.lib()
+    if tdm_compensation:
+        rt.check(L.hupr_fft_chain_tdm(*head, flags, loader, *table, *tail))
+    elif flags == 0:
+        rt.check(getattr(L, _PLAIN_ENTRIES[loader])(*head, *tail))
+    else:
+        rt.check(L.hupr_fft_chain_opts(*head, flags, loader, *tail))
+    return out
 
 
 def fft_chain(adc_iq, ws=None, window=None, magnitude=False, zero_doppler=None, tdm_compensation=False, tx_swapped=None,
@@ -109,23 +132,8 @@ def fft_chain(adc_iq, ws=None, window=None, magnitude=False, zero_doppler=None, 
     group's transmitters 0 and 2 were exchanged (``tools.augment.adc_mirror``); None = none.  Reference-trained weights expect the
     default, off.  ``interference``: an ``InterferenceFilter`` runs the interference blanking of preprocessing/interference.py on the
     cube first (two more launches, into a new buffer: ``adc_iq`` is left as it is); None, the default, is today's launches."""
-    _check_adc(adc_iq)
-    _refuse_swap_without_tdm(tdm_compensation, tx_swapped)
-    adc_iq = _interference_filtered(adc_iq, interference)
-    n = adc_iq.shape[0]
-    flags = _flags(window, magnitude, zero_doppler)
-    out = torch.empty((n, 16, 64, 64, 8), dtype=torch.float32 if magnitude else torch.complex64, device=adc_iq.device)
-    if ws is None:
-        ws, nbytes = _workspace(n, adc_iq.device)
-    else:
-        nbytes = ws.numel() * ws.element_size()
-    if tdm_compensation:
-        _launch_tdm(adc_iq, n, out, flags, 0, tx_swapped, frames_per_flag, ws, nbytes)
-    elif flags == 0:
-        rt.check(rt.lib().hupr_fft_chain_c64(rt.ptr(adc_iq), n, rt.ptr(out), rt.ptr(ws), nbytes, rt.stream()))
-    else:
-        rt.check(rt.lib().hupr_fft_chain_opts(rt.ptr(adc_iq), n, rt.ptr(out), flags, 0, rt.ptr(ws), nbytes, rt.stream()))
-    return out
+    return _chain(adc_iq, 0, (16, 64, 64, 8), torch.float32 if magnitude else torch.complex64, _flags(window, magnitude, zero_doppler), ws,
+                  None, tdm_compensation, tx_swapped, frames_per_flag, interference)
 
 
 def fft_chain_loader(adc_iq, ws=None, out=None, window=None, zero_doppler=None, tdm_compensation=False, tx_swapped=None,
@@ -133,50 +141,19 @@ def fft_chain_loader(adc_iq, ws=None, out=None, window=None, zero_doppler=None, 
     """adc_iq: int16 GPU tensor (n,4,192,256,2) -> fp32 GPU tensor (n, 8, 2, 64, 64, 8):
     Doppler bins 4..11, re/im split, per-elevation Normalize (datasets glue fused in).  ``window`` / ``zero_doppler`` /
     ``tdm_compensation`` / ``tx_swapped`` / ``frames_per_flag`` / ``interference``: see fft_chain (the statistics are those of the
-    compensated values)."""
-    _check_adc(adc_iq)
-    _refuse_swap_without_tdm(tdm_compensation, tx_swapped)
-    adc_iq = _interference_filtered(adc_iq, interference)
-    n = adc_iq.shape[0]
-    if out is None:
-        out = torch.empty((n, 8, 2, 64, 64, 8), dtype=torch.float32, device=adc_iq.device)
-    if ws is None:
-        ws, nbytes = _workspace(n, adc_iq.device)
-    else:
-        nbytes = ws.numel() * ws.element_size()
-    flags = _flags(window, False, zero_doppler)
-    if tdm_compensation:
-        _launch_tdm(adc_iq, n, out, flags, 1, tx_swapped, frames_per_flag, ws, nbytes)
-    elif flags == 0:
-        rt.check(rt.lib().hupr_fft_chain_loader_f32(rt.ptr(adc_iq), n, rt.ptr(out), rt.ptr(ws), nbytes, rt.stream()))
-    else:
-        rt.check(rt.lib().hupr_fft_chain_opts(rt.ptr(adc_iq), n, rt.ptr(out), flags, 1, rt.ptr(ws), nbytes, rt.stream()))
-    return out
+    compensated values).  ``out``: a tensor of that shape to write."""
+    return _chain(adc_iq, 1, (8, 2, 64, 64, 8), torch.float32, _flags(window, False, zero_doppler), ws, out, tdm_compensation,
+                  tx_swapped, frames_per_flag, interference)
 
 
 def fft_chain_loader_means(adc_iq, ws=None, zero_doppler=None, tdm_compensation=False, tx_swapped=None, frames_per_flag=1,
-                           interference=None):
+                           interference=None, out=None):
     """adc_iq: int16 GPU tensor (n,4,192,256,2) -> fp32 GPU tensor (n, 16, 64, 64): the loader tensor of ``fft_chain_loader``
     averaged over its elevation axis, plane index 2 f + c — what ``HuPRNet.forward`` computes first (models/networks.py:26-27).
     The fused training loader hands these planes to the model instead of the 8x larger (n,8,2,64,64,8) tensor.
-    ``tdm_compensation`` / ``tx_swapped`` / ``frames_per_flag`` / ``interference``: see fft_chain."""
-    _check_adc(adc_iq)
-    _refuse_swap_without_tdm(tdm_compensation, tx_swapped)
-    adc_iq = _interference_filtered(adc_iq, interference)
-    n = adc_iq.shape[0]
-    out = torch.empty((n, 16, 64, 64), dtype=torch.float32, device=adc_iq.device)
-    if ws is None:
-        ws, nbytes = _workspace(n, adc_iq.device)
-    else:
-        nbytes = ws.numel() * ws.element_size()
-    flags = _flags(None, False, zero_doppler)
-    if tdm_compensation:
-        _launch_tdm(adc_iq, n, out, flags, 2, tx_swapped, frames_per_flag, ws, nbytes)
-    elif flags == 0:
-        rt.check(rt.lib().hupr_fft_chain_loader_means_f32(rt.ptr(adc_iq), n, rt.ptr(out), rt.ptr(ws), nbytes, rt.stream()))
-    else:
-        rt.check(rt.lib().hupr_fft_chain_opts(rt.ptr(adc_iq), n, rt.ptr(out), flags, 2, rt.ptr(ws), nbytes, rt.stream()))
-    return out
+    ``tdm_compensation`` / ``tx_swapped`` / ``frames_per_flag`` / ``interference``: see fft_chain; ``out``: see fft_chain_loader."""
+    return _chain(adc_iq, 2, (16, 64, 64), torch.float32, _flags(None, False, zero_doppler), ws, out, tdm_compensation, tx_swapped,
+                  frames_per_flag, interference)
 
 
 def loader_normalize(cube):

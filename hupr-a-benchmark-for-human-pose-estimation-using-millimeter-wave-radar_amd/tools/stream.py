@@ -51,6 +51,7 @@ import torch
 
 from .. import functional as F_
 from .. import runtime as rt
+from ..preprocessing import process_iwr1843 as pre
 
 ADC_SHAPE = (4, 192, 256, 2)           # one sensor-frame: rx, chirp, sample, I/Q (int16)
 WARMUP_PUSHES = 2                      # eager pose-emitting pushes in front of the capture
@@ -415,8 +416,10 @@ class PoseFrame(_OccupancyFields):
         self.interference = interference
 
     def _map(self, fn):
-        return PoseFrame(self.frame, *[None if getattr(self, k) is None else fn(getattr(self, k))
-                                       for k in PoseFrame.__slots__[1:] + _OccupancyFields.__slots__ + _InterferenceFields.__slots__])
+        """A frame of the same class with ``fn`` of every tensor: the fields are the ``__slots__`` along the MRO, and the constructors
+        take them by those names."""
+        fields = {k: getattr(self, k) for c in type(self).__mro__ for k in getattr(c, "__slots__", ())}
+        return type(self)(**{k: v if v is None or k == "frame" else fn(v) for k, v in fields.items()})
 
     def clone(self):
         return self._map(torch.clone)
@@ -448,11 +451,6 @@ class TrackedPoseFrame(_CandidateFields):
         self.covariance, self.forecast, self.status = covariance, forecast, status
         self.candidates, self.candidate_scores, self.candidate_count, self.chosen = candidates, candidate_scores, candidate_count, chosen
 
-    def _map(self, fn):
-        return TrackedPoseFrame(self.frame, *[None if getattr(self, k) is None else fn(getattr(self, k))
-                                              for k in PoseFrame.__slots__[1:] + self.__slots__ + _OccupancyFields.__slots__
-                                              + _CandidateFields.__slots__ + _InterferenceFields.__slots__])
-
 
 class PoseStream:
     """Streaming session around a HuPRNet.  ``push(adc_hori, adc_vert)`` takes the new int16 frame of both sensors,
@@ -473,8 +471,8 @@ class PoseStream:
     tracker's own ``horizon_s``.  ``decode="integral"`` decodes the mass centroid of the window of ``decode_radius`` heat-map pixels
     around the peak (None: the targets' patch radius, 6 at 64 and 9 at 128; 0: the whole map), with ``smooth`` in the same launch and
     never with ``track``.  With the defaults the session decodes exactly as before, in the same two launches.
-    ``tdm_compensation=True``: the FFT chain of every push compensates the TDM Doppler phase (``hupr_fft_chain_tdm`` with no swap
-    table, inside the same graph replay) — for weights trained with ``DATASET.tdmCompensation``.
+    ``tdm_compensation=True``: the FFT chain of every push compensates the TDM Doppler phase (``fft_chain_loader_means`` with
+    ``tdm_compensation`` and no swap table, inside the same graph replay) — for weights trained with ``DATASET.tdmCompensation``.
     ``history=True`` (needs ``track``): after every push or flush that emits a pose the tracker's state and outputs are copied into a
     history on the device (tools/smooth.py: TrackHistory) — eager device-to-device copies on the session's stream, behind the graph
     replay and not inside it — and ``smoothed()`` returns the Rauch-Tung-Striebel smoothed poses emitted since the last ``reset()``
@@ -536,8 +534,7 @@ class PoseStream:
             self._staging = torch.empty((2, lanes, 16, self.pixels), dtype=torch.float32, device=dev)
             self._ring = torch.zeros((2, lanes, G, 16, self.pixels), dtype=torch.float32, device=dev)
             self._state = torch.zeros(max(int(L.hupr_stream_state_bytes()), 16), dtype=torch.uint8, device=dev)
-            self._ws_bytes = int(L.hupr_fft_chain_ws_bytes(2 * lanes))
-            self._ws = torch.empty(max(self._ws_bytes, 16), dtype=torch.uint8, device=dev)
+            self._ws = pre._workspace(2 * lanes, dev)[0]
             act = torch.bfloat16 if self._bf16 else torch.float32
             self._maps = tuple(torch.empty((lanes, G, D.rangeSize, D.azimuthSize, 32), dtype=act, device=dev) for _ in range(2))
             self._idx = torch.empty((lanes, self.K), dtype=torch.int32, device=dev)
@@ -577,11 +574,12 @@ class PoseStream:
                 self._occ = torch.zeros((lanes, 8), dtype=torch.float32, device=dev)
                 self._gstate = F_.presence_state(lanes, dev)
                 self._present = torch.zeros(lanes, dtype=torch.int32, device=dev)
-            # interference blanking (csrc/interference.hip): the counts per group and their sums per sensor-frame
-            self._if_groups = self._if_stats = None
+            # interference blanking (csrc/interference.hip): the counts per sensor-frame and per group, the former as the frames show them
+            self._if = self._if_stats = None
             if interference is not None:
-                self._if_groups = torch.zeros((2 * lanes, 12, 2), dtype=torch.int32, device=dev)
-                self._if_stats = torch.zeros((2, lanes, 2), dtype=torch.int32, device=dev)
+                self._if = F_.InterferenceStats(torch.zeros((2 * lanes, 2), dtype=torch.int32, device=dev),
+                                                torch.zeros((2 * lanes, 12, 2), dtype=torch.int32, device=dev))
+                self._if_stats = self._if.frames.view(2, lanes, 2)
             self._done = torch.cuda.Event()
         self._graphs = {}              # "host" / "device" input -> (CUDAGraph, (heatmap, gcn_heatmap))
         self._eager_emits = 0
@@ -600,25 +598,13 @@ class PoseStream:
     def _front(self, flush, emit=True):
         """FFT chain to means on the 2 x lanes new sensor-frames (not for a flush), the window MNet, with ``presence`` the detector
         and the gate on the centre frame (only where a pose is due: ``emit``), the state advance."""
-        from ..preprocessing import process_iwr1843 as pre
         L, s = rt.lib(), rt.stream()
         if not flush:
-            f = self.interference
+            adc, f = self._adc.view((2 * self.lanes,) + ADC_SHAPE), self.interference
             if f is not None:                      # in place on the session's copy of the frames: a workgroup holds its group before it writes
-                from ..preprocessing.interference import FILLS
-                rt.check(L.hupr_adc_interference_i16(rt.ptr(self._adc), rt.ptr(self._adc), 2 * self.lanes, f.K, f.guard, FILLS[f.fill], None,
-                                                     rt.ptr(self._if_groups), s))
-                rt.check(L.hupr_adc_interference_stats(rt.ptr(self._if_groups), 2 * self.lanes, rt.ptr(self._if_stats), s))
-            flags = pre._flags(None, False, None)
-            if self.tdm_compensation:
-                rt.check(L.hupr_fft_chain_tdm(rt.ptr(self._adc), 2 * self.lanes, rt.ptr(self._staging), flags, 2, None, 0, 1,
-                                              rt.ptr(self._ws), self._ws_bytes, s))
-            elif flags == 0:
-                rt.check(L.hupr_fft_chain_loader_means_f32(rt.ptr(self._adc), 2 * self.lanes, rt.ptr(self._staging), rt.ptr(self._ws),
-                                                           self._ws_bytes, s))
-            else:
-                rt.check(L.hupr_fft_chain_opts(rt.ptr(self._adc), 2 * self.lanes, rt.ptr(self._staging), flags, 2, rt.ptr(self._ws),
-                                               self._ws_bytes, s))
+                F_.adc_interference(adc, f.K, f.guard, f.fill, out=adc, stats=self._if)
+            pre.fft_chain_loader_means(adc, ws=self._ws, out=self._staging.view(2 * self.lanes, 16, 64, 64),
+                                       tdm_compensation=self.tdm_compensation)
         ra, re = self.model.RAchirpNet.temporalConvWx1x1, self.model.REchirpNet.temporalConvWx1x1
         fn = L.hupr_mnet_stream_bf16act if self._bf16 else L.hupr_mnet_stream_f32
         rt.check(fn(None if flush else rt.ptr(self._staging), rt.ptr(self._ring), rt.ptr(self._state), self.lookahead, int(flush),
@@ -629,41 +615,27 @@ class PoseStream:
             rt.check(L.hupr_cfar_ra_stream_f32(rt.ptr(self._ring), rt.ptr(self._state), self.lookahead, int(flush), self.lanes, self.G,
                                                g.guard, g.train, rt.ptr(self._alpha), self._alpha.numel(), None, None,
                                                rt.ptr(self._occ), s))
-            rt.check(L.hupr_presence_update(rt.ptr(self._occ), self.lanes, g.min_cells, g.confirm, g.hold, rt.ptr(self._gstate),
-                                            rt.ptr(self._present), s))
+            F_.presence_update(self._occ, self._gstate, g.min_cells, g.confirm, g.hold, out=self._present)
         rt.check(L.hupr_stream_advance(rt.ptr(self._state), self.lookahead, int(flush), s))
 
     def _back(self):
         """Encoders, decoder, heads on the window maps; arg-max of the GCN head; keypoints in image pixels."""
         heat, gcn = self.model.forward_chirp_maps(*self._maps)
-        L, s = rt.lib(), rt.stream()
-        rows = self.lanes * self.K
-        if self.track is not None:
-            t = self.track
-            head = (rt.ptr(F_._c(gcn)), rows, self.H, self.W, self.ratio, int(self.decode == "subpixel"), rt.ptr(self._tstate),
-                    t.rate_hz, t.accel_psd, t.meas_std, t.heatmap_gain, t.gate, t.max_coast, t.init_speed_std, t.min_score, t.horizon_s)
-            outs = (rt.ptr(self._idx), rt.ptr(self._mx), rt.ptr(self._raw), rt.ptr(self._kp), rt.ptr(self._vel), rt.ptr(self._cov),
-                    rt.ptr(self._fc), rt.ptr(self._status))
-            if t.associates:                           # the presence launches of _front precede this one on the same stream
-                present = self._present if t.gate_on_presence else None
-                rt.check(L.hupr_pose_track_assoc_f32(*head, t.candidates, t.min_separation, t.peak_ratio, rt.ptr(present), self.K,
-                                                     *outs, rt.ptr(self._cxy), rt.ptr(self._cscore), rt.ptr(self._ccount),
-                                                     rt.ptr(self._chosen), s))
-            else:
-                rt.check(L.hupr_pose_track_f32(*head, *outs, s))
-            return heat, gcn
-        if self._fused:
-            f = self.smooth
-            params = (0.0,) * 5 if f is None else (f.rate_hz, f.min_cutoff, f.beta, f.d_cutoff, f.min_score)
-            integral = self.decode == "integral"
-            fn = L.hupr_pose_decode_integral_f32 if integral else L.hupr_pose_decode_f32
-            mode = self.decode_radius if integral else int(self.decode == "subpixel")      # the sixth argument: radius / refine
-            rt.check(fn(rt.ptr(F_._c(gcn)), rows, self.H, self.W, self.ratio, mode, rt.ptr(self._fstate), *params, rt.ptr(self._idx),
-                        rt.ptr(self._mx), rt.ptr(self._kp if f is None else self._raw), rt.ptr(None if f is None else self._kp),
-                        rt.ptr(self._vel), s))
-            return heat, gcn
-        rt.check(L.hupr_argmax_rows_f32(rt.ptr(F_._c(gcn)), rows, self.H * self.W, rt.ptr(self._idx), rt.ptr(self._mx), s))
-        rt.check(L.hupr_stream_keypoints_f32(rt.ptr(self._idx), rt.ptr(self._mx), rt.ptr(self._kp), rows, self.W, self.ratio, s))
+        rows, t, f = self.lanes * self.K, self.track, self.smooth
+        maps, refine = gcn.reshape(self.lanes, self.K, self.H, self.W), self.decode == "subpixel"
+        # without a filter the decoded keypoints are the emitted ones (_kp); with one, _raw beside the filtered _kp and its velocity
+        out = (self._idx, self._mx, self._kp, None, None) if self._raw is None else (self._idx, self._mx, self._raw, self._kp, self._vel)
+        if t is not None:                              # the presence launches of _front precede this one on the same stream
+            out += (self._cov, self._fc, self._status) + ((self._cxy, self._cscore, self._ccount, self._chosen) if t.associates else ())
+            F_.pose_track(maps, self.ratio, refine, self._tstate, t, self._present if t.gate_on_presence else None, out=out)
+        elif self.decode == "integral":
+            F_.pose_decode_integral(maps, self.ratio, self.decode_radius, self._fstate, f, out=out)
+        elif self._fused:
+            F_.pose_decode(maps, self.ratio, refine, self._fstate, f, out=out)
+        else:
+            F_.argmax_rows(maps.view(rows, self.H * self.W), out=(self._idx.view(rows), self._mx.view(rows)))
+            rt.check(rt.lib().hupr_stream_keypoints_f32(rt.ptr(self._idx), rt.ptr(self._mx), rt.ptr(self._kp), rows, self.W, self.ratio,
+                                                        rt.stream()))
         return heat, gcn
 
     def _capture(self, kind):
@@ -685,12 +657,13 @@ class PoseStream:
     def _frame(self, center, out, pushed=True):
         if self._history is not None:                          # the emitted pose into the history: eager copies behind the launches
             self._history.append(self._tstate, self._status, self._kp, self._raw, self._mx)
-        if self.track is not None:
-            return TrackedPoseFrame(center, self._kp, self._mx, self._idx, out[0], out[1], self._raw, self._vel, self._cov, self._fc,
-                                    self._status, self._present, self._occ, self._cxy, self._cscore, self._ccount, self._chosen,
-                                    self._if_stats if pushed else None)
-        return PoseFrame(center, self._kp, self._mx, self._idx, out[0], out[1], self._raw, self._vel, self._present, self._occ,
-                         self._if_stats if pushed else None)
+        fields = dict(frame=center, keypoints=self._kp, scores=self._mx, indices=self._idx, heatmap=out[0], gcn_heatmap=out[1],
+                      raw_keypoints=self._raw, velocity=self._vel, present=self._present, occupancy=self._occ,
+                      interference=self._if_stats if pushed else None)
+        if self.track is None:
+            return PoseFrame(**fields)
+        return TrackedPoseFrame(covariance=self._cov, forecast=self._fc, status=self._status, candidates=self._cxy,
+                                candidate_scores=self._cscore, candidate_count=self._ccount, chosen=self._chosen, **fields)
 
     # -- public ---------------------------------------------------------------------------------------------------------------
     def push(self, adc_hori, adc_vert):
@@ -826,42 +799,27 @@ def parse(argv=None):
         p.error("--decode-radius needs --decode integral")
     if args.decode_radius is not None and args.decode_radius < 0:
         p.error("--decode-radius must be 0 (the whole map) or a positive number of heat-map pixels")
-    if not args.track:
-        for flag, given in (("--predict-now", args.predict_now), ("--accel-psd", args.accel_psd is not None),
-                            ("--gate", args.gate is not None), ("--max-coast", args.max_coast is not None), ("--rts", args.rts),
-                            ("--track-candidates", args.track_candidates is not None),
-                            ("--track-separation", args.track_separation is not None),
-                            ("--track-peak-ratio", args.track_peak_ratio is not None), ("--track-on-presence", args.track_on_presence)):
-            if given:
-                p.error("%s needs --track" % flag)
-    else:
-        if args.track_on_presence and not args.presence:
-            p.error("--track-on-presence needs --presence")
-        try:
-            tracking_from_args(args)
-        except TrackingError as e:
-            p.error(str(e))
-    if not args.presence:
-        for flag, dest in PRESENCE_FLAGS:
-            if getattr(args, dest) is not None:
-                p.error("%s needs --presence" % flag)
-    else:
-        try:
-            presence_from_args(args)
-        except PresenceError as e:
-            p.error(str(e))
-    if not args.interference:
-        for flag, dest in INTERFERENCE_FLAGS:
-            if getattr(args, dest) is not None:
-                p.error("%s needs --interference" % flag)
-    else:
-        try:
-            interference_from_args(args)
-        except ValueError as e:
-            p.error(str(e))
+    if args.track and args.track_on_presence and not args.presence:
+        p.error("--track-on-presence needs --presence")
+    # a dependent flag (given: neither None nor False) needs its switch; with the switch the settings object must build
+    for switch, flags, build, error in (("--track", TRACK_FLAGS, tracking_from_args, TrackingError),
+                                        ("--presence", PRESENCE_FLAGS, presence_from_args, PresenceError),
+                                        ("--interference", INTERFERENCE_FLAGS, interference_from_args, ValueError)):
+        if not getattr(args, switch[2:]):
+            for flag, dest in flags:
+                if getattr(args, dest) is not None and getattr(args, dest) is not False:
+                    p.error("%s needs %s" % (flag, switch))
+        else:
+            try:
+                build(args)
+            except error as e:
+                p.error(str(e))
     return args
 
 
+TRACK_FLAGS = (("--predict-now", "predict_now"), ("--accel-psd", "accel_psd"), ("--gate", "gate"), ("--max-coast", "max_coast"),
+               ("--rts", "rts"), ("--track-candidates", "track_candidates"), ("--track-separation", "track_separation"),
+               ("--track-peak-ratio", "track_peak_ratio"), ("--track-on-presence", "track_on_presence"))
 INTERFERENCE_FLAGS = (("--interference-threshold", "interference_threshold"), ("--interference-guard", "interference_guard"),
                       ("--interference-fill", "interference_fill"))
 
@@ -921,7 +879,6 @@ def load_model_best(model, log_dir, device, weights="live", tdm_compensation=Fal
     ``preprocess.json`` says the weights were trained with; ``interference`` (None or an InterferenceFilter) likewise."""
     if weights not in WEIGHTS:
         raise ValueError("weights must be one of %s, got %r" % (", ".join(WEIGHTS), weights))
-    from ..preprocessing import process_iwr1843 as pre
     path = os.path.join(log_dir, "model_best.pth")
     if not os.path.exists(path):
         raise FileNotFoundError("%s not found" % path)

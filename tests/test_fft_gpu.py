@@ -297,3 +297,26 @@ def test_zero_doppler_plane_conventions():
     assert torch.isfinite(old_ld).all() and (o4.std(2, unbiased=True) - 1).abs().max().item() < 1e-3
     with pytest.raises(ValueError):
         preprocessing.fft_chain(dev, zero_doppler="noise")
+
+
+@pytest.mark.parametrize("tdm", [False, True], ids=["plain", "tdm"])
+def test_loader_means_and_interference_write_into_the_caller_s_buffers(tdm):
+    """``fft_chain_loader_means(out=...)`` and ``adc_interference(out=adc, stats=...)`` on two sensor-frames: the given tensors come
+    back, holding the bits of the allocating calls (what the live stream's persistent buffers rely on)."""
+    from hupr_amd import functional as F_, preprocessing
+    dev = torch.from_numpy(synth.adc_cube_int16(0, nframes=2)).cuda()
+    want = preprocessing.fft_chain_loader_means(dev, tdm_compensation=tdm)
+    ws = torch.empty(preprocessing.process_iwr1843._workspace(2, dev.device)[1] + 512, dtype=torch.uint8, device="cuda")   # larger than asked
+    out = torch.full_like(want, 77.0)
+    got = preprocessing.fft_chain_loader_means(dev, ws=ws, out=out, tdm_compensation=tdm)
+    assert got is out and torch.equal(out, want) and want.abs().max().item() > 0
+    if tdm:
+        assert not torch.equal(want, preprocessing.fft_chain_loader_means(dev))
+    # K = 2, the most sensitive threshold, so that the counts are not zero on a clean synthetic cube
+    cube, stats, _ = F_.adc_interference(dev, 2, 8, "clutter")
+    assert stats.frames.any().item()
+    mine = F_.InterferenceStats(torch.full_like(stats.frames, 77), torch.full_like(stats.groups, 77))
+    frames, groups, adc = mine.frames, mine.groups, dev.clone()
+    got_cube, got_stats, mask = F_.adc_interference(adc, 2, 8, "clutter", out=adc, stats=mine)
+    assert got_cube is adc and got_stats is mine and mask is None and mine.frames is frames and mine.groups is groups
+    assert torch.equal(adc, cube) and torch.equal(frames, stats.frames) and torch.equal(groups, stats.groups)

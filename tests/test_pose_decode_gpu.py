@@ -1,6 +1,7 @@
 """GPU (-m gpu): hupr_pose_decode_f32 (csrc/pose_decode.hip) — arg-max, sub-pixel refinement, One-Euro filter — against an fp64 NumPy
 statement of the rule in include/hupr.h, written here (the reference project has no such decode), and the host-decode path built on
-it (misc.metrics.get_final_preds, TEST.decode).
+it (misc.metrics.get_final_preds, TEST.decode).  Section 8: every wrapper that takes ``out=`` (the decodes, the tracker, arg-max, the
+presence gate) writes the allocating call's bits into the caller's buffers, in one launch and without an allocation.
 
 Bounds.  Positions: 1e-3 heat-map pixel.  With inputs >= 1e-3 the logs are below 8 in magnitude, so a 2-ulp logf error is <= 1e-6;
 the gradient error is then <= 1e-6, the Hessian error <= 4e-6, and with the smallest Hessian eigenvalue >= 0.02 the offset error is
@@ -350,3 +351,69 @@ def test_get_final_preds_and_test_decode():
     dev = LossComputer(sub, "cuda").computeLoss((p1, p2), gt, decode="device")[2]
     idx, mxs = F_.argmax_rows(heat.reshape(28, 64 * 64))
     assert torch.equal(dev[0], idx) and torch.equal(dev[1], mxs)
+
+
+# ---- 8: out= — the wrappers write into buffers the caller owns --------------------------------------------------------------------------------
+def _out_cases():
+    """name -> (state factory or None, call(heat, state, out)) for every wrapper that takes ``out``: the two decodes with and without
+    a filter, the tracker on its two entries, the row arg-max, the presence gate.  No call allocates an input of its own."""
+    from hupr_amd import functional as F_
+    from hupr_amd.tools import PoseSmoothing, PoseTracking
+    sm = PoseSmoothing(10.0, min_score=0.1)
+    track = lambda **kw: PoseTracking(10.0, min_score=0.1, horizon_s=0.2, **kw)
+    present = torch.tensor([1, 0], dtype=torch.int32, device="cuda")
+    summary = torch.zeros((2, 8), dtype=torch.float32, device="cuda")           # the gate reads column 0, the detection count
+    summary[0, 0] = 5.0                                                          # lane 0 is a hit, lane 1 a miss
+    cases = {}
+    for refine in (0, 1):
+        cases["pose_decode refine=%d" % refine] = (None, lambda h, s, out, r=refine: F_.pose_decode(h, 4.0, refine=bool(r), out=out))
+        cases["pose_decode refine=%d filter" % refine] = (F_.pose_filter_state, lambda h, s, out, r=refine: F_.pose_decode(
+            h, 4.0, refine=bool(r), filter_state=s, smoothing=sm, out=out))
+    for radius in (2, 0):
+        cases["pose_decode_integral radius=%d" % radius] = (None, lambda h, s, out, r=radius: F_.pose_decode_integral(h, 4.0, r, out=out))
+        cases["pose_decode_integral radius=%d filter" % radius] = (F_.pose_filter_state, lambda h, s, out, r=radius: F_.pose_decode_integral(
+            h, 4.0, r, filter_state=s, smoothing=sm, out=out))
+    cases["pose_track"] = (F_.pose_track_state, lambda h, s, out: F_.pose_track(h, 4.0, track_state=s, tracking=track(), out=out))
+    cases["pose_track candidates=2"] = (F_.pose_track_state, lambda h, s, out: F_.pose_track(h, 4.0, track_state=s,
+                                                                                           tracking=track(candidates=2), out=out))
+    cases["pose_track present"] = (F_.pose_track_state, lambda h, s, out: F_.pose_track(h, 4.0, track_state=s, tracking=track(),
+                                                                                      present=present, out=out))
+    cases["argmax_rows"] = (None, lambda h, s, out: F_.argmax_rows(h.view(6, 64), out=out))
+    cases["presence_update"] = (lambda rows, dev: F_.presence_state(2, dev), lambda h, s, out: F_.presence_update(
+        summary, s, min_cells=3, confirm=1, hold=0, out=out))
+    return cases
+
+
+@pytest.mark.parametrize("name", ["pose_decode refine=0", "pose_decode refine=0 filter", "pose_decode refine=1", "pose_decode refine=1 filter",
+                                  "pose_decode_integral radius=2", "pose_decode_integral radius=2 filter", "pose_decode_integral radius=0",
+                                  "pose_decode_integral radius=0 filter", "pose_track", "pose_track candidates=2", "pose_track present",
+                                  "argmax_rows", "presence_update"])
+def test_out_buffers_get_the_allocating_call_s_bits_in_one_launch_and_no_allocation(name):
+    """Once allocating, once into sentinel-filled buffers with a clone of the same (already advanced) state: the same bits, the same
+    advanced state, the caller's own tensors back, one launch, and not a byte allocated on the device."""
+    from hupr_amd import runtime as rt
+    new_state, call = _out_cases()[name]
+    rng = np.random.RandomState(11)
+    warm, heat = (torch.from_numpy(rng.uniform(0.0, 1.0, (2, 3, 8, 8)).astype(np.float32)).cuda() for _ in range(2))
+    s1 = s2 = None
+    if new_state is not None:
+        s1 = new_state(6, "cuda")
+        call(warm, s1, None)                                                     # a state that has seen a frame
+        s2 = s1.clone()
+    want = call(heat, s1, None)
+    single = isinstance(want, torch.Tensor)                                      # presence_update returns its one tensor bare
+    want = (want,) if single else want
+    assert any(t is not None and t.any().item() for t in want)
+    bufs = tuple(None if t is None else torch.full_like(t, 77) for t in want)
+    torch.cuda.synchronize()
+    L = rt.lib()
+    n0, m0 = L.hupr_launch_count(), torch.cuda.memory_allocated()
+    got = call(heat, s2, bufs[0] if single else bufs)
+    assert L.hupr_launch_count() - n0 == 1 and torch.cuda.memory_allocated() == m0
+    got = (got,) if single else got
+    assert len(got) == len(want)
+    for k, (g, b, w) in enumerate(zip(got, bufs, want)):
+        assert g is b, k
+        assert (g is None and w is None) or (g.dtype == w.dtype and torch.equal(g, w)), k
+    if s1 is not None:
+        assert torch.equal(s1, s2) and s1.any().item()

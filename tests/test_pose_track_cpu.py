@@ -168,6 +168,21 @@ def test_tracked_pose_frame_is_a_pose_frame_with_three_more_fields():
     assert TrackedPoseFrame.STATUS[ref.LOST] == "LOST" and TrackedPoseFrame.STATUS[ref.UPDATED] == "UPDATED"
     # the base class still constructs positionally, without the new fields
     assert type(PoseFrame(3, *t[:7]).clone()) is PoseFrame
+    # cpu() and clone() round-trip every field of the class, whatever base class declares it, None included
+    fields = [k for c in TrackedPoseFrame.__mro__ for k in getattr(c, "__slots__", ())]
+    assert sorted(fields) == sorted(PoseFrame.__slots__ + TrackedPoseFrame.__slots__ + ("present", "occupancy", "interference", "candidates",
+                                                                                        "candidate_scores", "candidate_count", "chosen"))
+    full = TrackedPoseFrame(7, *t, present=torch.ones(1, dtype=torch.int32), occupancy=torch.full((1, 8), 2.0),
+                            candidates=torch.full((1, 2, 2), 7.0), candidate_scores=torch.full((1, 2), 8.0),
+                            candidate_count=torch.full((1,), 2, dtype=torch.int32), chosen=torch.full((1,), -1, dtype=torch.int32),
+                            interference=torch.full((2, 1, 2), 9, dtype=torch.int32))
+    for src in (pf, full):
+        for c in (src.cpu(), src.clone()):
+            assert type(c) is TrackedPoseFrame and c.frame == src.frame
+            for k in fields:
+                a, b = getattr(src, k), getattr(c, k)
+                assert a == b if k == "frame" else (a is None and b is None) or (torch.equal(a, b) and a.dtype == b.dtype), k
+    assert pf.cpu().chosen is None and pf.cpu().interference is None and full.cpu().chosen is not None
 
 
 def test_stream_command_tracking_arguments():
