@@ -387,8 +387,15 @@ __global__ __launch_bounds__(256) void hupr_k_doppler_range(const int16_t* __res
                 else acc[k1] = pk_cfma_s(acc[k1], x[4 * g + q], (v2f){w64re(n2 * d), w64im(n2 * d)});
             }
     }
-    if constexpr (WIN == 0)                              // exact clutter removal, see above: acc[0] holds the exact chirp sum
+    // The zero-Doppler rule (include/hupr.h).  Without the Doppler window bin 0 is analytically zero — the range window commutes with
+    // the chirp mean — and takes the convention of the call whatever the range window: exactly zero, or the UNWINDOWED dither of the
+    // exact chirp sum.  WIN == 0: acc[0] holds that sum (exact clutter removal, see above).  WIN == 1: acc[0] holds the fp32 residue of
+    // sum_c fl((x_c - mean) w), which is dropped; 64 * mean is the sum again (at most 64 int16 values: exact in fp32, 1 / 64 a power
+    // of two).  With the Doppler window the bin is honest leakage and stays as computed: the convention flags do not reach it.
+    if constexpr (WIN == 0)
         acc[0] = zd_exact ? (v2f){0.f, 0.f} : zero_doppler_dither(acc[0], vant, tid);
+    else if constexpr ((WIN & 2) == 0)
+        acc[0] = zd_exact ? (v2f){0.f, 0.f} : zero_doppler_dither(mean * 64.0f, vant, tid);
 #pragma unroll
     for (int k1 = 0; k1 < 16; ++k1) {
         const int i = (k1 < 8) ? k1 + 8 : k1 - 8;        // fftshift + keep 24..39 -> i = (d + 8) & 63

@@ -84,7 +84,15 @@ int hupr_fft_chain_loader_means_f32(const int16_t* adc_iq, int n_sf, float* mean
  *      bit for bit by oracle/fft_chain.py::zero_doppler_dither), transformed and normalised like every other bin.
  *        HUPR_FFT_ZERO_DOPPLER_EXACT  the bin is exactly 0 (round 3's behaviour; the loader epilogues then emit zeros in f = 4)
  *        HUPR_FFT_RANGE_FIRST         the range-first order of rounds 1-2 (the reference's order of operations in fp32: the bin
- *                                     holds that order's own fp32 rounding residue, ~1e-7 relative); slower (2.6 vs 4 TB/s) */
+ *                                     holds that order's own fp32 rounding residue, ~1e-7 relative); slower (2.6 vs 4 TB/s)
+ *      Under a window, in the default (Doppler-first) order:
+ *        no Doppler window (no window at all, or HUPR_FFT_HANN_RANGE alone)  the bin is still analytically zero (the range window
+ *                 commutes with the chirp mean) and follows the convention: by default the SAME unwindowed dither as without a
+ *                 window, under HUPR_FFT_ZERO_DOPPLER_EXACT exactly 0, and the loader epilogues then emit zeros in f = 4;
+ *        HUPR_FFT_HANN_DOPPLER (alone or with HUPR_FFT_HANN_RANGE)  the window un-nulls the bin: index 8 is ordinary leakage of the
+ *                 neighbouring bins, computed like every other bin.  HUPR_FFT_ZERO_DOPPLER_EXACT is accepted and has NO effect on it,
+ *                 and no dither is inserted (a process-wide convention must not make a windowed call fail);
+ *        HUPR_FFT_RANGE_FIRST  as without a window: whatever that order's arithmetic leaves. */
 #define HUPR_FFT_HANN_RANGE 1
 #define HUPR_FFT_HANN_DOPPLER 2
 #define HUPR_FFT_MAGNITUDE 4
