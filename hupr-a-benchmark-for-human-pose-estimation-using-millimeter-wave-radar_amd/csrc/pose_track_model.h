@@ -1,7 +1,8 @@
 // The constant-velocity model shared by the Kalman tracker (pose_track.hip), the tracker that picks its measurement among several
-// heat-map peaks (pose_assoc.hip) and the Rauch-Tung-Striebel smoother that runs backwards over their recorded states
-// (pose_smooth.hip).  The status codes are the HUPR_TRACK_* / HUPR_SMOOTH_* of include/hupr.h.  The two trackers share one statement
-// of the filter: the measurement read off the heat-map, predict, gate, Joseph update, the end of the frame and its stores.
+// heat-map peaks (pose_assoc.hip), the one that assigns left / right partner rows jointly (pose_pairs.hip) and the Rauch-Tung-Striebel
+// smoother that runs backwards over their recorded states (pose_smooth.hip).  The status codes are the HUPR_TRACK_* / HUPR_SMOOTH_*
+// of include/hupr.h.  The trackers share one statement of the filter: the measurement read off the heat-map, predict, gate, Joseph
+// update, the end of the frame and its stores.
 #pragma once
 #include "hupr_common.h"
 #include "pose_refine.h"

@@ -2064,6 +2064,32 @@ def check_peaks(K, min_separation, peak_ratio, name="pose_peaks"):
     return int(K), int(min_separation), float(peak_ratio)
 
 
+MAX_GROUP_ROWS = 32                 # joints in a group of the pair tracker (hupr_pose_track_pairs_f32)
+
+
+def check_pair_table(pairs, swap_cost, group, name="pose_track"):
+    """The two pair-tracker settings, checked in ``name``'s name for groups of ``group`` rows -> (the partner table as a list of
+    ``group`` ints: entry j the partner of joint j or j itself, its own inverse; float swap_cost >= 0, finite)."""
+    if not 1 <= group <= MAX_GROUP_ROWS:
+        raise ValueError("%s pairs joints inside groups of 1..%d rows (the last lead axis of the heat-maps), got %d"
+                         % (name, MAX_GROUP_ROWS, group))
+    try:
+        table = list(pairs)
+    except TypeError:
+        raise ValueError("%s with pair_swap needs tracking.pairs, one partner per joint of the group of %d, got %r"
+                         % (name, group, pairs)) from None
+    if len(table) != group:
+        raise ValueError("%s needs one tracking.pairs entry per joint of the group of %d, got %d" % (name, group, len(table)))
+    for j, q in enumerate(table):
+        if isinstance(q, bool) or not isinstance(q, (int, np.integer)) or not 0 <= q < group or table[q] != j:
+            raise ValueError("%s: tracking.pairs[%d] = %r: every entry is a joint of the group, and the partner's partner is the joint "
+                             "itself" % (name, j, q))
+    if (isinstance(swap_cost, bool) or not isinstance(swap_cost, (int, float, np.integer, np.floating))
+            or not 0 <= swap_cost <= 3.0e38):                                           # finite as an fp32 launch argument
+        raise ValueError("%s needs a finite swap_cost >= 0, got %r" % (name, swap_cost))
+    return [int(q) for q in table], float(swap_cost)
+
+
 def pose_peaks(heat, ratio, K, min_separation=3, peak_ratio=0.25, refine=True):
     """heat (..., H, W) fp32 GPU -> (positions (..., K, 2) in image pixels, scores (..., K), pixel indices int32 (..., K), count int32
     (...)): the up to ``K`` <= 4 peaks of every map that the associating tracker chooses among, in one launch and without a tracker
@@ -2089,7 +2115,11 @@ def pose_track(heat, ratio, refine=True, track_state=None, tracking=None, presen
     group of joints, 0 = nobody there, the group has no measurement in this frame), the launch is the associating tracker's
     (csrc/pose_assoc.hip, hupr_pose_track_assoc_f32): it reads ``tracking.candidates``, ``min_separation`` and ``peak_ratio`` too and
     returns the eight outputs plus (candidate positions (..., K, 2), candidate scores (..., K), candidate count int32 (...), chosen
-    int32 (...), -1 where no measurement went into the state).  ``out``: the returned 8- or 12-tuple, to write (``_outputs``)."""
+    int32 (...), -1 where no measurement went into the state).  ``out``: the returned 8- or 12-tuple, to write (``_outputs``).
+    With ``tracking.pair_swap`` the launch is the pair tracker's (csrc/pose_pairs.hip, hupr_pose_track_pairs_f32): the last lead axis
+    of ``heat`` is the group of joints, ``tracking.pairs`` names every joint's partner in it (itself for a joint without one) and
+    ``tracking.swap_cost`` prices a peak from the partner's map; partner rows share the peaks of both maps.  It returns those twelve
+    plus source int32 (...): 0 the measurement came from the row's own map, 1 from its partner's, -1 none; ``out`` is that 13-tuple."""
     heat, lead, rows, H, W = _pose_heat("pose_track", heat)
     if track_state is None or tracking is None:
         raise ValueError("pose_track needs its track_state and its tracking parameters")
@@ -2101,7 +2131,8 @@ def pose_track(heat, ratio, refine=True, track_state=None, tracking=None, presen
     params = tuple(int(getattr(tracking, k)) if k == "max_coast" else float(getattr(tracking, k)) for k in _TRACK_PARAMS)
     slots = (((), _I32), ((), _F32)) + (((2,), _F32),) * 3 + (((3,), _F32), ((2,), _F32), ((), _I32))
     K = getattr(tracking, "candidates", 1)
-    if K == 1 and present is None:
+    paired = getattr(tracking, "pair_swap", False)
+    if K == 1 and present is None and not paired:
         out = _outputs("pose_track", out, lead, heat.device, slots)
         rt.check(rt.lib().hupr_pose_track_f32(rt.ptr(heat), rows, H, W, float(ratio), int(bool(refine)), rt.ptr(track_state), *params,
                                               *map(rt.ptr, out), rt.stream()))
@@ -2116,9 +2147,18 @@ def pose_track(heat, ratio, refine=True, track_state=None, tracking=None, presen
         if present.device != heat.device:
             raise ValueError("present is on %s, the heat-maps on %s" % (present.device, heat.device))
         group = lead[-1] if lead else 1
-    out = _outputs("pose_track", out, lead, heat.device, slots + (((K, 2), _F32), ((K,), _F32), ((), _I32), ((), _I32)))
-    rt.check(rt.lib().hupr_pose_track_assoc_f32(rt.ptr(heat), rows, H, W, float(ratio), int(bool(refine)), rt.ptr(track_state), *params,
-                                                K, sep, floor, rt.ptr(present), group, *map(rt.ptr, out), rt.stream()))
+    slots += (((K, 2), _F32), ((K,), _F32), ((), _I32), ((), _I32))
+    if not paired:
+        out = _outputs("pose_track", out, lead, heat.device, slots)
+        rt.check(rt.lib().hupr_pose_track_assoc_f32(rt.ptr(heat), rows, H, W, float(ratio), int(bool(refine)), rt.ptr(track_state),
+                                                    *params, K, sep, floor, rt.ptr(present), group, *map(rt.ptr, out), rt.stream()))
+        return out
+    group = lead[-1] if lead else 1
+    table, swap_cost = check_pair_table(getattr(tracking, "pairs", None), getattr(tracking, "swap_cost", 0.0), group, "pose_track")
+    out = _outputs("pose_track", out, lead, heat.device, slots + (((), _I32),))
+    rt.check(rt.lib().hupr_pose_track_pairs_f32(rt.ptr(heat), rows, H, W, float(ratio), int(bool(refine)), rt.ptr(track_state), *params,
+                                                K, sep, floor, rt.ptr(present), group, (ctypes.c_int * group)(*table), swap_cost,
+                                                *map(rt.ptr, out), rt.stream()))
     return out
 
 

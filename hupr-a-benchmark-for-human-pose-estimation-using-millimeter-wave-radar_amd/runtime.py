@@ -65,6 +65,10 @@ SIGNATURES = {
     "hupr_pose_track_assoc_f32": (c_int, [c_void_p, c_long, c_int, c_int, c_float, c_int, c_void_p] + [c_float] * 5 + [c_int] +
                                   [c_float] * 3 + [c_int, c_int, c_float, c_void_p, c_int] + [c_void_p] * 13),
     "hupr_pose_peaks_f32": (c_int, [c_void_p, c_long, c_int, c_int, c_float, c_int, c_int, c_int, c_float] + [c_void_p] * 5),
+    # the associating tracker with left / right partner rows assigned jointly (csrc/pose_pairs.hip); the partner table is host memory
+    "hupr_pose_track_pairs_f32": (c_int, [c_void_p, c_long, c_int, c_int, c_float, c_int, c_void_p] + [c_float] * 5 + [c_int] +
+                                  [c_float] * 3 + [c_int, c_int, c_float, c_void_p, c_int, ctypes.POINTER(c_int), c_float] +
+                                  [c_void_p] * 14),
     # Rauch-Tung-Striebel smoother over a recorded run of the tracker (csrc/pose_smooth.hip)
     "hupr_pose_smooth_rts_f32": (c_int, [c_void_p] * 3 + [c_long, c_long, c_float, c_float] + [c_void_p] * 5),
     # scene occupancy: CA-CFAR detection on the mean planes and the presence gate (csrc/cfar.hip); the table of the first two is host memory

@@ -2,7 +2,8 @@ from .optim import FusedAdam, FusedSGD  # noqa: F401
 
 _STREAM = ("PoseStream", "PoseFrame", "StreamSchedule", "stream_window_sources", "StreamError", "LookaheadError",
            "FrameShapeError", "FrameDtypeError", "StreamEndedError", "PoseSmoothing", "DecodeError", "SmoothingError",
-           "PoseTracking", "TrackedPoseFrame", "TrackingError", "PresenceGate", "PresenceError", "InterferenceError")
+           "PoseTracking", "TrackedPoseFrame", "PairedPoseFrame", "TrackingError", "PresenceGate", "PresenceError",
+           "InterferenceError")
 _SMOOTH = ("SequenceSmoother", "SmoothedSequence", "TrackHistory", "jitter")
 
 

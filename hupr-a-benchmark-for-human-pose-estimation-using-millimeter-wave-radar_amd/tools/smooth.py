@@ -102,7 +102,8 @@ class TrackHistory:
 
 class SequenceSmoother:
     """A tracker (``functional.pose_track`` on a state of its own) that remembers: ``track(heat, ratio, refine)`` is one frame of
-    ``rows`` heat-maps and returns ``pose_track``'s tuple (with ``tracking.candidates`` > 1 the associating tracker's twelve);
+    ``rows`` heat-maps and returns ``pose_track``'s tuple (with ``tracking.candidates`` > 1 the associating tracker's twelve, with
+    ``tracking.pair_swap`` — whose ``pairs`` must then fit the ``rows`` joints of a frame — those and ``source``);
     ``new_sequence()`` zeroes the state, so that the next frame starts new tracks and the smoother's chain breaks there by itself;
     ``smooth()`` smooths everything tracked so far in one launch."""
 
@@ -113,6 +114,9 @@ class SequenceSmoother:
             raise TrackingError("PoseTracking.gate_on_presence needs a live session with presence: there is no gate to ask here")
         if isinstance(rows, bool) or not isinstance(rows, (int, np.integer)) or rows < 1:
             raise ValueError("rows must be a positive integer, got %r" % (rows,))
+        if tracking.pair_swap and (tracking.pairs is None or len(tracking.pairs) != rows):
+            raise TrackingError("PoseTracking.pair_swap needs pairs for the %d rows of a frame (PoseTracking.for_joints), got %r"
+                                % (rows, tracking.pairs))
         self.tracking, self.rows, self.device = tracking, int(rows), torch.device(device)
         self.state = F_.pose_track_state(self.rows, self.device)
         self.history = TrackHistory((self.rows,), self.device)
@@ -187,12 +191,14 @@ def temporal_setting(cfg):
         if not hasattr(kw, "__dict__") or isinstance(kw, type):
             raise ValueError("TEST.tracking must be a mapping of PoseTracking arguments, got %r" % (kw,))
         kw = vars(kw)
-    known = tuple(k for k in PoseTracking.ARGUMENTS if k != "rate_hz")
+    known = tuple(k for k in PoseTracking.ARGUMENTS + PoseTracking.PAIR_ARGUMENTS if k != "rate_hz")
     for k in kw:
         if k not in known:
             raise ValueError("TEST.tracking.%s is no PoseTracking argument (%s; the rate is TEST.temporalRate)" % (k, ", ".join(known)))
     try:
         tracking = PoseTracking(float(rate), **dict(kw))
+        if tracking.pair_swap:                          # the partner table of this config's joints (None: their L_* / R_* names)
+            tracking = tracking.for_joints(cfg.DATASET.idxToJoints)
     except TrackingError as e:
         raise ValueError("TEST.tracking: %s" % e) from None
     if mode == "off":

@@ -22,7 +22,8 @@ the device; either replaces the two decode launches by one (csrc/pose_decode.hip
 outliers are gated, drop-outs coast on the track's velocity, every joint carries a covariance and a forecast.  With
 ``PoseTracking(candidates=C)``, C > 1, the track chooses its measurement among up to C peaks of the heat-map instead of taking the
 strongest (csrc/pose_assoc.hip, one launch in the tracker's place), and ``gate_on_presence=True`` takes the measurement away where the
-presence gate sees nobody.
+presence gate sees nobody.  ``PoseTracking(pair_swap=True)`` assigns the left / right partners of the skeleton jointly, each pair
+sharing the peaks of both its maps (csrc/pose_pairs.hip, one launch likewise): a left / right exchange by the network is followed.
 ``decode="integral"`` decodes the mass centroid of the window of ``decode_radius`` pixels around the peak (default: the targets' patch
 radius; 0: the whole map) — what the integral coordinate loss trains — in one launch of csrc/pose_integral.hip in place of the two,
 ``smooth`` included; it does not combine with ``track``, whose measurement is pinned to the sub-pixel decode.
@@ -31,7 +32,8 @@ radius; 0: the whole map) — what the integral coordinate loss trains — in on
                                     [--lookahead N] [--math f32|bf16] [--no-graph] [--out poses.json]
                                     [--decode argmax|subpixel|integral [--decode-radius N]] [--smooth --rate FPS]
                                     [--track --rate FPS [--predict-now] [--accel-psd Q] [--gate D2] [--max-coast N] [--rts]
-                                     [--track-candidates N] [--track-separation N] [--track-peak-ratio X] [--track-on-presence]]
+                                     [--track-candidates N] [--track-separation N] [--track-peak-ratio X] [--track-on-presence]
+                                     [--track-pairs [--track-swap-cost X]]]
                                     [--presence [--pfa X] [--cfar-guard N] [--cfar-train N] [--min-cells N] [--confirm N] [--hold N]]
 
 ``presence=PresenceGate(...)`` / ``--presence``: scene occupancy.  A CA-CFAR detector on the centre frame's horizontal mean planes and a
@@ -148,7 +150,30 @@ class _AssociationFields:
     __slots__ = ("candidates", "min_separation", "peak_ratio", "gate_on_presence")
 
 
-class PoseTracking(_AssociationFields):
+class _PairFields(_AssociationFields):
+    """The three settings ``PoseTracking`` gained with the joint assignment of left / right partners (a base class of their own, for
+    the same reason; ``PoseTracking.PAIR_ARGUMENTS`` lists them)."""
+    __slots__ = ("pair_swap", "swap_cost", "pairs")
+
+
+def check_pairs(pairs, joints=None):
+    """A partner table: a sequence of 1..``F_.MAX_GROUP_ROWS`` integers (no bools), entry j the partner of joint j or j itself, its own
+    inverse, and ``joints`` long where that is given -> the table as a tuple of ints.  Anything else is a TrackingError."""
+    try:
+        table = tuple(pairs)
+    except TypeError:
+        raise TrackingError("PoseTracking.pairs must be None or a sequence of joint indices, got %r" % (pairs,)) from None
+    if not 1 <= len(table) <= F_.MAX_GROUP_ROWS or (joints is not None and len(table) != joints):
+        raise TrackingError("PoseTracking.pairs must hold one entry per joint (%s), got %d"
+                            % ("1..%d" % F_.MAX_GROUP_ROWS if joints is None else joints, len(table)))
+    for j, q in enumerate(table):
+        if isinstance(q, bool) or not isinstance(q, (int, np.integer)) or not 0 <= q < len(table) or table[int(q)] != j:
+            raise TrackingError("PoseTracking.pairs[%d] = %r: every entry is a joint index, and the partner's partner is the joint itself"
+                                % (j, q))
+    return tuple(int(q) for q in table)
+
+
+class PoseTracking(_PairFields):
     """Kalman tracker settings of a session (a constant-velocity filter per joint; the rule is stated beside hupr_pose_track_f32 in
     include/hupr.h): ``rate_hz`` the frame rate of the stream; ``accel_psd`` (pixel^2 / s^3) the power of the white acceleration that
     drives the process noise; the measurement noise is ``heatmap_gain`` times the spread of the heat-map around its peak plus
@@ -162,21 +187,35 @@ class PoseTracking(_AssociationFields):
     (0, 1]) times as high and more than ``min_separation`` heat-map pixels from every peak taken; the one inside the gate with the
     smallest d2 + ln det S updates the track.  ``gate_on_presence`` (a session with ``presence`` only): a lane the presence gate calls
     empty has no measurement, its tracks coast and end.  The defaults of these three are guesses too, unmeasured on real captures;
-    ``candidates=1`` is today's tracker, and stays the default because a second candidate can be the wrong one."""
+    ``candidates=1`` is today's tracker, and stays the default because a second candidate can be the wrong one.
+    ``pair_swap=True``: the left / right partners of the skeleton are assigned jointly (csrc/pose_pairs.hip; the rule is stated beside
+    hupr_pose_track_pairs_f32): the two tracks of a pair share the peaks of both maps — each takes one, none is taken twice, the most
+    tracks updated and then the smallest summed cost win — so that a network which exchanges a left and a right limb is followed
+    instead of both tracks ending.  ``pairs``: the partner of every joint (itself for a joint without one), None = the ``L_*`` /
+    ``R_*`` names of ``DATASET.idxToJoints`` (``tools.augment.mirror_pairs``).  ``swap_cost`` (>= 0) is added to the cost of a peak
+    from the partner's map: 0 follows a swap at once, but two partners that pass close to each other then take each other's peak now
+    and then; a larger value keeps those apart and follows a real swap late (PAPERS.md has the numbers).  Hence off by default; a good
+    ``swap_cost`` for real captures is unmeasured.  It composes with ``candidates`` and ``gate_on_presence``."""
     __slots__ = ("rate_hz", "accel_psd", "meas_std", "heatmap_gain", "gate", "max_coast", "init_speed_std", "min_score", "horizon_s")
     ARGUMENTS = __slots__ + _AssociationFields.__slots__
+    PAIR_ARGUMENTS = _PairFields.__slots__
 
     def __init__(self, rate_hz, accel_psd=200.0, meas_std=1.0, heatmap_gain=1.0, gate=13.816, max_coast=5, init_speed_std=50.0,
-                 min_score=0.0, horizon_s=0.0, candidates=1, min_separation=3, peak_ratio=0.25, gate_on_presence=False):
+                 min_score=0.0, horizon_s=0.0, candidates=1, min_separation=3, peak_ratio=0.25, gate_on_presence=False, pair_swap=False,
+                 swap_cost=0.0, pairs=None):
         vals = dict(rate_hz=rate_hz, accel_psd=accel_psd, meas_std=meas_std, heatmap_gain=heatmap_gain, gate=gate,
-                    init_speed_std=init_speed_std, min_score=min_score, horizon_s=horizon_s, peak_ratio=peak_ratio)
+                    init_speed_std=init_speed_std, min_score=min_score, horizon_s=horizon_s, peak_ratio=peak_ratio, swap_cost=swap_cost)
         vals = {k: _finite(TrackingError, "PoseTracking." + k, v) for k, v in vals.items()}
         for k in ("rate_hz", "meas_std", "gate", "init_speed_std"):
             if not vals[k] > 0:
                 raise TrackingError("PoseTracking.%s must be positive, got %r" % (k, vals[k]))
-        for k in ("accel_psd", "heatmap_gain", "horizon_s"):
+        for k in ("accel_psd", "heatmap_gain", "horizon_s", "swap_cost"):
             if vals[k] < 0:
                 raise TrackingError("PoseTracking.%s must not be negative, got %r" % (k, vals[k]))
+        if not isinstance(pair_swap, bool):
+            raise TrackingError("PoseTracking.pair_swap must be True or False, got %r" % (pair_swap,))
+        self.pair_swap = pair_swap
+        self.pairs = None if pairs is None else check_pairs(pairs)
         if not 0 < peak_ratio <= 1:
             raise TrackingError("PoseTracking.peak_ratio must be in (0, 1], got %r" % (peak_ratio,))
         self.max_coast = _count(TrackingError, "PoseTracking.max_coast", max_coast, 0)
@@ -191,16 +230,36 @@ class PoseTracking(_AssociationFields):
             setattr(self, k, float(v))
 
     def __repr__(self):
-        return "PoseTracking(%s)" % ", ".join("%s=%r" % (k, getattr(self, k)) for k in self.ARGUMENTS)
+        shown = self.ARGUMENTS + (self.PAIR_ARGUMENTS if self.pair_swap else ())        # without the option: what it always printed
+        return "PoseTracking(%s)" % ", ".join("%s=%r" % (k, getattr(self, k)) for k in shown)
 
     @property
     def associates(self):
-        """Whether a session with these settings launches the associating tracker (csrc/pose_assoc.hip) instead of the plain one."""
-        return self.candidates > 1 or self.gate_on_presence
+        """Whether a session with these settings launches an associating tracker (csrc/pose_assoc.hip, or csrc/pose_pairs.hip with
+        ``pair_swap``) instead of the plain one."""
+        return self.candidates > 1 or self.gate_on_presence or self.pair_swap
+
+    def _copy(self, **changed):
+        return PoseTracking(**dict({k: getattr(self, k) for k in self.ARGUMENTS + self.PAIR_ARGUMENTS}, **changed))
 
     def with_horizon(self, horizon_s):
         """A copy that forecasts ``horizon_s`` seconds ahead."""
-        return PoseTracking(**dict({k: getattr(self, k) for k in self.ARGUMENTS}, horizon_s=horizon_s))
+        return self._copy(horizon_s=horizon_s)
+
+    def for_joints(self, names):
+        """With ``pair_swap``: a copy whose ``pairs`` fit the joints ``names`` — ``mirror_pairs(names)`` where ``pairs`` is None, else
+        ``pairs`` itself, which must hold one entry per name.  Without ``pair_swap``: these settings themselves."""
+        if not self.pair_swap:
+            return self
+        names = list(names)
+        pairs = self.pairs
+        if pairs is None:
+            from .augment import mirror_pairs
+            try:
+                pairs = mirror_pairs(names)
+            except ValueError as e:
+                raise TrackingError("PoseTracking.pairs: %s" % e) from None
+        return self._copy(pairs=check_pairs(pairs, len(names)))
 
 
 class PresenceGate:
@@ -441,15 +500,29 @@ class TrackedPoseFrame(_CandidateFields):
     With ``PoseTracking(candidates=C > 1)`` or ``gate_on_presence`` also ``candidates`` (lanes, K, C, 2), the heat-map peaks every
     joint's track chose among, in image pixels (peak 0 is ``raw_keypoints``), ``candidate_scores`` (lanes, K, C) their heat-map
     values, ``candidate_count`` (lanes, K) int32 how many there are (the slots behind hold zeros) and ``chosen`` (lanes, K) int32,
-    the peak that went into the track in this frame, -1 for none; all four None otherwise."""
+    the peak that went into the track in this frame, -1 for none; all four None otherwise.  ``source`` is None here: a session with
+    ``PoseTracking(pair_swap=True)`` emits ``PairedPoseFrame``s, which carry it."""
     __slots__ = ("covariance", "forecast", "status")
     STATUS = ("UPDATED", "COASTED_MISSING", "COASTED_GATED", "STARTED", "LOST")
+    source = None
 
     def __init__(self, frame, keypoints, scores, indices, heatmap, gcn_heatmap, raw_keypoints, velocity, covariance, forecast, status,
                  present=None, occupancy=None, candidates=None, candidate_scores=None, candidate_count=None, chosen=None, interference=None):
         super().__init__(frame, keypoints, scores, indices, heatmap, gcn_heatmap, raw_keypoints, velocity, present, occupancy, interference)
         self.covariance, self.forecast, self.status = covariance, forecast, status
         self.candidates, self.candidate_scores, self.candidate_count, self.chosen = candidates, candidate_scores, candidate_count, chosen
+
+
+class PairedPoseFrame(TrackedPoseFrame):
+    """What a tracking session with ``PoseTracking(pair_swap=True)`` emits: a ``TrackedPoseFrame`` with its four candidate fields and
+    ``source`` (lanes, K) int32, the heat-map the peak that went into the track stands in: 0 the joint's own, 1 its partner's
+    (``chosen`` is then a peak of the partner's ``candidates``), -1 for none.  (A class of its own, so that the fields of a
+    ``TrackedPoseFrame`` are what they always were.)"""
+    __slots__ = ("source",)
+
+    def __init__(self, *fields, source=None, **more):
+        super().__init__(*fields, **more)
+        self.source = source
 
 
 class PoseStream:
@@ -487,6 +560,10 @@ class PoseStream:
     ``candidates``, ``candidate_scores``, ``candidate_count`` and ``chosen``.  ``PoseTracking(gate_on_presence=True)`` (needs
     ``presence``) hands that launch the gate's verdict on the emitted frame: a lane the gate calls empty has no measurement, its tracks
     coast and then report LOST.  With ``candidates=1`` and no coupling the session launches the plain tracker, as before.
+    ``track=PoseTracking(..., pair_swap=True)``: the left / right partners of the skeleton (``pairs``, by default the ``L_*`` / ``R_*``
+    names of ``DATASET.idxToJoints``) are assigned jointly (csrc/pose_pairs.hip: one launch in the tracker's place likewise, inside the
+    same graph replay), so a left / right exchange by the network is followed; the session emits ``PairedPoseFrame``s: the four
+    candidate fields and ``source``.  Off by default: see ``PoseTracking``.
     ``interference=InterferenceFilter(...)``: interference blanking of the pushed frames (preprocessing/interference.py,
     csrc/interference.hip: two launches between the upload and the FFT chain, inside the same graph replay, in place on the session's
     device copy of the frames — a caller's device tensors are left as they are).  Every frame a push emits gains ``interference``,
@@ -508,6 +585,8 @@ class PoseStream:
             raise StreamError("history must be True or False, got %r" % (history,))
         if history and track is None:
             raise TrackingError("history needs track: it records the tracker's states for smoothed()")
+        if track is not None:                                  # pair_swap: the partner table of this config's joints
+            track = track.for_joints(getattr(D, "idxToJoints", range(D.numKeypoints)))
         self.track = track.with_horizon(self.lookahead / track.rate_hz) if predict_now else track
         self.presence = check_presence(presence)
         self.interference = check_interference(interference)
@@ -563,6 +642,8 @@ class PoseStream:
                 self._cscore = torch.zeros((lanes, self.K, C), dtype=torch.float32, device=dev)
                 self._ccount = torch.zeros((lanes, self.K), dtype=torch.int32, device=dev)
                 self._chosen = torch.full((lanes, self.K), -1, dtype=torch.int32, device=dev)
+            # with pair_swap (csrc/pose_pairs.hip in its place): the map every choice came from
+            self._source = torch.full((lanes, self.K), -1, dtype=torch.int32, device=dev) if track is not None and track.pair_swap else None
             self._history = None
             if history:
                 from .smooth import TrackHistory
@@ -627,6 +708,7 @@ class PoseStream:
         out = (self._idx, self._mx, self._kp, None, None) if self._raw is None else (self._idx, self._mx, self._raw, self._kp, self._vel)
         if t is not None:                              # the presence launches of _front precede this one on the same stream
             out += (self._cov, self._fc, self._status) + ((self._cxy, self._cscore, self._ccount, self._chosen) if t.associates else ())
+            out += (self._source,) if t.pair_swap else ()
             F_.pose_track(maps, self.ratio, refine, self._tstate, t, self._present if t.gate_on_presence else None, out=out)
         elif self.decode == "integral":
             F_.pose_decode_integral(maps, self.ratio, self.decode_radius, self._fstate, f, out=out)
@@ -662,8 +744,9 @@ class PoseStream:
                       interference=self._if_stats if pushed else None)
         if self.track is None:
             return PoseFrame(**fields)
-        return TrackedPoseFrame(covariance=self._cov, forecast=self._fc, status=self._status, candidates=self._cxy,
-                                candidate_scores=self._cscore, candidate_count=self._ccount, chosen=self._chosen, **fields)
+        fields.update(covariance=self._cov, forecast=self._fc, status=self._status, candidates=self._cxy, candidate_scores=self._cscore,
+                      candidate_count=self._ccount, chosen=self._chosen)
+        return TrackedPoseFrame(**fields) if self._source is None else PairedPoseFrame(source=self._source, **fields)
 
     # -- public ---------------------------------------------------------------------------------------------------------------
     def push(self, adc_hori, adc_vert):
@@ -764,6 +847,10 @@ def parse(argv=None):
                    "strongest (default 0.25)")
     p.add_argument("--track-on-presence", action="store_true", help="with --track and --presence: no measurement while the presence gate "
                    "sees nobody")
+    p.add_argument("--track-pairs", action="store_true", help="with --track: assign the L_* / R_* partner joints jointly, so a left / "
+                   "right exchange by the network is followed; every record gains candidates, chosen and source")
+    p.add_argument("--track-swap-cost", type=float, default=None, help="with --track-pairs: cost added to a peak from the partner's "
+                   "heat-map (default 0)")
     p.add_argument("--rts", action="store_true", help="with --track: after the flush, smooth the whole recording backwards (Rauch-Tung-"
                    "Striebel); every record gains smoothed, smoothed_velocity, smoothed_covariance and smoothed_flag")
     p.add_argument("--tdm-compensation", action="store_true", help="compensate the TDM Doppler phase in the FFT chain (weights trained "
@@ -801,6 +888,8 @@ def parse(argv=None):
         p.error("--decode-radius must be 0 (the whole map) or a positive number of heat-map pixels")
     if args.track and args.track_on_presence and not args.presence:
         p.error("--track-on-presence needs --presence")
+    if args.track_swap_cost is not None and not args.track_pairs:
+        p.error("--track-swap-cost needs --track-pairs")
     # a dependent flag (given: neither None nor False) needs its switch; with the switch the settings object must build
     for switch, flags, build, error in (("--track", TRACK_FLAGS, tracking_from_args, TrackingError),
                                         ("--presence", PRESENCE_FLAGS, presence_from_args, PresenceError),
@@ -819,7 +908,8 @@ def parse(argv=None):
 
 TRACK_FLAGS = (("--predict-now", "predict_now"), ("--accel-psd", "accel_psd"), ("--gate", "gate"), ("--max-coast", "max_coast"),
                ("--rts", "rts"), ("--track-candidates", "track_candidates"), ("--track-separation", "track_separation"),
-               ("--track-peak-ratio", "track_peak_ratio"), ("--track-on-presence", "track_on_presence"))
+               ("--track-peak-ratio", "track_peak_ratio"), ("--track-on-presence", "track_on_presence"),
+               ("--track-pairs", "track_pairs"), ("--track-swap-cost", "track_swap_cost"))
 INTERFERENCE_FLAGS = (("--interference-threshold", "interference_threshold"), ("--interference-guard", "interference_guard"),
                       ("--interference-fill", "interference_fill"))
 
@@ -853,10 +943,11 @@ def tracking_from_args(args):
     if not args.track:
         return None
     kw = {k: getattr(args, k) for k in ("accel_psd", "gate", "max_coast") if getattr(args, k) is not None}
-    for dest, k in (("track_candidates", "candidates"), ("track_separation", "min_separation"), ("track_peak_ratio", "peak_ratio")):
+    for dest, k in (("track_candidates", "candidates"), ("track_separation", "min_separation"), ("track_peak_ratio", "peak_ratio"),
+                    ("track_swap_cost", "swap_cost")):
         if getattr(args, dest) is not None:
             kw[k] = getattr(args, dest)
-    return PoseTracking(args.rate, gate_on_presence=args.track_on_presence, **kw)
+    return PoseTracking(args.rate, gate_on_presence=args.track_on_presence, pair_swap=args.track_pairs, **kw)
 
 
 def add_smoothed(records, seq, lane=0):
@@ -948,6 +1039,8 @@ def main(argv=None):
                                              zip(pf.candidates.cpu().numpy()[0], pf.candidate_scores.cpu().numpy()[0],
                                                  pf.candidate_count.cpu().numpy()[0])]
                 records[-1]["chosen"] = [int(c) for c in pf.chosen.cpu().numpy()[0]]
+            if pf.source is not None:
+                records[-1]["source"] = [int(c) for c in pf.source.cpu().numpy()[0]]
         if pf.present is not None:
             records[-1]["present"] = int(pf.present.cpu().numpy()[0])
             records[-1]["occupancy"] = [float(v) for v in pf.occupancy.cpu().numpy()[0]]

@@ -498,6 +498,46 @@ int hupr_pose_track_assoc_f32(const float* heat, long rows, int H, int W, float 
  * argument errors; rows == 0 is a no-op. */
 int hupr_pose_peaks_f32(const float* heat, long rows, int H, int W, float ratio, int refine, int K, int min_separation,
                         float peak_ratio, float* cand_xy, float* cand_score, int* cand_idx, int* cand_count, hupr_stream_t stream);
+/* hupr_pose_track_assoc_f32 with the left / right partners of a skeleton resolved together (csrc/pose_pairs.hip): a network that
+ * exchanges a left and a right limb puts each track's peak into its partner's heat-map, and the two tracks then share the peaks of
+ * both maps by global nearest neighbour on the two-track problem (Blackman 1986; Bar-Shalom, Li & Kirubarajan 2001).  New, no
+ * reference counterpart.  One 64-lane wave per unit (below), which owns the states of its one or two rows; the pool of at most 8
+ * measurements is in LDS; no scratch, no atomics: the same maps and the same state give the same bits.  Everything not said here is
+ * hupr_pose_track_assoc_f32's: the arguments up to rows_per_group, the state and its layout (so a state may pass between the three
+ * entries, and hupr_pose_smooth_rts_f32 reads any of them), the candidates of a map with their refinement and R_k, the usable rule, the
+ * presence flags, predict, gate, update, coasting, the end of a track, the eight outputs and the four candidate outputs.  idx, maxval
+ * and raw_keypoints are the row's own decode, bit for bit.
+ * partner_host : HOST memory, int [rows_per_group]: the partner of joint j inside its group of rows_per_group consecutive rows, or j
+ *   itself for a joint without one.  It is copied into the launch arguments, so there is no device table and the entry captures into a
+ *   graph.  rows_per_group is always read here (1..32), with or without present_or_null.
+ * Unit: one row without a partner, or two partner rows a < b of one group.
+ * Pool of a unit: the candidates of a's map in the slots 0 .. K-1, then (two rows) those of b's map in K .. 2K-1.
+ * Admissible measurements.  For every live track of the unit, after its prediction, every usable pool entry e gets nu, S, det S and d2
+ *   as in hupr_pose_track_f32.  e is admissible for the track when det S > 0 and finite and d2 <= gate; its cost is
+ *   c = d2 + ln det S, plus swap_cost when e comes from the other row's map.
+ * Assignment.  Every live track gets one of its admissible entries or none, and no entry goes to two tracks.  Among all such
+ *   assignments the one that updates the most tracks is taken; among those the one with the smallest fp32 sum c_a + c_b (the one cost
+ *   where one track is updated); a tie goes to the lexicographically smaller (entry of a, entry of b) in pool order, "none" last.
+ * Update or coast.  An assigned track is updated with its entry.  Every other live track coasts or ends as in hupr_pose_track_f32,
+ *   with status HUPR_TRACK_COASTED_GATED if any pool entry was usable, else HUPR_TRACK_COASTED_MISSING.
+ * Start.  A row without a live track (also one whose track ended in this frame) starts one from its OWN map's candidate 0 iff that is
+ *   usable and was not assigned to a track in this frame; otherwise the row is HUPR_TRACK_LOST.
+ * Outputs beside hupr_pose_track_assoc_f32's twelve: source [rows] int, the map the measurement that went into the state came from:
+ *   0 the row's own, 1 its partner's, -1 when none did.  chosen is the slot inside that map.
+ * With partner_host[j] == j for every j and swap_cost = 0 the twelve outputs and the state are hupr_pose_track_assoc_f32's bit for
+ *   bit, and source = (chosen >= 0 ? 0 : -1).
+ * swap_cost >= 0 prices a measurement from the partner's map: 0 (no preference) follows a swap at once but lets two partners that
+ *   pass close to each other take each other's peak now and then; a larger value keeps close partners apart and follows a swap late.
+ * Returns -1 (HUPR_ERR_ARG) before any launch for hupr_pose_track_assoc_f32's errors, a null partner_host or source, rows_per_group
+ * outside 1..32, rows no multiple of it, an entry of partner_host outside 0 .. rows_per_group-1 or partner_host[partner_host[j]] != j,
+ * swap_cost negative or not finite.  rows == 0 is a no-op. */
+int hupr_pose_track_pairs_f32(const float* heat, long rows, int H, int W, float ratio, int refine, float* state, float rate_hz,
+                              float accel_psd, float meas_std, float heatmap_gain, float gate, int max_coast, float init_speed_std,
+                              float min_score, float horizon_s, int K, int min_separation, float peak_ratio,
+                              const int* present_or_null, int rows_per_group, const int* partner_host, float swap_cost, int* idx,
+                              float* maxval, float* raw_keypoints, float* keypoints, float* velocity, float* covariance,
+                              float* forecast, int* status, float* cand_xy, float* cand_score, int* cand_count, int* chosen,
+                              int* source, hupr_stream_t stream);
 /* Fixed-interval Rauch-Tung-Striebel smoother over a recorded run of hupr_pose_track_f32 in one launch (csrc/pose_smooth.hip; Rauch,
  * Tung & Striebel 1965): the backward pass over the states the filter left behind, so that the answer for frame k uses the frames
  * after it too.  New, no reference counterpart.  One thread per row, sequential in the frame: a latency-bound recurrence of T
