@@ -2200,6 +2200,66 @@ def pose_smooth_rts(states, status, keypoints, tracking):
     return smoothed, vel, cov, flag
 
 
+SMOOTH_EMPTY = 4                    # pose_smooth_lag's flag of a tail slot whose frame does not exist yet
+MAX_LAG = 64
+
+
+def check_lag(lag, name="pose_smooth_lag"):
+    """``lag`` as an int where it is an integer (no bool) in 1..MAX_LAG; otherwise a ValueError in ``name``'s name."""
+    if isinstance(lag, bool) or not isinstance(lag, (int, np.integer)) or not 1 <= lag <= MAX_LAG:
+        raise ValueError("%s needs an integer lag in 1..%d frames, got %r" % (name, MAX_LAG, lag))
+    return int(lag)
+
+
+def pose_lag_state(rows, lag, device):
+    """A zero-filled ("new sequence") state of the fixed-lag smoother for ``rows`` (sample, joint) rows and ``lag`` frames, fp32 and
+    opaque: the ring of the last ``lag + 1`` tracker states with their outputs, and a frame counter per row."""
+    lag = check_lag(lag, "pose_lag_state")
+    return _pose_state(lambda n: rt.lib().hupr_pose_lag_state_bytes(n, lag), rows, device)
+
+
+def pose_smooth_lag(track_state, status, filtered, raw, scores, lag_state, tracking, lag, out=None):
+    """One frame of the fixed-lag Rauch-Tung-Striebel smoother behind ``pose_track``, in one launch (csrc/pose_lag.hip; the rule is
+    stated beside hupr_pose_smooth_lag_f32 in include/hupr.h).  ``track_state`` (..., 16) fp32: the tracker's state right after the
+    ``pose_track`` call of the frame; ``status`` int32 (...), ``filtered`` (..., 2), ``raw`` (..., 2) and ``scores`` (...): that
+    call's status, filtered keypoints, raw keypoints and maxima; ``lag_state`` (``pose_lag_state`` for the same rows and ``lag``,
+    advanced in place); ``tracking`` the parameters of the run (``rate_hz`` and ``accel_psd`` are read).  The frame is filed in the
+    ring, and the backward pass of ``pose_smooth_rts`` runs over the last ``lag + 1`` frames -> the tail, slot j = the frame j
+    frames ago: (keypoints (lag + 1, ..., 2), velocity (lag + 1, ..., 2), position covariance (lag + 1, ..., 3), flag int32
+    (lag + 1, ...), one of the SMOOTH_* codes; and the filter's record of the same frames: filtered (lag + 1, ..., 2), raw
+    (lag + 1, ..., 2), status int32 (lag + 1, ...), scores (lag + 1, ...)).  Slot ``lag`` is the fixed-lag answer; a slot whose
+    frame does not exist yet holds zeros and SMOOTH_EMPTY.  ``out``: that 8-tuple, to write (``_outputs``).  Device tensors, no
+    sync."""
+    lag = check_lag(lag)
+    for name, t, dtype in (("track_state", track_state, _F32), ("status", status, _I32), ("filtered", filtered, _F32), ("raw", raw, _F32),
+                           ("scores", scores, _F32), ("lag_state", lag_state, _F32)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype:
+            raise ValueError("pose_smooth_lag needs %s as a %s tensor, got %s" % (name, dtype, getattr(t, "dtype", type(t).__name__)))
+    if tracking is None:
+        raise ValueError("pose_smooth_lag needs the tracking parameters of the filter run")
+    lead = tuple(status.shape)
+    rows = int(np.prod(lead, dtype=np.int64))
+    if (track_state.numel() != rows * 16 or (rows and track_state.shape[-1] != 16) or tuple(filtered.shape) != lead + (2,)
+            or tuple(raw.shape) != lead + (2,) or tuple(scores.shape) != lead):
+        raise ValueError("pose_smooth_lag needs the %d x 16 track_state, filtered %r, raw %r and scores %r beside status %r, got %r, %r, "
+                         "%r and %r" % (rows, lead + (2,), lead + (2,), lead, lead, tuple(track_state.shape), tuple(filtered.shape),
+                                        tuple(raw.shape), tuple(scores.shape)))
+    for name, t in (("track_state", track_state), ("filtered", filtered), ("raw", raw), ("scores", scores), ("lag_state", lag_state)):
+        if t.device != status.device:
+            raise ValueError("%s is on %s, status on %s" % (name, t.device, status.device))
+    if not status.is_cuda:
+        raise ValueError("pose_smooth_lag needs GPU tensors (no CPU fallback), got %s" % status.device)
+    if not lag_state.is_contiguous() or lag_state.numel() * 4 != int(rt.lib().hupr_pose_lag_state_bytes(rows, lag)):
+        raise ValueError("lag_state must be the fp32 tensor pose_lag_state(%d, %d, device) returns" % (rows, lag))
+    track_state, status, filtered, raw, scores = _c(track_state), _c(status), _c(filtered), _c(raw), _c(scores)
+    xy, scalar = ((2,), _F32), ((), _F32)
+    out = _outputs("pose_smooth_lag", out, (lag + 1,) + lead, status.device, (xy, xy, ((3,), _F32), ((), _I32), xy, xy, ((), _I32), scalar))
+    rt.check(rt.lib().hupr_pose_smooth_lag_f32(rt.ptr(track_state), rt.ptr(status), rt.ptr(filtered), rt.ptr(raw), rt.ptr(scores), rows, lag,
+                                               float(tracking.rate_hz), float(tracking.accel_psd), rt.ptr(lag_state), *map(rt.ptr, out),
+                                               rt.stream()))
+    return out
+
+
 # ---- scene occupancy: CA-CFAR detection on the mean planes, presence gate (csrc/cfar.hip) -----------------------------------------------
 CFAR_SUMMARY = ("count", "peak_snr", "peak_f", "peak_r", "peak_a", "centroid_r", "centroid_a", "doppler")
 

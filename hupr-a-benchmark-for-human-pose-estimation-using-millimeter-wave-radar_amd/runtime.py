@@ -71,6 +71,9 @@ SIGNATURES = {
                                   [c_void_p] * 14),
     # Rauch-Tung-Striebel smoother over a recorded run of the tracker (csrc/pose_smooth.hip)
     "hupr_pose_smooth_rts_f32": (c_int, [c_void_p] * 3 + [c_long, c_long, c_float, c_float] + [c_void_p] * 5),
+    # fixed-lag smoother behind the tracker, one launch per frame over a ring of its states (csrc/pose_lag.hip)
+    "hupr_pose_lag_state_bytes": (c_size_t, [c_long, c_int]),
+    "hupr_pose_smooth_lag_f32": (c_int, [c_void_p] * 5 + [c_long, c_int, c_float, c_float] + [c_void_p] * 10),
     # scene occupancy: CA-CFAR detection on the mean planes and the presence gate (csrc/cfar.hip); the table of the first two is host memory
     "hupr_cfar_table_len": (c_int, [c_int, c_int]),
     "hupr_cfar_alpha_table_f32": (c_int, [ctypes.c_double, c_int, c_int, ctypes.POINTER(c_float), c_int]),

@@ -3,8 +3,8 @@ from .optim import FusedAdam, FusedSGD  # noqa: F401
 _STREAM = ("PoseStream", "PoseFrame", "StreamSchedule", "stream_window_sources", "StreamError", "LookaheadError",
            "FrameShapeError", "FrameDtypeError", "StreamEndedError", "PoseSmoothing", "DecodeError", "SmoothingError",
            "PoseTracking", "TrackedPoseFrame", "PairedPoseFrame", "TrackingError", "PresenceGate", "PresenceError",
-           "InterferenceError")
-_SMOOTH = ("SequenceSmoother", "SmoothedSequence", "TrackHistory", "jitter")
+           "InterferenceError", "LaggedPose", "LaggedTrackedPoseFrame", "LaggedPairedPoseFrame")
+_SMOOTH = ("SequenceSmoother", "SmoothedSequence", "TrackHistory", "LagRecord", "jitter")
 
 
 def __getattr__(name):          # lazy: Runner pulls in datasets/models

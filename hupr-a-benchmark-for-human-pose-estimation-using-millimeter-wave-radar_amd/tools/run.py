@@ -150,12 +150,13 @@ class Runner(BaseRunner):
         (``mean_position_error``): AP's OKS thresholds are too coarse to show a sub-pixel change.  ``TRAINING.boneLoss`` prints that
         line and one more, the mean error of the bones' lengths in image pixels (``mean_bone_error``).
         ``--keypoints`` prints the per-joint APs (``evaluateEach``) instead of the summary line.
-        ``TEST.temporal: track`` or ``rts`` (``temporal_setting``): the test set is walked in loader order as sequences (sequence and
+        ``TEST.temporal: track``, ``rts`` or ``lag`` (``temporal_setting``): the test set is walked in loader order as sequences (sequence and
         frame from ``imageId``; a new sequence or a frame that is not its predecessor + 1 zeroes the tracker state), every sample's
         second-head maps go through ``SequenceSmoother.track`` one frame per call, and the keypoints written and scored are the
-        Kalman-filtered ones (``track``) or the Rauch-Tung-Striebel smoothed ones (``rts``).  After the AP line come an ``MPJPE``
-        line for the raw, the filtered and (``rts``) the smoothed keypoints and a ``Jitter`` line (``tools.smooth.jitter``) for each
-        of them and for the ground truth.
+        Kalman-filtered ones (``track``), the Rauch-Tung-Striebel smoothed ones (``rts``) or the fixed-lag smoothed ones (``lag``:
+        every frame smoothed over the ``TEST.temporalLag`` frames behind it, ``SequenceSmoother.smooth_lagged``).  After the AP line
+        come an ``MPJPE`` line for the raw, the filtered and the smoothed (``rts``) or lagged (``lag``) keypoints and a ``Jitter``
+        line (``tools.smooth.jitter``) for each of them and for the ground truth.
         ``TEST.presence`` (``tools.stream.presence_setting``): the test set is walked as sequences in the same way, the CA-CFAR
         detector (``functional.cfar_ra``) runs on the horizontal mean planes of every sample's labelled frame (window position G / 2)
         and the presence gate across each sequence, and one more line is printed: ``Presence: <share> of <n> labelled frames present,
@@ -169,7 +170,8 @@ class Runner(BaseRunner):
         blanked = [] if self.engine.interference is not None else None
         temporal = self.temporal
         if temporal is not None:
-            smoother = SequenceSmoother(temporal.tracking, self.numKeypoints, self.engine.device)
+            smoother = SequenceSmoother(temporal.tracking, self.numKeypoints, self.engine.device,
+                                        lag=temporal.lag if temporal.mode == "lag" else None)
             walker, boxes, ids = SequenceWalker(), [], []
         gate = self.presence
         if gate is not None:
@@ -218,11 +220,12 @@ class Runner(BaseRunner):
                 gts.append({"image_id": int(batch["imageId"][j]), "keypoints": gt_joints[j].numpy().astype(np.float64),
                             "bbox": batch["bbox"][j].numpy().astype(np.float64)})
         if temporal is not None:
-            seq = (smoother.smooth() if temporal.mode == "rts" else smoother.history.record()).cpu()
+            seq = {"rts": smoother.smooth, "lag": smoother.smooth_lagged, "track": smoother.history.record}[temporal.mode]().cpu()
             tracks = {"raw": seq.raw.numpy(), "filtered": seq.filtered.numpy()}
-            if temporal.mode == "rts":
-                tracks["smoothed"] = seq.keypoints.numpy()
-            self.saveKeypoints(savePreds, tracks["smoothed" if temporal.mode == "rts" else "filtered"], boxes, ids)
+            scored = {"rts": "smoothed", "lag": "lagged", "track": "filtered"}[temporal.mode]
+            if scored != "filtered":
+                tracks[scored] = seq.keypoints.numpy()
+            self.saveKeypoints(savePreds, tracks[scored], boxes, ids)
             visited = np.stack([g["keypoints"] for g in gts])
         if self.world > 1:
             parts = [None] * self.world

@@ -8,6 +8,10 @@ the frames after it too: a gap the filter coasted through becomes an interpolati
 ``Runner.eval`` walks a labelled test set through a ``SequenceSmoother`` under ``TEST.temporal`` (``temporal_setting``,
 ``SequenceWalker``).  ``jitter`` is the metric both print.
 
+``SequenceSmoother(..., lag=L)`` also runs the fixed-lag smoother of the live stream behind every tracked frame (csrc/pose_lag.hip,
+hupr_pose_smooth_lag_f32: the backward pass over the last L + 1 frames only) and keeps its answers, ``smooth_lagged()`` returns them and
+``TEST.temporal: lag`` scores them: what a live consumer that waits L frames would have seen.
+
 The smoother is a latency-bound recurrence (one thread per row, T dependent steps); nothing here claims a speed."""
 import math
 
@@ -17,9 +21,10 @@ import torch
 from .. import functional as F_
 from .stream import PoseTracking, TrackingError
 
-FLAGS = ("SMOOTHED", "END", "PASSTHROUGH", "DEGENERATE")
-TEMPORAL = ("off", "track", "rts")
+FLAGS = ("SMOOTHED", "END", "PASSTHROUGH", "DEGENERATE", "EMPTY")
+TEMPORAL = ("off", "track", "rts", "lag")
 DEFAULT_RATE_HZ = 10.0              # the HuPR capture rate
+DEFAULT_LAG = 4                     # frames: 0.4 s at that rate (PAPERS.md has what the lag buys on the tracker tests' scenario)
 SEQUENCE_STRIDE = 100000            # image_id = frame + 100000 * sequence (datasets/base.py)
 
 
@@ -73,10 +78,14 @@ class TrackHistory:
 
     def append(self, state, status, filtered, raw, scores):
         """One frame: the tracker's state tensor right after the frame's launch and that launch's outputs."""
+        self._append((state, status, filtered, raw, scores))
+
+    def _append(self, values):
+        """One frame: a tensor per entry of ``_FIELDS``, in that order."""
         if self.length == self._capacity:
             self._grow(2 * self._capacity)
         k = self.length
-        for name, t in (("states", state), ("status", status), ("filtered", filtered), ("raw", raw), ("scores", scores)):
+        for (name, _, _), t in zip(self._FIELDS, values):
             dst = self._buf[name][k]
             dst.copy_(t.reshape(dst.shape), non_blocking=True)
         self.length = k + 1
@@ -100,14 +109,42 @@ class TrackHistory:
         return SmoothedSequence(kp, vel, cov, flag, b["filtered"].clone(), b["raw"].clone(), b["status"].clone(), b["scores"].clone())
 
 
+class LagRecord(TrackHistory):
+    """The fixed-lag answers of the frames of a ``TrackHistory``, position by position: ``append(tail)`` takes a new frame with the
+    tail of its launch (``functional.pose_smooth_lag``) — the frame enters with tail slot 0, the filter's own pose, and the frame
+    ``lag`` positions back gets slot ``lag`` once ``due``; ``settle(tail, m)`` gives the last ``m`` frames the slots m-1 .. 0, what
+    they are owed when nothing follows.  Device-to-device copies on the current stream, no sync."""
+    _FIELDS = (("keypoints", (2,), torch.float32), ("velocity", (2,), torch.float32), ("covariance", (3,), torch.float32),
+               ("flag", (), torch.int32))
+
+    def append(self, tail, lag, due):
+        self._append(tuple(t[0] for t in tail[:4]))
+        if due:
+            for (name, _, _), t in zip(self._FIELDS, tail):
+                self._buf[name][self.length - 1 - lag].copy_(t[lag].reshape(self._buf[name].shape[1:]), non_blocking=True)
+
+    def settle(self, tail, m):
+        for (name, _, _), t in zip(self._FIELDS, tail):
+            if m:
+                dst = self._buf[name][self.length - m:self.length]
+                dst.copy_(t[:m].flip(0).reshape(dst.shape), non_blocking=True)
+
+    def views(self):
+        return tuple(self._views()[name] for name, _, _ in self._FIELDS)
+
+
 class SequenceSmoother:
     """A tracker (``functional.pose_track`` on a state of its own) that remembers: ``track(heat, ratio, refine)`` is one frame of
     ``rows`` heat-maps and returns ``pose_track``'s tuple (with ``tracking.candidates`` > 1 the associating tracker's twelve, with
     ``tracking.pair_swap`` — whose ``pairs`` must then fit the ``rows`` joints of a frame — those and ``source``);
     ``new_sequence()`` zeroes the state, so that the next frame starts new tracks and the smoother's chain breaks there by itself;
-    ``smooth()`` smooths everything tracked so far in one launch."""
+    ``smooth()`` smooths everything tracked so far in one launch.
+    ``lag=L`` (an integer in 1..64; None, the default, adds nothing): ``track`` also runs the fixed-lag smoother's launch behind the
+    tracker's (``functional.pose_smooth_lag`` on a lag state of its own) and keeps tail slot L, the answer for the frame L calls
+    back; ``smooth_lagged()`` returns the fixed-lag answers of every frame tracked so far, those of a sequence's last L frames taken
+    from the tail of its last launch; ``new_sequence()`` takes them before it zeroes the lag state too."""
 
-    def __init__(self, tracking, rows, device):
+    def __init__(self, tracking, rows, device, lag=None):
         if not isinstance(tracking, PoseTracking):
             raise TrackingError("tracking must be a PoseTracking, got %r" % (tracking,))
         if tracking.gate_on_presence:
@@ -120,6 +157,11 @@ class SequenceSmoother:
         self.tracking, self.rows, self.device = tracking, int(rows), torch.device(device)
         self.state = F_.pose_track_state(self.rows, self.device)
         self.history = TrackHistory((self.rows,), self.device)
+        self.lag = None if lag is None else F_.check_lag(lag, "SequenceSmoother: lag")
+        if self.lag is not None:
+            self.lag_state = F_.pose_lag_state(self.rows, self.lag, self.device)
+            self.lagged = LagRecord((self.rows,), self.device)
+            self._tail, self._run = None, 0                    # the last launch's tail; frames tracked in the current sequence
 
     def __len__(self):
         return len(self.history)
@@ -128,18 +170,46 @@ class SequenceSmoother:
         out = F_.pose_track(heat, ratio, refine=refine, track_state=self.state, tracking=self.tracking)
         mx, raw, kp, status = out[1], out[2], out[3], out[7]
         self.history.append(self.state, status, kp, raw, mx)
+        if self.lag is not None:
+            lead = (self.rows,)
+            self._tail = F_.pose_smooth_lag(self.state, status.reshape(lead), kp.reshape(lead + (2,)), raw.reshape(lead + (2,)),
+                                            mx.reshape(lead), self.lag_state, self.tracking, self.lag, out=self._tail)
+            self._run += 1
+            self.lagged.append(self._tail, self.lag, self._run > self.lag)
         return out
 
+    def _settle(self):
+        """The current sequence's last frames get what the tail of its last launch owes them (again after every further frame)."""
+        if self.lag is not None and self._run:
+            self.lagged.settle(self._tail, min(self.lag, self._run))
+
     def new_sequence(self):
+        self._settle()
         self.state.zero_()
+        if self.lag is not None:
+            self.lag_state.zero_()
+            self._run = 0
 
     def clear(self):
         """Forget the history and the tracks."""
         self.state.zero_()
         self.history.clear()
+        if self.lag is not None:
+            self.lag_state.zero_()
+            self.lagged.clear()
+            self._run = 0
 
     def smooth(self):
         return self.history.smooth(self.tracking)
+
+    def smooth_lagged(self):
+        """-> SmoothedSequence of the fixed-lag answers of every frame tracked so far: frame k smoothed over the ``lag`` frames behind
+        it, or over those its sequence still had.  No launch but the copies; needs ``lag``."""
+        if self.lag is None:
+            raise TrackingError("smooth_lagged() needs a SequenceSmoother built with lag=...")
+        self._settle()
+        rec = self.history.record()
+        return SmoothedSequence(*[t.clone() for t in self.lagged.views()], rec.filtered, rec.raw, rec.status, rec.scores)
 
 
 def jitter(keypoints):
@@ -160,30 +230,36 @@ def jitter(keypoints):
 
 # ---- Runner.eval under TEST.temporal -----------------------------------------------------------------------------------------------------
 class TemporalSetting:
-    """``TEST.temporal`` as read by ``temporal_setting``: ``mode`` "track" or "rts", ``tracking`` the PoseTracking of the run."""
-    __slots__ = ("mode", "tracking")
+    """``TEST.temporal`` as read by ``temporal_setting``: ``mode`` "track", "rts" or "lag", ``tracking`` the PoseTracking of the run,
+    ``lag`` the frames of ``TEST.temporalLag`` (read by "lag" only)."""
+    __slots__ = ("mode", "tracking", "lag")
 
-    def __init__(self, mode, tracking):
-        self.mode, self.tracking = mode, tracking
+    def __init__(self, mode, tracking, lag=DEFAULT_LAG):
+        self.mode, self.tracking, self.lag = mode, tracking, lag
 
 
 def temporal_setting(cfg):
-    """``TEST.temporal`` / ``TEST.temporalRate`` / ``TEST.tracking`` (no keys of the reference's YAML) -> None with ``temporal`` absent
-    or ``off``, else a TemporalSetting.  ``temporal``: ``off``, ``track`` (the Kalman filter's keypoints are scored) or ``rts`` (the
-    smoothed ones).  ``temporalRate``: the frame rate in Hz, a positive finite number, absent = 10.0, the HuPR capture rate.
-    ``tracking``: a mapping of PoseTracking keyword arguments other than ``rate_hz``.  All three are checked whatever ``temporal``
-    says; anything else, and ``TEST.decode: integral`` beside ``track`` or ``rts`` (the tracker's measurement is the sub-pixel
-    decode's, as in the live stream), raises here, where the config is read."""
+    """``TEST.temporal`` / ``TEST.temporalRate`` / ``TEST.temporalLag`` / ``TEST.tracking`` (no keys of the reference's YAML) -> None
+    with ``temporal`` absent or ``off``, else a TemporalSetting.  ``temporal``: ``off``, ``track`` (the Kalman filter's keypoints
+    are scored), ``rts`` (the smoothed ones) or ``lag`` (the fixed-lag smoothed ones, what a live consumer ``temporalLag`` frames
+    late would see).  ``temporalRate``: the frame rate in Hz, a positive finite number, absent = 10.0, the HuPR capture rate.
+    ``temporalLag``: an integer in 1..64 frames, absent = 4.  ``tracking``: a mapping of PoseTracking keyword arguments other than
+    ``rate_hz``.  All four are checked whatever ``temporal`` says; anything else, and ``TEST.decode: integral`` beside ``track``,
+    ``rts`` or ``lag`` (the tracker's measurement is the sub-pixel decode's, as in the live stream), raises here, where the config is
+    read."""
     from ..misc.metrics import decode_setting
     test = getattr(cfg, "TEST", None)
     mode = getattr(test, "temporal", "off")
     if mode is False:                                   # YAML reads a bare off as False
         mode = "off"
     if not isinstance(mode, str) or mode not in TEMPORAL:
-        raise ValueError("TEST.temporal must be 'off', 'track' or 'rts', got %r" % (mode,))
+        raise ValueError("TEST.temporal must be 'off', 'track', 'rts' or 'lag', got %r" % (mode,))
     rate = getattr(test, "temporalRate", DEFAULT_RATE_HZ)
     if isinstance(rate, bool) or not isinstance(rate, (int, float)) or not math.isfinite(rate) or not rate > 0:
         raise ValueError("TEST.temporalRate must be a positive finite number (Hz), got %r" % (rate,))
+    lag = getattr(test, "temporalLag", DEFAULT_LAG)
+    if isinstance(lag, bool) or not isinstance(lag, (int, np.integer)) or not 1 <= lag <= F_.MAX_LAG:
+        raise ValueError("TEST.temporalLag must be an integer in 1..%d (frames), got %r" % (F_.MAX_LAG, lag))
     kw = getattr(test, "tracking", None)
     if kw is None:
         kw = {}
@@ -206,7 +282,7 @@ def temporal_setting(cfg):
     if decode_setting(cfg) == "integral":
         raise ValueError("TEST.temporal: %s and TEST.decode: integral exclude each other: the tracker's measurement is the sub-pixel "
                          "decode's" % mode)
-    return TemporalSetting(mode, tracking)
+    return TemporalSetting(mode, tracking, int(lag))
 
 
 def sequence_and_frame(image_id):

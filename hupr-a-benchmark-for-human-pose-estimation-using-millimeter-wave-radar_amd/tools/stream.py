@@ -33,7 +33,7 @@ radius; 0: the whole map) — what the integral coordinate loss trains — in on
                                     [--decode argmax|subpixel|integral [--decode-radius N]] [--smooth --rate FPS]
                                     [--track --rate FPS [--predict-now] [--accel-psd Q] [--gate D2] [--max-coast N] [--rts]
                                      [--track-candidates N] [--track-separation N] [--track-peak-ratio X] [--track-on-presence]
-                                     [--track-pairs [--track-swap-cost X]]]
+                                     [--track-pairs [--track-swap-cost X]] [--track-lag N]]
                                     [--presence [--pfa X] [--cfar-guard N] [--cfar-train N] [--min-cells N] [--confirm N] [--hold N]]
 
 ``presence=PresenceGate(...)`` / ``--presence``: scene occupancy.  A CA-CFAR detector on the centre frame's horizontal mean planes and a
@@ -42,6 +42,10 @@ record gains ``present`` and ``occupancy``.  It reports only, the pose is what i
 
 ``--rts`` (with ``--track``): the capture is a finished file, so after the flush the recorded tracker states go through the
 Rauch-Tung-Striebel smoother (tools/smooth.py, csrc/pose_smooth.hip) and every record gains the smoothed pose.
+
+``lag=N`` / ``--track-lag N`` (with ``--track``): fixed-lag smoothing while the stream runs (csrc/pose_lag.hip, one launch behind the
+tracker's inside the same replay): every emitted frame carries the pose of N frames earlier smoothed over the N frames since, and every
+record gains ``lagged``, ``lagged_velocity``, ``lagged_covariance`` and ``lagged_flag``, the last N from ``lag_tail()``.
 """
 import argparse
 import json
@@ -90,7 +94,7 @@ class SmoothingError(StreamError):
 
 class TrackingError(StreamError):
     """A ``PoseTracking`` parameter out of range, ``track`` is not a ``PoseTracking``, ``track`` together with ``smooth`` or with
-    ``decode="integral"``, or ``predict_now`` without ``track``."""
+    ``decode="integral"``, ``predict_now``, ``history`` or ``lag`` without ``track``, or ``lag`` outside 1..64."""
 
 
 class InterferenceError(StreamError):
@@ -464,6 +468,7 @@ class PoseFrame(_OccupancyFields):
     ``interference`` and in the frames of a ``flush()``, which pushes nothing.  Device tensors owned by the session, valid until its
     next push / flush / reset."""
     __slots__ = ("frame", "keypoints", "scores", "indices", "heatmap", "gcn_heatmap", "raw_keypoints", "velocity")
+    lagged = None                       # the fixed-lag pose that falls due with this frame: only a session with ``lag`` fills it
 
     def __init__(self, frame, keypoints, scores, indices, heatmap, gcn_heatmap, raw_keypoints=None, velocity=None, present=None,
                  occupancy=None, interference=None):
@@ -478,7 +483,8 @@ class PoseFrame(_OccupancyFields):
         """A frame of the same class with ``fn`` of every tensor: the fields are the ``__slots__`` along the MRO, and the constructors
         take them by those names."""
         fields = {k: getattr(self, k) for c in type(self).__mro__ for k in getattr(c, "__slots__", ())}
-        return type(self)(**{k: v if v is None or k == "frame" else fn(v) for k, v in fields.items()})
+        each = lambda k, v: v if v is None or k == "frame" else v._map(fn) if k == "lagged" else fn(v)
+        return type(self)(**{k: each(k, v) for k, v in fields.items()})
 
     def clone(self):
         return self._map(torch.clone)
@@ -525,6 +531,62 @@ class PairedPoseFrame(TrackedPoseFrame):
         self.source = source
 
 
+class LaggedPose:
+    """The fixed-lag smoothed pose that falls due with an emitted frame of a session with ``lag=L`` (csrc/pose_lag.hip; the rule is
+    stated beside hupr_pose_smooth_lag_f32 in include/hupr.h): the pose of ``frame`` = the emitted centre - L, smoothed backwards
+    over the L poses emitted since.  ``keypoints`` (lanes, K, 2), ``velocity`` (lanes, K, 2) per second, ``covariance`` (lanes, K, 3)
+    = (Pxx, Pxy, Pyy), ``flag`` (lanes, K) int32, one of ``functional.SMOOTH_*``; and what the filter gave for that frame:
+    ``filtered`` its keypoints, ``raw_keypoints`` the decoded ones, ``status`` its status codes, ``scores`` the maxima.  Device
+    tensors owned by the session, valid until its next push / flush / reset."""
+    __slots__ = ("frame", "keypoints", "velocity", "covariance", "flag", "filtered", "raw_keypoints", "status", "scores")
+
+    def __init__(self, frame, keypoints, velocity, covariance, flag, filtered, raw_keypoints, status, scores):
+        self.frame, self.keypoints, self.velocity, self.covariance, self.flag = frame, keypoints, velocity, covariance, flag
+        self.filtered, self.raw_keypoints, self.status, self.scores = filtered, raw_keypoints, status, scores
+
+    def _map(self, fn):
+        return LaggedPose(self.frame, *[fn(getattr(self, k)) for k in self.__slots__[1:]])
+
+    def clone(self):
+        return self._map(torch.clone)
+
+    def cpu(self):
+        """Host copies (synchronises)."""
+        return self._map(lambda t: t.cpu())
+
+
+class LaggedTrackedPoseFrame(TrackedPoseFrame):
+    """What a tracking session with ``lag=L`` emits: a ``TrackedPoseFrame`` with ``lagged``, the ``LaggedPose`` of L frames ago, None
+    in the first L frames of a sequence.  (A class of its own, so that the fields of a ``TrackedPoseFrame`` are what they always
+    were.)"""
+    __slots__ = ("lagged",)
+
+    def __init__(self, *fields, lagged=None, **more):
+        super().__init__(*fields, **more)
+        self.lagged = lagged
+
+
+class LaggedPairedPoseFrame(PairedPoseFrame):
+    """The same for a session with ``PoseTracking(pair_swap=True)``: a ``PairedPoseFrame`` with ``lagged``."""
+    __slots__ = ("lagged",)
+
+    def __init__(self, *fields, lagged=None, **more):
+        super().__init__(*fields, **more)
+        self.lagged = lagged
+
+
+def check_lag(lag, track):
+    """The session's ``lag`` argument: None, or with ``track`` an integer in 1..``F_.MAX_LAG`` -> None or the int."""
+    if lag is None:
+        return None
+    if track is None:
+        raise TrackingError("lag needs track: the fixed-lag smoother runs over the tracker's states")
+    try:
+        return F_.check_lag(lag, "PoseStream: lag")
+    except ValueError as e:
+        raise TrackingError(str(e)) from None
+
+
 class PoseStream:
     """Streaming session around a HuPRNet.  ``push(adc_hori, adc_vert)`` takes the new int16 frame of both sensors,
     (lanes, 4, 192, 256, 2) each — device tensors are used directly, host tensors go through the session's pinned staging and an
@@ -567,10 +629,18 @@ class PoseStream:
     ``interference=InterferenceFilter(...)``: interference blanking of the pushed frames (preprocessing/interference.py,
     csrc/interference.hip: two launches between the upload and the FFT chain, inside the same graph replay, in place on the session's
     device copy of the frames — a caller's device tensors are left as they are).  Every frame a push emits gains ``interference``,
-    the filter's counts on the frame that push brought in.  It composes with every other setting; the default adds nothing."""
+    the filter's counts on the frame that push brought in.  It composes with every other setting; the default adds nothing.
+    ``lag=L`` (needs ``track``; an integer in 1..64): fixed-lag smoothing.  Behind the tracker's launch of every push or flush that
+    emits a pose, one launch of csrc/pose_lag.hip, inside the same graph replay, files the tracker's state in a ring of L + 1 frames
+    on the device and runs the Rauch-Tung-Striebel backward pass over that ring.  The session then emits ``LaggedTrackedPoseFrame``s
+    (``LaggedPairedPoseFrame``s with ``pair_swap``): every frame gains ``lagged``, the ``LaggedPose`` of the frame L poses earlier —
+    None in the first L emitted frames — and after ``flush()`` ``lag_tail()`` returns the L poses still owed.  The smoother reports
+    only: the filter's own outputs are those of a session without ``lag``, bit for bit; ``reset()`` starts its ring anew.  It works
+    with all three tracker launches and with ``history`` and ``presence``.  The default, None, adds nothing."""
 
     def __init__(self, model, cfg, lanes=1, lookahead=None, graph=True, device=None, decode="argmax", smooth=None, track=None,
-                 predict_now=False, decode_radius=None, tdm_compensation=False, history=False, presence=None, interference=None):
+                 predict_now=False, decode_radius=None, tdm_compensation=False, history=False, presence=None, interference=None,
+                 lag=None):
         D = cfg.DATASET
         self.G = D.numGroupFrames
         self.schedule = StreamSchedule(self.G, lookahead)
@@ -585,6 +655,7 @@ class PoseStream:
             raise StreamError("history must be True or False, got %r" % (history,))
         if history and track is None:
             raise TrackingError("history needs track: it records the tracker's states for smoothed()")
+        self.lag = check_lag(lag, track)
         if track is not None:                                  # pair_swap: the partner table of this config's joints
             track = track.for_joints(getattr(D, "idxToJoints", range(D.numKeypoints)))
         self.track = track.with_horizon(self.lookahead / track.rate_hz) if predict_now else track
@@ -644,6 +715,14 @@ class PoseStream:
                 self._chosen = torch.full((lanes, self.K), -1, dtype=torch.int32, device=dev)
             # with pair_swap (csrc/pose_pairs.hip in its place): the map every choice came from
             self._source = torch.full((lanes, self.K), -1, dtype=torch.int32, device=dev) if track is not None and track.pair_swap else None
+            # the fixed-lag smoother behind it (csrc/pose_lag.hip): its ring and counters, and the tail of the last launch
+            self._lstate = self._tail = None
+            if self.lag is not None:
+                self._lstate = F_.pose_lag_state(lanes * self.K, self.lag, dev)
+                lead = (self.lag + 1, lanes, self.K)
+                self._tail = tuple(torch.zeros(lead + tail, dtype=dtype, device=dev) for tail, dtype in
+                                   (((2,), torch.float32), ((2,), torch.float32), ((3,), torch.float32), ((), torch.int32),
+                                    ((2,), torch.float32), ((2,), torch.float32), ((), torch.int32), ((), torch.float32)))
             self._history = None
             if history:
                 from .smooth import TrackHistory
@@ -710,6 +789,8 @@ class PoseStream:
             out += (self._cov, self._fc, self._status) + ((self._cxy, self._cscore, self._ccount, self._chosen) if t.associates else ())
             out += (self._source,) if t.pair_swap else ()
             F_.pose_track(maps, self.ratio, refine, self._tstate, t, self._present if t.gate_on_presence else None, out=out)
+            if self.lag is not None:                   # reads what the tracker left, writes its own ring and tail only
+                F_.pose_smooth_lag(self._tstate, self._status, self._kp, self._raw, self._mx, self._lstate, t, self.lag, out=self._tail)
         elif self.decode == "integral":
             F_.pose_decode_integral(maps, self.ratio, self.decode_radius, self._fstate, f, out=out)
         elif self._fused:
@@ -746,7 +827,16 @@ class PoseStream:
             return PoseFrame(**fields)
         fields.update(covariance=self._cov, forecast=self._fc, status=self._status, candidates=self._cxy, candidate_scores=self._cscore,
                       candidate_count=self._ccount, chosen=self._chosen)
-        return TrackedPoseFrame(**fields) if self._source is None else PairedPoseFrame(source=self._source, **fields)
+        if self.lag is None:
+            return TrackedPoseFrame(**fields) if self._source is None else PairedPoseFrame(source=self._source, **fields)
+        lagged = self._lagged(center, self.lag) if center >= self.lag else None
+        if self._source is None:
+            return LaggedTrackedPoseFrame(lagged=lagged, **fields)
+        return LaggedPairedPoseFrame(source=self._source, lagged=lagged, **fields)
+
+    def _lagged(self, newest, j):
+        """Tail slot ``j`` of the last launch, whose newest pose was number ``newest``, as a LaggedPose of views."""
+        return LaggedPose(newest - j, *[t[j] for t in self._tail])
 
     # -- public ---------------------------------------------------------------------------------------------------------------
     def push(self, adc_hori, adc_vert):
@@ -803,9 +893,21 @@ class PoseStream:
                 self._tstate.zero_()                           # likewise: the next usable measurement of a joint starts its track
             if self._gstate is not None:
                 self._gstate.zero_()                           # absent, no hits, no misses
+            if self._lstate is not None:
+                self._lstate.zero_()                           # a new sequence: an empty ring, every row's counter at 0
         self.schedule.reset()
         if self._history is not None:
             self._history.clear()
+
+    def lag_tail(self):
+        """After ``flush()``: the ``min(lag, poses emitted)`` fixed-lag poses still owed at the end of a sequence, oldest first -> a
+        list of ``LaggedPose`` (independent copies), from the slots lag-1 .. 0 of the last launch's tail: each is smoothed with all
+        the poses there are behind it, the last one is the filter's own.  It launches nothing; needs a session built with ``lag``."""
+        if self.lag is None:
+            raise TrackingError("lag_tail() needs a session built with track=... and lag=...")
+        emitted = self.schedule.frames_emitted
+        with torch.cuda.device(self.device):
+            return [self._lagged(emitted - 1, j).clone() for j in range(min(self.lag, emitted) - 1, -1, -1)]
 
     def smoothed(self):
         """The poses emitted since the last ``reset()``, smoothed backwards over the tracker's recorded states -> a
@@ -851,6 +953,8 @@ def parse(argv=None):
                    "right exchange by the network is followed; every record gains candidates, chosen and source")
     p.add_argument("--track-swap-cost", type=float, default=None, help="with --track-pairs: cost added to a peak from the partner's "
                    "heat-map (default 0)")
+    p.add_argument("--track-lag", type=int, default=None, help="with --track: fixed-lag smoothing over this many frames, 1..64; every "
+                   "record gains lagged, lagged_velocity, lagged_covariance and lagged_flag, N frames after its own pose")
     p.add_argument("--rts", action="store_true", help="with --track: after the flush, smooth the whole recording backwards (Rauch-Tung-"
                    "Striebel); every record gains smoothed, smoothed_velocity, smoothed_covariance and smoothed_flag")
     p.add_argument("--tdm-compensation", action="store_true", help="compensate the TDM Doppler phase in the FFT chain (weights trained "
@@ -890,6 +994,8 @@ def parse(argv=None):
         p.error("--track-on-presence needs --presence")
     if args.track_swap_cost is not None and not args.track_pairs:
         p.error("--track-swap-cost needs --track-pairs")
+    if args.track_lag is not None and not 1 <= args.track_lag <= F_.MAX_LAG:
+        p.error("--track-lag must be an integer in 1..%d frames" % F_.MAX_LAG)
     # a dependent flag (given: neither None nor False) needs its switch; with the switch the settings object must build
     for switch, flags, build, error in (("--track", TRACK_FLAGS, tracking_from_args, TrackingError),
                                         ("--presence", PRESENCE_FLAGS, presence_from_args, PresenceError),
@@ -909,7 +1015,7 @@ def parse(argv=None):
 TRACK_FLAGS = (("--predict-now", "predict_now"), ("--accel-psd", "accel_psd"), ("--gate", "gate"), ("--max-coast", "max_coast"),
                ("--rts", "rts"), ("--track-candidates", "track_candidates"), ("--track-separation", "track_separation"),
                ("--track-peak-ratio", "track_peak_ratio"), ("--track-on-presence", "track_on_presence"),
-               ("--track-pairs", "track_pairs"), ("--track-swap-cost", "track_swap_cost"))
+               ("--track-pairs", "track_pairs"), ("--track-swap-cost", "track_swap_cost"), ("--track-lag", "track_lag"))
 INTERFERENCE_FLAGS = (("--interference-threshold", "interference_threshold"), ("--interference-guard", "interference_guard"),
                       ("--interference-fill", "interference_fill"))
 
@@ -960,6 +1066,19 @@ def add_smoothed(records, seq, lane=0):
         rec["smoothed_velocity"] = [[float(vx), float(vy)] for vx, vy in seq.velocity[k, lane].numpy()]
         rec["smoothed_covariance"] = [[float(v) for v in c] for c in seq.covariance[k, lane].numpy()]
         rec["smoothed_flag"] = [int(c) for c in seq.flag[k, lane].numpy()]
+    return records
+
+
+def add_lagged(records, lagged, lane=0):
+    """--track-lag: ``lane`` of a LaggedPose into the record of its frame (records[k] is frame k), in place."""
+    lp = lagged.cpu()
+    rec = records[lp.frame]
+    if rec["frame"] != lp.frame:
+        raise ValueError("record %d holds frame %d" % (lp.frame, rec["frame"]))
+    rec["lagged"] = [[float(x), float(y)] for x, y in lp.keypoints[lane].numpy()]
+    rec["lagged_velocity"] = [[float(vx), float(vy)] for vx, vy in lp.velocity[lane].numpy()]
+    rec["lagged_covariance"] = [[float(v) for v in c] for c in lp.covariance[lane].numpy()]
+    rec["lagged_flag"] = [int(c) for c in lp.flag[lane].numpy()]
     return records
 
 
@@ -1022,7 +1141,8 @@ def main(argv=None):
     session = PoseStream(model, cfg, lanes=1, lookahead=args.lookahead, graph=not args.no_graph, device=dev, decode=args.decode,
                          smooth=PoseSmoothing(args.rate) if args.smooth else None, track=tracking_from_args(args),
                          predict_now=args.predict_now, decode_radius=args.decode_radius, tdm_compensation=args.tdm_compensation,
-                         history=args.rts, presence=presence_from_args(args), interference=interference_from_args(args))
+                         history=args.rts, presence=presence_from_args(args), interference=interference_from_args(args),
+                         lag=args.track_lag)
     records = []
 
     def record(pf):
@@ -1046,6 +1166,8 @@ def main(argv=None):
             records[-1]["occupancy"] = [float(v) for v in pf.occupancy.cpu().numpy()[0]]
         if pf.interference is not None:              # (sensor, {samples replaced, chirps touched}) of the frame this push brought in
             records[-1]["interference"] = [[int(v) for v in row] for row in pf.interference.cpu().numpy()[:, 0]]
+        if pf.lagged is not None:                    # the pose of --track-lag frames ago falls due: into that frame's record
+            add_lagged(records, pf.lagged)
 
     for i in range(n):
         pf = session.push(frames[0][i:i + 1], frames[1][i:i + 1])
@@ -1053,6 +1175,9 @@ def main(argv=None):
             record(pf)
     for pf in session.flush():
         record(pf)
+    if args.track_lag is not None:
+        for lp in session.lag_tail():                # the last frames' answers, each smoothed with all the frames there are
+            add_lagged(records, lp)
     if args.rts and records:
         add_smoothed(records, session.smoothed())
     with open(args.out, "w") as fp:

@@ -573,6 +573,48 @@ int hupr_pose_track_pairs_f32(const float* heat, long rows, int H, int W, float 
 #define HUPR_SMOOTH_DEGENERATE 3
 int hupr_pose_smooth_rts_f32(const float* states, const int* status, const float* keypoints, long T, long rows, float rate_hz,
                              float accel_psd, float* smoothed, float* velocity, float* covariance, int* flag, hupr_stream_t stream);
+/* Fixed-lag Rauch-Tung-Striebel smoother behind the tracker, one launch per tracked frame (csrc/pose_lag.hip; Moore 1973; Simon,
+ * Optimal State Estimation, ch. 9): the frame is filed in a ring of the last L + 1 tracker states in device memory, and the backward
+ * pass of hupr_pose_smooth_rts_f32 runs over the ring only.  The oldest frame of the ring is the fixed-lag answer: the pose of L = lag
+ * frames ago, smoothed with the L frames seen since.  New, no reference counterpart.  One thread per row, 64 per workgroup, a
+ * latency-bound recurrence of at most L dependent steps.  No LDS, no atomics, no scratch: every output is bit-identical from run to
+ * run and independent of the other rows.  No argument depends on the frame number — the counter is in the lag state —, so the launch
+ * captures into a graph and replays.
+ * track_state : float [rows][16], the tracker's state tensor right after the launch of this frame, whichever of hupr_pose_track_f32,
+ *             hupr_pose_track_assoc_f32 and hupr_pose_track_pairs_f32 wrote it (one layout).  16-byte aligned.  Read only.
+ * status : int [rows], keypoints : float [rows][2], raw_keypoints : float [rows][2], maxval : float [rows]: that launch's status,
+ *             filtered keypoints, raw keypoints and maxima.  Read only: the smoother reports, it feeds nothing back.
+ * lag_state : hupr_pose_lag_state_bytes(rows, lag) bytes, opaque, 16-byte aligned, advanced in place: the ring — [L + 1][rows][16]
+ *             states and, in the same [slot][rows] order, the four other inputs — and a frame counter per row.  All zero means a new
+ *             sequence; a state belongs to one (rows, lag).  hupr_pose_lag_state_bytes returns 0 for rows < 0 or beyond 2^31 / 65 and
+ *             for lag outside 1..64.
+ * rate_hz, accel_psd : those of the filter run, as in hupr_pose_smooth_rts_f32.
+ * Per row, with n the number of frames of this row filed since its lag state was zeroed (the row's own counter; a counter the entry
+ * did not write counts as 0):
+ *   File.  The five inputs of the row are copied into slot n mod (L + 1) of the ring, and the counter becomes n + 1.  (It is kept
+ *     below 2 (L + 1) by subtracting L + 1: n mod (L + 1) and min(n, L) are all that is read of it.)
+ *   Window.  The frames n, n-1, ..., max(n - L, 0) — the ring's slots (n - j) mod (L + 1) — are a recording of T = min(n, L) + 1
+ *     frames, and the backward pass over it is hupr_pose_smooth_rts_f32's word for word, frame n being its frame T-1:
+ *     HUPR_SMOOTH_PASSTHROUGH where the status is HUPR_TRACK_LOST; HUPR_SMOOTH_END at frame n and in front of a successor that is
+ *     HUPR_TRACK_STARTED or HUPR_TRACK_LOST, with xs = x, Ps = P bit for bit; otherwise predict, Cholesky, the two triangular solves,
+ *     xs and Ps, HUPR_SMOOTH_SMOOTHED, or HUPR_SMOOTH_DEGENERATE with the filter's own state, from which the chain goes on.  The two
+ *     kernels compile the same expressions (csrc/pose_rts.h): the tail below is hupr_pose_smooth_rts_f32 over the same T frames bit
+ *     for bit.  Gains are recomputed in every launch, none is kept in the ring.
+ * Outputs, the tail: slot j = 0..L is frame n - j.  tail_keypoints [L+1][rows][2] = (xs[0], xs[1]), tail_velocity [L+1][rows][2] =
+ *   (xs[2], xs[3]) per second, tail_covariance [L+1][rows][3] = (Ps00, Ps01, Ps11), tail_flag [L+1][rows] int; and the filter's record
+ *   of the same frames as it was filed: tail_filtered [L+1][rows][2], tail_raw [L+1][rows][2], tail_status [L+1][rows] int,
+ *   tail_scores [L+1][rows].  Slot 0 is the newest frame, always HUPR_SMOOTH_END or HUPR_SMOOTH_PASSTHROUGH: the filter itself.  Slot
+ *   L is the fixed-lag answer, the pose of frame n - L.  A slot j > n — the frame does not exist yet — holds zeros in all eight and
+ *   the flag HUPR_SMOOTH_EMPTY.  After the last frame of a sequence the slots L-1 .. 0 are the answers still owed, each smoothed with
+ *   all the frames there are.
+ * Returns -1 (HUPR_ERR_ARG) before any launch for a null pointer, lag outside 1..64, rows < 0 or beyond 2^31 / 65, track_state or
+ * lag_state not 16-byte aligned, rate_hz not positive and finite, accel_psd negative or not finite.  rows == 0 is a no-op. */
+#define HUPR_SMOOTH_EMPTY 4
+size_t hupr_pose_lag_state_bytes(long rows, int lag);
+int hupr_pose_smooth_lag_f32(const float* track_state, const int* status, const float* keypoints, const float* raw_keypoints,
+                             const float* maxval, long rows, int lag, float rate_hz, float accel_psd, float* lag_state,
+                             float* tail_keypoints, float* tail_velocity, float* tail_covariance, int* tail_flag, float* tail_filtered,
+                             float* tail_raw, int* tail_status, float* tail_scores, hupr_stream_t stream);
 /* Scene occupancy (csrc/cfar.hip): cell-averaging constant-false-alarm-rate detection on the (range, azimuth) maps of a sensor-frame's
  * elevation-mean planes, a per-frame summary of the detections, and a presence gate over the summaries (Rohling 1983; Richards,
  * Fundamentals of Radar Signal Processing, ch. 6).  New, no reference counterpart.  One workgroup per frame, 48 KB of LDS, no atomics,
