@@ -2,7 +2,8 @@
 // heat-map peaks (pose_assoc.hip), the one that assigns left / right partner rows jointly (pose_pairs.hip) and the Rauch-Tung-Striebel
 // smoother that runs backwards over their recorded states (pose_smooth.hip).  The status codes are the HUPR_TRACK_* / HUPR_SMOOTH_*
 // of include/hupr.h.  The trackers share one statement of the filter: the measurement read off the heat-map, predict, gate, Joseph
-// update, the end of the frame and its stores.
+// update, the end of the frame and its stores.  The likelihood
+// kernel behind tools/calibrate.py (pose_fit.hip) runs the same frame for many parameter candidates at once.
 #pragma once
 #include "hupr_common.h"
 #include "pose_refine.h"
@@ -187,11 +188,10 @@ __device__ __forceinline__ int track_coast(Track& t, const Tracker& f, int coast
     return coasted;
 }
 
-// The end of the frame, by one lane: a row without a live track starts one from ``z`` if that is usable, else its state is all zero;
-// then the state and the five outputs of row r are stored.  ``code`` is the status so far (HUPR_TRACK_LOST without a live track);
-// -> the status stored.
-__device__ __forceinline__ int track_finish(Track& t, const Measurement& z, const Tracker& f, int code, long r, float* state, float* filtered,
-                                             float* velocity, float* covariance, float* forecast, int* status) {
+// The end of the frame's state logic: a row without a live track starts one from ``z`` if that is usable, else its state is all zero.
+// ``code`` is the status so far (HUPR_TRACK_LOST without a live track); -> the frame's status.  Nothing is stored: the likelihood
+// kernel (pose_fit.hip) runs the frame on registers alone.
+__device__ __forceinline__ int track_end(Track& t, const Measurement& z, const Tracker& f, int code) {
     HUPR_EXACT_FP
     if (!t.live) {
         if (z.usable) {
@@ -207,6 +207,14 @@ __device__ __forceinline__ int track_finish(Track& t, const Measurement& z, cons
         }
         t.coast = 0.f;
     }
+    return code;
+}
+
+// The end of the frame, by one lane: ``track_end``, then the state and the five outputs of row r are stored.  -> the status stored.
+__device__ __forceinline__ int track_finish(Track& t, const Measurement& z, const Tracker& f, int code, long r, float* state, float* filtered,
+                                             float* velocity, float* covariance, float* forecast, int* status) {
+    HUPR_EXACT_FP
+    code = track_end(t, z, f, code);
     float4* s = reinterpret_cast<float4*>(state + r * kTrackFloats);
     s[0] = make_float4(t.x0, t.x1, t.x2, t.x3);
     s[1] = make_float4(t.p00, t.p01, t.p02, t.p03);

@@ -11,6 +11,7 @@ Nothing here computes with torch ops except allocation, views, concatenation of 
 bookkeeping; every kernel is reached through ``runtime.lib()`` and fails loudly without the HIP library.
 """
 import ctypes
+import math
 import os
 import threading
 
@@ -2160,6 +2161,95 @@ def pose_track(heat, ratio, refine=True, track_state=None, tracking=None, presen
                                                 K, sep, floor, rt.ptr(present), group, (ctypes.c_int * group)(*table), swap_cost,
                                                 *map(rt.ptr, out), rt.stream()))
     return out
+
+
+MEAS_FLOATS = 8                     # pose_measure's record of a row and frame: zx, zy, score, m, Sxx, Sxy, Syy, 0
+
+
+def pose_measure(heat, ratio, refine=True, out=None):
+    """heat (..., H, W) fp32 GPU -> (idx int32 (...), maxval (...), raw keypoints (..., 2), meas (..., 8)) in one launch
+    (csrc/pose_fit.hip; the rule is stated beside hupr_pose_measure_f32 in include/hupr.h): the measurement half of ``pose_track``
+    without a filter.  The first three are ``pose_decode``'s bits; ``meas`` = (zx, zy, score, m, Sxx, Sxy, Syy, 0) is the raw keypoint,
+    the maximum and the mass and second central moments of the tracker's covariance window — everything the tracker reads of a
+    frame, so that a recording of it can be run through the filter again under other parameters (``pose_track_nll``).  ``out``: that
+    4-tuple, to write (``_outputs``).  Device tensors, no sync."""
+    heat, lead, rows, H, W = _pose_heat("pose_measure", heat)
+    out = _outputs("pose_measure", out, lead, heat.device, (((), _I32), ((), _F32), ((2,), _F32), ((MEAS_FLOATS,), _F32)))
+    rt.check(rt.lib().hupr_pose_measure_f32(rt.ptr(heat), rows, H, W, float(ratio), int(bool(refine)), *map(rt.ptr, out), rt.stream()))
+    return out
+
+
+def check_track_candidates(params, name="pose_track_nll"):
+    """Parameter candidates for ``pose_track_nll``: anything ``np.asarray`` turns into (G, 3) numbers = (accel_psd, meas_std,
+    heatmap_gain) per candidate, or a tensor (copied to the host) -> a float32 (G, 3) array.  The tracker's rule for the three holds
+    for every candidate — accel_psd and heatmap_gain >= 0, meas_std > 0, all finite as fp32 —, else a ValueError in ``name``'s name:
+    the library entry takes them as device memory and cannot check."""
+    if isinstance(params, torch.Tensor):
+        params = params.detach().cpu().numpy()
+    try:
+        p = np.asarray(params, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("%s needs (G, 3) candidates (accel_psd, meas_std, heatmap_gain), got %r" % (name, params)) from None
+    if p.ndim != 2 or p.shape[1] != 3:
+        raise ValueError("%s needs (G, 3) candidates (accel_psd, meas_std, heatmap_gain), got shape %r" % (name, p.shape))
+    with np.errstate(over="ignore"):
+        p32 = p.astype(np.float32)
+    ok = np.isfinite(p32).all(axis=1) & (p32[:, 0] >= 0) & (p32[:, 1] > 0) & (p32[:, 2] >= 0)
+    if not ok.all():
+        g = int(np.flatnonzero(~ok)[0])
+        raise ValueError("%s: candidate %d = (accel_psd %r, meas_std %r, heatmap_gain %r): accel_psd and heatmap_gain must not be "
+                         "negative, meas_std must be positive, all finite" % ((name, g) + tuple(p[g].tolist())))
+    return p32
+
+
+def outlier_cost(extent):
+    """What a measurement costs the likelihood as an outlier uniform over an image of ``extent`` = (width, height) pixels, in the units
+    of d2 + ln det S: 2 ln(width height / 2 pi) — 18.50 at 256 x 256."""
+    try:
+        w, h = (float(v) for v in extent)
+    except (TypeError, ValueError):
+        raise ValueError("extent must be (width, height) in image pixels, got %r" % (extent,)) from None
+    if not (0 < w < float("inf") and 0 < h < float("inf")):
+        raise ValueError("extent must be (width, height) in image pixels, positive and finite, got %r" % (extent,))
+    return 2.0 * math.log(w * h / (2.0 * math.pi))
+
+
+def pose_track_nll(meas, start, tracking, params, extent, ratio):
+    """The likelihood of a recording under many tracker parameters, in one launch (csrc/pose_fit.hip; the rule is stated beside
+    hupr_pose_track_nll_f32 in include/hupr.h).  ``meas`` (T, ..., 8) fp32 GPU: frame by frame what ``pose_measure`` gave; ``start``
+    (T,) int32 or bool on the same device: non-zero where a frame begins a sequence (every track is zeroed in front of it);
+    ``tracking`` the parameters all candidates share (``rate_hz``, ``gate``, ``max_coast``, ``init_speed_std``, ``min_score`` are
+    read); ``params`` (G, 3) = (accel_psd, meas_std, heatmap_gain) per candidate (``check_track_candidates``: checked on the host,
+    before the upload and any launch); ``extent`` = (width, height) of the image in pixels, which prices an outlier
+    (``outlier_cost``); ``ratio`` image pixels per heat-map pixel, the one ``pose_measure`` was called with — the moments in ``meas``
+    are heat-map pixels squared -> (nll float64 (G, ...): per candidate and row the sum of min(d2 + ln det S, outlier cost) over the
+    frames scored; counts int32 (G, ..., 6): the frames per TRACK_* status in code order, then the frames scored; final_state
+    (G, ..., 16): the track state after the last frame).  Every thread runs the plain ``pose_track`` frame, so a candidate that
+    equals a ``pose_track`` run's parameters ends in that run's state bit for bit.  Device tensors, no sync."""
+    if not isinstance(meas, torch.Tensor) or meas.dtype != _F32 or meas.dim() < 2 or meas.shape[-1] != MEAS_FLOATS:
+        raise ValueError("pose_track_nll needs meas as a (T, ..., %d) fp32 tensor, got %s" % (MEAS_FLOATS, getattr(meas, "shape", type(meas).__name__)))
+    if not meas.is_cuda:
+        raise ValueError("pose_track_nll needs GPU tensors (no CPU fallback), got %s" % meas.device)
+    if tracking is None:
+        raise ValueError("pose_track_nll needs the tracking parameters the candidates share")
+    T, lead = int(meas.shape[0]), tuple(meas.shape[1:-1])
+    if not isinstance(start, torch.Tensor) or start.dtype not in (_I32, torch.bool) or tuple(start.shape) != (T,):
+        raise ValueError("pose_track_nll needs start as a (%d,) int32 or bool tensor, got %s" % (T, getattr(start, "shape", type(start).__name__)))
+    if start.device != meas.device:
+        raise ValueError("start is on %s, meas on %s" % (start.device, meas.device))
+    cand = check_track_candidates(params)
+    cost = outlier_cost(extent)
+    G, rows, dev = cand.shape[0], int(np.prod(lead, dtype=np.int64)), meas.device
+    meas, start = _c(meas), _c(start.to(_I32))
+    nll = torch.empty((G,) + lead, dtype=torch.float64, device=dev)
+    counts = torch.empty((G,) + lead + (6,), dtype=_I32, device=dev)
+    final = torch.empty((G,) + lead + (16,), dtype=_F32, device=dev)
+    table = torch.from_numpy(cand).to(dev)
+    rt.check(rt.lib().hupr_pose_track_nll_f32(rt.ptr(meas), rt.ptr(start), T, rows, float(ratio), float(tracking.rate_hz),
+                                              float(tracking.gate), int(tracking.max_coast), float(tracking.init_speed_std),
+                                              float(tracking.min_score), cost, rt.ptr(table), G, rt.ptr(nll), rt.ptr(counts),
+                                              rt.ptr(final), rt.stream()))
+    return nll, counts, final
 
 
 SMOOTH_SMOOTHED, SMOOTH_END, SMOOTH_PASSTHROUGH, SMOOTH_DEGENERATE = range(4)                   # pose_smooth_rts's flags

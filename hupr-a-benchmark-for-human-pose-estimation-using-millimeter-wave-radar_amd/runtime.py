@@ -74,6 +74,10 @@ SIGNATURES = {
     # fixed-lag smoother behind the tracker, one launch per frame over a ring of its states (csrc/pose_lag.hip)
     "hupr_pose_lag_state_bytes": (c_size_t, [c_long, c_int]),
     "hupr_pose_smooth_lag_f32": (c_int, [c_void_p] * 5 + [c_long, c_int, c_float, c_float] + [c_void_p] * 10),
+    # the tracker's measurement alone, and the likelihood of a recording of it under G parameter candidates (csrc/pose_fit.hip)
+    "hupr_pose_measure_f32": (c_int, [c_void_p, c_long, c_int, c_int, c_float, c_int] + [c_void_p] * 5),
+    "hupr_pose_track_nll_f32": (c_int, [c_void_p, c_void_p, c_long, c_long, c_float, c_float, c_float, c_int, c_float, c_float, c_float,
+                                        c_void_p, c_long] + [c_void_p] * 4),
     # scene occupancy: CA-CFAR detection on the mean planes and the presence gate (csrc/cfar.hip); the table of the first two is host memory
     "hupr_cfar_table_len": (c_int, [c_int, c_int]),
     "hupr_cfar_alpha_table_f32": (c_int, [ctypes.c_double, c_int, c_int, ctypes.POINTER(c_float), c_int]),

@@ -5,6 +5,7 @@ _STREAM = ("PoseStream", "PoseFrame", "StreamSchedule", "stream_window_sources",
            "PoseTracking", "TrackedPoseFrame", "PairedPoseFrame", "TrackingError", "PresenceGate", "PresenceError",
            "InterferenceError", "LaggedPose", "LaggedTrackedPoseFrame", "LaggedPairedPoseFrame")
 _SMOOTH = ("SequenceSmoother", "SmoothedSequence", "TrackHistory", "LagRecord", "jitter")
+_CALIBRATE = ("MeasurementRecord", "TrackingFit", "fit_tracking")
 
 
 def __getattr__(name):          # lazy: Runner pulls in datasets/models
@@ -17,4 +18,7 @@ def __getattr__(name):          # lazy: Runner pulls in datasets/models
     if name in _SMOOTH:         # offline smoothing of tracked sequences (tools/smooth.py)
         from . import smooth
         return getattr(smooth, name)
+    if name in _CALIBRATE:      # fitting the tracker's noise parameters to a recording (tools/calibrate.py)
+        from . import calibrate
+        return getattr(calibrate, name)
     raise AttributeError(name)

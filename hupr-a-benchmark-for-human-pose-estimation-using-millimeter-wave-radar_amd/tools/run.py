@@ -156,7 +156,10 @@ class Runner(BaseRunner):
         Kalman-filtered ones (``track``), the Rauch-Tung-Striebel smoothed ones (``rts``) or the fixed-lag smoothed ones (``lag``:
         every frame smoothed over the ``TEST.temporalLag`` frames behind it, ``SequenceSmoother.smooth_lagged``).  After the AP line
         come an ``MPJPE`` line for the raw, the filtered and the smoothed (``rts``) or lagged (``lag``) keypoints and a ``Jitter``
-        line (``tools.smooth.jitter``) for each of them and for the ground truth.
+        line (``tools.smooth.jitter``) for each of them and for the ground truth.  With ``TEST.temporalFit: true`` the walk also records
+        every frame's measurements, and one more line follows: ``tracker fit:`` the maximum-likelihood ``accel_psd``, ``meas_std`` and
+        ``heatmap_gain`` on them (``tools.calibrate.fit_tracking``), the cost per measurement at the configured and at the fitted
+        values, and the fitted run's status counts.  Nothing is scored again: the values go under ``TEST.tracking`` for the next run.
         ``TEST.presence`` (``tools.stream.presence_setting``): the test set is walked as sequences in the same way, the CA-CFAR
         detector (``functional.cfar_ra``) runs on the horizontal mean planes of every sample's labelled frame (window position G / 2)
         and the presence gate across each sequence, and one more line is printed: ``Presence: <share> of <n> labelled frames present,
@@ -171,7 +174,7 @@ class Runner(BaseRunner):
         temporal = self.temporal
         if temporal is not None:
             smoother = SequenceSmoother(temporal.tracking, self.numKeypoints, self.engine.device,
-                                        lag=temporal.lag if temporal.mode == "lag" else None)
+                                        lag=temporal.lag if temporal.mode == "lag" else None, measurements=temporal.fit)
             walker, boxes, ids = SequenceWalker(), [], []
         gate = self.presence
         if gate is not None:
@@ -259,6 +262,8 @@ class Runner(BaseRunner):
                     print("MPJPE %s: %.3f px (n = %d)" % ((name,) + mean_position_error(gts, self.saveKeypoints([], kp, boxes, ids))[::2]))
                 for name, kp in list(tracks.items()) + [("truth", visited)]:
                     print("Jitter %s: %.3f px" % (name, jitter([kp[a:b] for a, b in walker.segments()])))
+                if temporal.fit:                    # TEST.temporalFit: the values to put under TEST.tracking; nothing is scored again
+                    print(smoother.fit_tracking().line())
             if blanked is not None:
                 print(interference_line("Interference", blanked))
             if gate is not None:

@@ -12,6 +12,10 @@ the frames after it too: a gap the filter coasted through becomes an interpolati
 hupr_pose_smooth_lag_f32: the backward pass over the last L + 1 frames only) and keeps its answers, ``smooth_lagged()`` returns them and
 ``TEST.temporal: lag`` scores them: what a live consumer that waits L frames would have seen.
 
+``SequenceSmoother(..., measurements=True)`` also records every frame's measurements (csrc/pose_fit.hip, ``functional.pose_measure``)
+for ``fit_tracking()``, the maximum-likelihood fit of the tracker's noise parameters (tools/calibrate.py); ``TEST.temporalFit`` asks
+``Runner.eval`` for it.
+
 The smoother is a latency-bound recurrence (one thread per row, T dependent steps); nothing here claims a speed."""
 import math
 
@@ -19,6 +23,7 @@ import numpy as np
 import torch
 
 from .. import functional as F_
+from .calibrate import FITTED, MeasurementRecord, fit_tracking
 from .stream import PoseTracking, TrackingError
 
 FLAGS = ("SMOOTHED", "END", "PASSTHROUGH", "DEGENERATE", "EMPTY")
@@ -142,9 +147,12 @@ class SequenceSmoother:
     ``lag=L`` (an integer in 1..64; None, the default, adds nothing): ``track`` also runs the fixed-lag smoother's launch behind the
     tracker's (``functional.pose_smooth_lag`` on a lag state of its own) and keeps tail slot L, the answer for the frame L calls
     back; ``smooth_lagged()`` returns the fixed-lag answers of every frame tracked so far, those of a sequence's last L frames taken
-    from the tail of its last launch; ``new_sequence()`` takes them before it zeroes the lag state too."""
+    from the tail of its last launch; ``new_sequence()`` takes them before it zeroes the lag state too.
+    ``measurements=True``: ``track`` also launches ``functional.pose_measure`` on the frame's maps and files its measurements in
+    ``record``, a ``MeasurementRecord`` (tools/calibrate.py) that ``fit_tracking`` reads; the frame after ``new_sequence()`` is marked
+    as a sequence's first.  The tracker's own launch and outputs are what they are without it."""
 
-    def __init__(self, tracking, rows, device, lag=None):
+    def __init__(self, tracking, rows, device, lag=None, measurements=False):
         if not isinstance(tracking, PoseTracking):
             raise TrackingError("tracking must be a PoseTracking, got %r" % (tracking,))
         if tracking.gate_on_presence:
@@ -162,6 +170,10 @@ class SequenceSmoother:
             self.lag_state = F_.pose_lag_state(self.rows, self.lag, self.device)
             self.lagged = LagRecord((self.rows,), self.device)
             self._tail, self._run = None, 0                    # the last launch's tail; frames tracked in the current sequence
+        if not isinstance(measurements, bool):
+            raise ValueError("measurements must be True or False, got %r" % (measurements,))
+        self.record = MeasurementRecord((self.rows,), self.device) if measurements else None
+        self._first = True                                     # the next frame starts a sequence
 
     def __len__(self):
         return len(self.history)
@@ -170,6 +182,10 @@ class SequenceSmoother:
         out = F_.pose_track(heat, ratio, refine=refine, track_state=self.state, tracking=self.tracking)
         mx, raw, kp, status = out[1], out[2], out[3], out[7]
         self.history.append(self.state, status, kp, raw, mx)
+        if self.record is not None:
+            self.record.ratio, self.record.extent = float(ratio), (heat.shape[-1] * float(ratio), heat.shape[-2] * float(ratio))
+            self.record.append(F_.pose_measure(heat, ratio, refine=refine)[3], start=self._first)
+            self._first = False
         if self.lag is not None:
             lead = (self.rows,)
             self._tail = F_.pose_smooth_lag(self.state, status.reshape(lead), kp.reshape(lead + (2,)), raw.reshape(lead + (2,)),
@@ -186,14 +202,18 @@ class SequenceSmoother:
     def new_sequence(self):
         self._settle()
         self.state.zero_()
+        self._first = True
         if self.lag is not None:
             self.lag_state.zero_()
             self._run = 0
 
     def clear(self):
-        """Forget the history and the tracks."""
+        """Forget the history, the measurements and the tracks."""
         self.state.zero_()
         self.history.clear()
+        self._first = True
+        if self.record is not None:
+            self.record.clear()
         if self.lag is not None:
             self.lag_state.zero_()
             self.lagged.clear()
@@ -201,6 +221,13 @@ class SequenceSmoother:
 
     def smooth(self):
         return self.history.smooth(self.tracking)
+
+    def fit_tracking(self, fit=FITTED, rounds=3):
+        """``tools.calibrate.fit_tracking`` on the measurements of every frame tracked so far -> TrackingFit; needs
+        ``measurements=True``."""
+        if self.record is None:
+            raise TrackingError("fit_tracking() needs a SequenceSmoother built with measurements=True")
+        return fit_tracking(self.record, self.tracking, fit, rounds)
 
     def smooth_lagged(self):
         """-> SmoothedSequence of the fixed-lag answers of every frame tracked so far: frame k smoothed over the ``lag`` frames behind
@@ -231,11 +258,12 @@ def jitter(keypoints):
 # ---- Runner.eval under TEST.temporal -----------------------------------------------------------------------------------------------------
 class TemporalSetting:
     """``TEST.temporal`` as read by ``temporal_setting``: ``mode`` "track", "rts" or "lag", ``tracking`` the PoseTracking of the run,
-    ``lag`` the frames of ``TEST.temporalLag`` (read by "lag" only)."""
-    __slots__ = ("mode", "tracking", "lag")
+    ``lag`` the frames of ``TEST.temporalLag`` (read by "lag" only), ``fit`` whether ``TEST.temporalFit`` asks for the tracker's noise
+    parameters to be fitted behind the walk (tools/calibrate.py)."""
+    __slots__ = ("mode", "tracking", "lag", "fit")
 
-    def __init__(self, mode, tracking, lag=DEFAULT_LAG):
-        self.mode, self.tracking, self.lag = mode, tracking, lag
+    def __init__(self, mode, tracking, lag=DEFAULT_LAG, fit=False):
+        self.mode, self.tracking, self.lag, self.fit = mode, tracking, lag, fit
 
 
 def temporal_setting(cfg):
@@ -246,7 +274,9 @@ def temporal_setting(cfg):
     ``temporalLag``: an integer in 1..64 frames, absent = 4.  ``tracking``: a mapping of PoseTracking keyword arguments other than
     ``rate_hz``.  All four are checked whatever ``temporal`` says; anything else, and ``TEST.decode: integral`` beside ``track``,
     ``rts`` or ``lag`` (the tracker's measurement is the sub-pixel decode's, as in the live stream), raises here, where the config is
-    read."""
+    read.  ``TEST.temporalFit`` (no key of the reference's YAML either): absent or ``false`` is off; ``true`` needs ``temporal`` to be
+    something other than ``off`` and makes ``Runner.eval`` fit ``accel_psd``, ``meas_std`` and ``heatmap_gain`` to the walked frames'
+    measurements and print them (``tools.calibrate.fit_tracking``); anything but a bool raises here."""
     from ..misc.metrics import decode_setting
     test = getattr(cfg, "TEST", None)
     mode = getattr(test, "temporal", "off")
@@ -277,12 +307,17 @@ def temporal_setting(cfg):
             tracking = tracking.for_joints(cfg.DATASET.idxToJoints)
     except TrackingError as e:
         raise ValueError("TEST.tracking: %s" % e) from None
+    fit = getattr(test, "temporalFit", False)
+    if not isinstance(fit, bool):
+        raise ValueError("TEST.temporalFit must be true or false, got %r" % (fit,))
+    if fit and mode == "off":
+        raise ValueError("TEST.temporalFit: true needs TEST.temporal: track, rts or lag: the fit reads the frames that walk tracks")
     if mode == "off":
         return None
     if decode_setting(cfg) == "integral":
         raise ValueError("TEST.temporal: %s and TEST.decode: integral exclude each other: the tracker's measurement is the sub-pixel "
                          "decode's" % mode)
-    return TemporalSetting(mode, tracking, int(lag))
+    return TemporalSetting(mode, tracking, int(lag), fit)
 
 
 def sequence_and_frame(image_id):

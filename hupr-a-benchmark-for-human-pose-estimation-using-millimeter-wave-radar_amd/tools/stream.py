@@ -185,7 +185,8 @@ class PoseTracking(_PairFields):
     quantile, 2 d.o.f.; the default is the 99.9 % one); ``max_coast`` the number of consecutive frames a track goes on without an
     accepted measurement before it ends; ``init_speed_std`` (pixel / s) the velocity uncertainty of a new track; a joint whose score
     is <= ``min_score`` has no measurement; ``horizon_s`` (s) how far ahead of the filtered pose the forecast looks.  The defaults
-    are guesses: good values for real captures are unmeasured.
+    are guesses: good values for real captures are unmeasured, and ``tools.calibrate.fit_tracking`` (``PoseStream.fit_tracking``,
+    ``TEST.temporalFit``) fits ``accel_psd``, ``meas_std`` and ``heatmap_gain`` to a recording by maximum likelihood.
     ``candidates`` (1..4) > 1: the track chooses its measurement among that many peaks of the heat-map (csrc/pose_assoc.hip; the
     rule is stated beside hupr_pose_track_assoc_f32): the arg-max and the next local maxima that are at least ``peak_ratio`` (in
     (0, 1]) times as high and more than ``min_separation`` heat-map pixels from every peak taken; the one inside the gate with the
@@ -636,11 +637,19 @@ class PoseStream:
     (``LaggedPairedPoseFrame``s with ``pair_swap``): every frame gains ``lagged``, the ``LaggedPose`` of the frame L poses earlier —
     None in the first L emitted frames — and after ``flush()`` ``lag_tail()`` returns the L poses still owed.  The smoother reports
     only: the filter's own outputs are those of a session without ``lag``, bit for bit; ``reset()`` starts its ring anew.  It works
-    with all three tracker launches and with ``history`` and ``presence``.  The default, None, adds nothing."""
+    with all three tracker launches and with ``history`` and ``presence``.  The default, None, adds nothing.
+    ``measurements=True`` (needs ``track``): the session records what the tracker measured, so that its noise parameters can be fitted
+    to the capture afterwards.  Behind the tracker's launch of every push or flush that emits a pose, one launch of
+    csrc/pose_fit.hip (``functional.pose_measure``), inside the same graph replay, writes the frame's measurements — raw keypoint,
+    score and covariance window, 32 bytes per joint — and an eager device-to-device copy behind the replay files them in a
+    ``MeasurementRecord`` (tools/calibrate.py).  ``fit_tracking()`` then returns the maximum-likelihood ``accel_psd``, ``meas_std`` and
+    ``heatmap_gain`` over everything recorded (``tools.calibrate.fit_tracking``); ``reset()`` keeps the record and marks the next
+    pose as a sequence's first.  It reports only: the tracker's outputs are those of a session without it, bit for bit.  The default,
+    False, adds nothing."""
 
     def __init__(self, model, cfg, lanes=1, lookahead=None, graph=True, device=None, decode="argmax", smooth=None, track=None,
                  predict_now=False, decode_radius=None, tdm_compensation=False, history=False, presence=None, interference=None,
-                 lag=None):
+                 lag=None, measurements=False):
         D = cfg.DATASET
         self.G = D.numGroupFrames
         self.schedule = StreamSchedule(self.G, lookahead)
@@ -656,6 +665,10 @@ class PoseStream:
         if history and track is None:
             raise TrackingError("history needs track: it records the tracker's states for smoothed()")
         self.lag = check_lag(lag, track)
+        if not isinstance(measurements, bool):
+            raise StreamError("measurements must be True or False, got %r" % (measurements,))
+        if measurements and track is None:
+            raise TrackingError("measurements needs track: it records what the tracker measured for fit_tracking()")
         if track is not None:                                  # pair_swap: the partner table of this config's joints
             track = track.for_joints(getattr(D, "idxToJoints", range(D.numKeypoints)))
         self.track = track.with_horizon(self.lookahead / track.rate_hz) if predict_now else track
@@ -727,6 +740,15 @@ class PoseStream:
             if history:
                 from .smooth import TrackHistory
                 self._history = TrackHistory((lanes, self.K), dev)
+            # the tracker's measurements alone (csrc/pose_fit.hip) behind it: the frame's record, the launch's own copy of the decode,
+            # and the recording; _fresh: the next pose is the first of a sequence
+            self._meas = self._meas_decode = self._record = None
+            if measurements:
+                from .calibrate import MeasurementRecord
+                self._meas = torch.zeros((lanes, self.K, F_.MEAS_FLOATS), dtype=torch.float32, device=dev)
+                self._meas_decode = (torch.empty_like(self._idx), torch.empty_like(self._mx), torch.empty_like(self._kp))
+                self._record = MeasurementRecord((lanes, self.K), dev, ratio=self.ratio, extent=(self.W * self.ratio, self.H * self.ratio))
+            self._fresh = True
             # scene occupancy (csrc/cfar.hip): the threshold table, the detector's summary, the gate's state and verdict
             self._alpha = self._occ = self._gstate = self._present = None
             if presence is not None:
@@ -791,6 +813,8 @@ class PoseStream:
             F_.pose_track(maps, self.ratio, refine, self._tstate, t, self._present if t.gate_on_presence else None, out=out)
             if self.lag is not None:                   # reads what the tracker left, writes its own ring and tail only
                 F_.pose_smooth_lag(self._tstate, self._status, self._kp, self._raw, self._mx, self._lstate, t, self.lag, out=self._tail)
+            if self._meas is not None:                 # reads the maps only, writes buffers of its own
+                F_.pose_measure(maps, self.ratio, refine, out=self._meas_decode + (self._meas,))
         elif self.decode == "integral":
             F_.pose_decode_integral(maps, self.ratio, self.decode_radius, self._fstate, f, out=out)
         elif self._fused:
@@ -820,6 +844,9 @@ class PoseStream:
     def _frame(self, center, out, pushed=True):
         if self._history is not None:                          # the emitted pose into the history: eager copies behind the launches
             self._history.append(self._tstate, self._status, self._kp, self._raw, self._mx)
+        if self._record is not None:                           # likewise the emitted pose's measurements
+            self._record.append(self._meas, start=self._fresh)
+            self._fresh = False
         fields = dict(frame=center, keypoints=self._kp, scores=self._mx, indices=self._idx, heatmap=out[0], gcn_heatmap=out[1],
                       raw_keypoints=self._raw, velocity=self._vel, present=self._present, occupancy=self._occ,
                       interference=self._if_stats if pushed else None)
@@ -898,6 +925,7 @@ class PoseStream:
         self.schedule.reset()
         if self._history is not None:
             self._history.clear()
+        self._fresh = True                                     # the measurement record stays: a fit may span sequences
 
     def lag_tail(self):
         """After ``flush()``: the ``min(lag, poses emitted)`` fixed-lag poses still owed at the end of a sequence, oldest first -> a
@@ -917,6 +945,22 @@ class PoseStream:
             raise TrackingError("smoothed() needs a session built with track=... and history=True")
         with torch.cuda.device(self.device):
             return self._history.smooth(self.track)
+
+    @property
+    def measurements(self):
+        """The session's ``MeasurementRecord`` (None without ``measurements=True``): one frame per pose emitted since construction."""
+        return self._record
+
+    def fit_tracking(self, fit=("accel_psd", "meas_std", "heatmap_gain"), rounds=3):
+        """The maximum-likelihood tracker noise parameters on the poses recorded so far -> ``tools.calibrate.TrackingFit``, whose
+        ``tracking`` is a copy of the session's with the fitted values (``tools.calibrate.fit_tracking``: ``rounds`` launches of
+        csrc/pose_fit.hip and a host read-back each).  The session goes on with the parameters it was built with.  Needs
+        ``measurements=True`` and at least one emitted pose."""
+        if self._record is None:
+            raise TrackingError("fit_tracking() needs a session built with track=... and measurements=True")
+        from .calibrate import fit_tracking
+        with torch.cuda.device(self.device):
+            return fit_tracking(self._record, self.track, fit, rounds)
 
 
 # ---- command ---------------------------------------------------------------------------------------------------------------------
@@ -957,6 +1001,9 @@ def parse(argv=None):
                    "record gains lagged, lagged_velocity, lagged_covariance and lagged_flag, N frames after its own pose")
     p.add_argument("--rts", action="store_true", help="with --track: after the flush, smooth the whole recording backwards (Rauch-Tung-"
                    "Striebel); every record gains smoothed, smoothed_velocity, smoothed_covariance and smoothed_flag")
+    p.add_argument("--fit-tracker", action="store_true", help="with --track: record what the tracker measured and, after the flush, print "
+                   "the PoseTracking(...) whose accel_psd, meas_std and heatmap_gain are the maximum-likelihood fit to this capture; "
+                   "nothing is written for it")
     p.add_argument("--tdm-compensation", action="store_true", help="compensate the TDM Doppler phase in the FFT chain (weights trained "
                    "with DATASET.tdmCompensation)")
     p.add_argument("--presence", action="store_true", help="scene occupancy: CA-CFAR detection on the centre frame and a presence gate; "
@@ -1015,7 +1062,8 @@ def parse(argv=None):
 TRACK_FLAGS = (("--predict-now", "predict_now"), ("--accel-psd", "accel_psd"), ("--gate", "gate"), ("--max-coast", "max_coast"),
                ("--rts", "rts"), ("--track-candidates", "track_candidates"), ("--track-separation", "track_separation"),
                ("--track-peak-ratio", "track_peak_ratio"), ("--track-on-presence", "track_on_presence"),
-               ("--track-pairs", "track_pairs"), ("--track-swap-cost", "track_swap_cost"), ("--track-lag", "track_lag"))
+               ("--track-pairs", "track_pairs"), ("--track-swap-cost", "track_swap_cost"), ("--track-lag", "track_lag"),
+               ("--fit-tracker", "fit_tracker"))
 INTERFERENCE_FLAGS = (("--interference-threshold", "interference_threshold"), ("--interference-guard", "interference_guard"),
                       ("--interference-fill", "interference_fill"))
 
@@ -1142,7 +1190,7 @@ def main(argv=None):
                          smooth=PoseSmoothing(args.rate) if args.smooth else None, track=tracking_from_args(args),
                          predict_now=args.predict_now, decode_radius=args.decode_radius, tdm_compensation=args.tdm_compensation,
                          history=args.rts, presence=presence_from_args(args), interference=interference_from_args(args),
-                         lag=args.track_lag)
+                         lag=args.track_lag, measurements=args.fit_tracker)
     records = []
 
     def record(pf):
@@ -1183,6 +1231,10 @@ def main(argv=None):
     with open(args.out, "w") as fp:
         json.dump(records, fp)
     print("%d frames -> %s" % (len(records), args.out))
+    if args.fit_tracker and records:                 # printed, not written: the values are for the next run's --accel-psd and TEST.tracking
+        fitted = session.fit_tracking()
+        print(fitted.line())
+        print(fitted.tracking)
     return records
 
 

@@ -615,6 +615,52 @@ int hupr_pose_smooth_lag_f32(const float* track_state, const int* status, const 
                              const float* maxval, long rows, int lag, float rate_hz, float accel_psd, float* lag_state,
                              float* tail_keypoints, float* tail_velocity, float* tail_covariance, int* tail_flag, float* tail_filtered,
                              float* tail_raw, int* tail_status, float* tail_scores, hupr_stream_t stream);
+/* The measurement half of hupr_pose_track_f32 without a filter, in one launch (csrc/pose_fit.hip): what a recording has to keep of a
+ * frame so that the tracker can be run over it again, under any parameters.  New, no reference counterpart.  One 64-lane wave per
+ * row, no scratch, no LDS.
+ * heat, idx, maxval and raw_keypoints are those of hupr_pose_decode_f32 for the same refine, bit for bit.
+ * meas : float [rows][8] = (zx, zy, score, m, Sxx, Sxy, Syy, 0), 16-byte aligned: z = raw_keypoints and score = maxval of the row, and
+ *   the mass m and the second central moments of the radius-3 window around the arg-max pixel exactly as hupr_pose_track_f32 computes
+ *   them (m = 0 and NaN moments where maxval <= 0).  With these eight floats and (ratio, meas_std, heatmap_gain, min_score) the
+ *   measurement of hupr_pose_track_f32 — z, R = ratio^2 heatmap_gain S + meas_std^2 I, usable or not — is determined, bit for bit.
+ * Returns -1 (HUPR_ERR_ARG) before any launch for a null pointer, H or W below 1, rows or H * W beyond 2^31, meas not 16-byte aligned.
+ * rows == 0 is a no-op. */
+int hupr_pose_measure_f32(const float* heat, long rows, int H, int W, float ratio, int refine, int* idx, float* maxval,
+                          float* raw_keypoints, float* meas, hupr_stream_t stream);
+/* The likelihood of a whole recording of hupr_pose_measure_f32 under G candidate parameter triples, in one launch (csrc/pose_fit.hip):
+ * the search of a maximum-likelihood fit of the tracker's noise parameters (Bar-Shalom, Li & Kirubarajan 2001, ch. 5 and 11.6; Abbeel
+ * et al., RSS 2005).  New, no reference counterpart.  One thread per (candidate, row), a wave being 64 candidates of one row: the
+ * record is read with wave-uniform loads, and each thread runs a recurrence of T dependent frames on registers.  No LDS, no atomics, no
+ * scratch: each thread adds its costs in frame order, and every output is bit-identical from run to run.
+ * meas  : float [T][rows][8], frame by frame what hupr_pose_measure_f32 wrote; 16-byte aligned.  Read only.
+ * start : int [T]; a non-zero entry marks the first frame of a sequence: every row's track is zeroed in front of it (what a caller of
+ *   hupr_pose_track_f32 does by zeroing the state between two recordings).  The tracks are all zero in front of frame 0 in any case.
+ * ratio, rate_hz, gate, max_coast, init_speed_std, min_score : hupr_pose_track_f32's, shared by all candidates; horizon_s plays no part.
+ * params : DEVICE memory, float [G][3] = (accel_psd, meas_std, heatmap_gain) of candidate g.  hupr_pose_track_f32's rule for the three
+ *   (accel_psd and heatmap_gain >= 0, meas_std > 0, all finite) is the caller's to check before the upload: the entry cannot read them.
+ * Per (candidate g, row r), for t = 0 .. T-1, the frame of hupr_pose_track_f32 with the same device functions in the same order:
+ *   1. start[t] != 0: the track becomes all zero.
+ *   2. The measurement z, R and usable from meas[t][r] under the candidate's meas_std and heatmap_gain.
+ *   3. Live track: predict; nu, S, det S and d2; ``valid`` iff usable, det S > 0 and finite.  Accepted iff valid and d2 <= gate: the
+ *      Joseph update; otherwise the track coasts or ends as in hupr_pose_track_f32.
+ *   4. No live track (also one that ended in this frame): a usable measurement starts one, otherwise the state is all zero.
+ *   Cost: on every frame where the track was live in front of step 3 and the gate was valid, accepted or not,
+ *     c = fminf(d2 + logf(det S), outlier_cost)  (fp32)
+ *   is added to a double.  d2 + ln det S is minus twice the Gaussian log-likelihood of the innovation up to 2 ln 2 pi; outlier_cost is
+ *   what a measurement costs as an outlier uniform over the image, 2 ln(image area / 2 pi) in the same units, so that a candidate
+ *   whose tiny R and Q gate everything out pays outlier_cost per frame instead of nothing.  A frame that starts a track or has no
+ *   usable measurement adds nothing.
+ * Outputs: nll [G][rows] double, the sums; counts [G][rows][6] int = the number of frames with status HUPR_TRACK_UPDATED,
+ *   COASTED_MISSING, COASTED_GATED, STARTED, LOST (code order), then the number of frames scored; final_state_or_null
+ *   [G][rows][16], the state after the last frame in hupr_pose_track_f32's layout, 16-byte aligned: for a candidate that equals the
+ *   parameters of a hupr_pose_track_f32 run over the same frames, that run's state bit for bit.
+ * G == 0 or rows == 0 is a no-op; T == 0 with G > 0 zeroes the outputs and launches nothing.
+ * Returns -1 (HUPR_ERR_ARG) before any launch for a null required pointer, T, rows or G negative, T or rows beyond 2^31, G beyond 2^22,
+ * meas or final_state not 16-byte aligned, hupr_pose_track_f32's errors for the shared parameters, ratio not positive and finite,
+ * outlier_cost NaN. */
+int hupr_pose_track_nll_f32(const float* meas, const int* start, long T, long rows, float ratio, float rate_hz, float gate, int max_coast,
+                            float init_speed_std, float min_score, float outlier_cost, const float* params, long G, double* nll,
+                            int* counts, float* final_state_or_null, hupr_stream_t stream);
 /* Scene occupancy (csrc/cfar.hip): cell-averaging constant-false-alarm-rate detection on the (range, azimuth) maps of a sensor-frame's
  * elevation-mean planes, a per-frame summary of the detections, and a presence gate over the summaries (Rohling 1983; Richards,
  * Fundamentals of Radar Signal Processing, ch. 6).  New, no reference counterpart.  One workgroup per frame, 48 KB of LDS, no atomics,
