@@ -2047,6 +2047,13 @@ def pose_track_state(rows, device):
     return _pose_state(rt.lib().hupr_pose_track_state_bytes, rows, device)
 
 
+def pose_imm_state(rows, device):
+    """A zero-filled ("never seen") state of the two-model tracker (``pose_track`` with ``tracking.accel_psd_moving``) for ``rows``
+    rows: (rows, 32) fp32 = the still model's x, y, vx, vy and covariance triangle, the moving model's same 14, the two mode
+    probabilities, live, coast."""
+    return _pose_state(rt.lib().hupr_pose_track_imm_state_bytes, rows, device)
+
+
 MAX_CANDIDATES = 4                  # of pose_track's association and of pose_peaks
 
 
@@ -2105,6 +2112,19 @@ def pose_peaks(heat, ratio, K, min_separation=3, peak_ratio=0.25, refine=True):
     return xy, score, index, count
 
 
+def _present_group(present, lead, device):
+    """``pose_track``'s ``present`` flags checked against the lead shape of its heat-maps -> rows per flag (1 without flags)."""
+    if present is None:
+        return 1
+    if (not isinstance(present, torch.Tensor) or present.dtype != torch.int32 or tuple(present.shape) != lead[:-1]
+            or not present.is_contiguous()):
+        raise ValueError("present must be a contiguous int32 tensor of shape %r (one flag per group of %d rows)"
+                         % (lead[:-1], lead[-1] if lead else 1))
+    if present.device != device:
+        raise ValueError("present is on %s, the heat-maps on %s" % (present.device, device))
+    return lead[-1] if lead else 1
+
+
 def pose_track(heat, ratio, refine=True, track_state=None, tracking=None, present=None, out=None):
     """heat (..., H, W) fp32 GPU -> (idx int32 (...), maxval (...), raw keypoints (..., 2), filtered keypoints (..., 2), velocity
     (..., 2), position covariance (..., 3) = (Pxx, Pxy, Pyy), forecast (..., 2), status int32 (...)) in one launch
@@ -2120,34 +2140,44 @@ def pose_track(heat, ratio, refine=True, track_state=None, tracking=None, presen
     With ``tracking.pair_swap`` the launch is the pair tracker's (csrc/pose_pairs.hip, hupr_pose_track_pairs_f32): the last lead axis
     of ``heat`` is the group of joints, ``tracking.pairs`` names every joint's partner in it (itself for a joint without one) and
     ``tracking.swap_cost`` prices a peak from the partner's map; partner rows share the peaks of both maps.  It returns those twelve
-    plus source int32 (...): 0 the measurement came from the row's own map, 1 from its partner's, -1 none; ``out`` is that 13-tuple."""
+    plus source int32 (...): 0 the measurement came from the row's own map, 1 from its partner's, -1 none; ``out`` is that 13-tuple.
+    With ``tracking.accel_psd_moving`` (not None) the launch is the two-model tracker's (csrc/pose_imm.hip, hupr_pose_track_imm_f32):
+    a still filter with ``accel_psd`` and a moving one with ``accel_psd_moving`` run on the arg-max measurement, coupled by
+    ``tracking.switch_prob`` and started with ``tracking.moving_prior``; ``track_state`` is ``pose_imm_state``'s, ``present`` is
+    allowed, ``candidates`` > 1 and ``pair_swap`` are not.  It returns the eight outputs — the mixture of the two models — plus moving
+    (...): the probability of the moving model, 0 without a live track; ``out`` is that 9-tuple."""
     heat, lead, rows, H, W = _pose_heat("pose_track", heat)
     if track_state is None or tracking is None:
         raise ValueError("pose_track needs its track_state and its tracking parameters")
+    imm = getattr(tracking, "accel_psd_moving", None) is not None
+    state_bytes, state_name = ((rt.lib().hupr_pose_track_imm_state_bytes, "pose_imm_state") if imm else
+                               (rt.lib().hupr_pose_track_state_bytes, "pose_track_state"))
     if (not isinstance(track_state, torch.Tensor) or track_state.dtype != torch.float32 or not track_state.is_contiguous()
-            or track_state.numel() * 4 != int(rt.lib().hupr_pose_track_state_bytes(rows))):
-        raise ValueError("track_state must be the fp32 tensor pose_track_state(%d, device) returns" % rows)
+            or track_state.numel() * 4 != int(state_bytes(rows))):
+        raise ValueError("track_state must be the fp32 tensor %s(%d, device) returns" % (state_name, rows))
     if track_state.device != heat.device:
         raise ValueError("track_state is on %s, the heat-maps on %s" % (track_state.device, heat.device))
     params = tuple(int(getattr(tracking, k)) if k == "max_coast" else float(getattr(tracking, k)) for k in _TRACK_PARAMS)
     slots = (((), _I32), ((), _F32)) + (((2,), _F32),) * 3 + (((3,), _F32), ((2,), _F32), ((), _I32))
     K = getattr(tracking, "candidates", 1)
     paired = getattr(tracking, "pair_swap", False)
+    if imm:
+        if K != 1 or paired:
+            raise ValueError("pose_track: accel_psd_moving goes with the arg-max measurement only, not with candidates > 1 or pair_swap")
+        group = _present_group(present, lead, heat.device)
+        out = _outputs("pose_track", out, lead, heat.device, slots + (((), _F32),))
+        rt.check(rt.lib().hupr_pose_track_imm_f32(rt.ptr(heat), rows, H, W, float(ratio), int(bool(refine)), rt.ptr(track_state), *params,
+                                                  float(tracking.accel_psd_moving), float(getattr(tracking, "switch_prob", 0.05)),
+                                                  float(getattr(tracking, "moving_prior", 0.5)), rt.ptr(present), group,
+                                                  *map(rt.ptr, out), rt.stream()))
+        return out
     if K == 1 and present is None and not paired:
         out = _outputs("pose_track", out, lead, heat.device, slots)
         rt.check(rt.lib().hupr_pose_track_f32(rt.ptr(heat), rows, H, W, float(ratio), int(bool(refine)), rt.ptr(track_state), *params,
                                               *map(rt.ptr, out), rt.stream()))
         return out
     K, sep, floor = check_peaks(K, getattr(tracking, "min_separation", 3), getattr(tracking, "peak_ratio", 0.25), "pose_track")
-    group = 1
-    if present is not None:
-        if (not isinstance(present, torch.Tensor) or present.dtype != torch.int32 or tuple(present.shape) != lead[:-1]
-                or not present.is_contiguous()):
-            raise ValueError("present must be a contiguous int32 tensor of shape %r (one flag per group of %d rows)"
-                             % (lead[:-1], lead[-1] if lead else 1))
-        if present.device != heat.device:
-            raise ValueError("present is on %s, the heat-maps on %s" % (present.device, heat.device))
-        group = lead[-1] if lead else 1
+    group = _present_group(present, lead, heat.device)
     slots += (((K, 2), _F32), ((K,), _F32), ((), _I32), ((), _I32))
     if not paired:
         out = _outputs("pose_track", out, lead, heat.device, slots)

@@ -69,6 +69,10 @@ SIGNATURES = {
     "hupr_pose_track_pairs_f32": (c_int, [c_void_p, c_long, c_int, c_int, c_float, c_int, c_void_p] + [c_float] * 5 + [c_int] +
                                   [c_float] * 3 + [c_int, c_int, c_float, c_void_p, c_int, ctypes.POINTER(c_int), c_float] +
                                   [c_void_p] * 14),
+    # the tracker with a still and a moving model per joint, interacting-multiple-model (csrc/pose_imm.hip)
+    "hupr_pose_track_imm_state_bytes": (c_size_t, [c_long]),
+    "hupr_pose_track_imm_f32": (c_int, [c_void_p, c_long, c_int, c_int, c_float, c_int, c_void_p] + [c_float] * 5 + [c_int] +
+                                [c_float] * 6 + [c_void_p, c_int] + [c_void_p] * 10),
     # Rauch-Tung-Striebel smoother over a recorded run of the tracker (csrc/pose_smooth.hip)
     "hupr_pose_smooth_rts_f32": (c_int, [c_void_p] * 3 + [c_long, c_long, c_float, c_float] + [c_void_p] * 5),
     # fixed-lag smoother behind the tracker, one launch per frame over a ring of its states (csrc/pose_lag.hip)

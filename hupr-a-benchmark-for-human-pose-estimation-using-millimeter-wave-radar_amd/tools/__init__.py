@@ -3,8 +3,9 @@ from .optim import FusedAdam, FusedSGD  # noqa: F401
 _STREAM = ("PoseStream", "PoseFrame", "StreamSchedule", "stream_window_sources", "StreamError", "LookaheadError",
            "FrameShapeError", "FrameDtypeError", "StreamEndedError", "PoseSmoothing", "DecodeError", "SmoothingError",
            "PoseTracking", "TrackedPoseFrame", "PairedPoseFrame", "TrackingError", "PresenceGate", "PresenceError",
-           "InterferenceError", "LaggedPose", "LaggedTrackedPoseFrame", "LaggedPairedPoseFrame")
-_SMOOTH = ("SequenceSmoother", "SmoothedSequence", "TrackHistory", "LagRecord", "jitter")
+           "InterferenceError", "LaggedPose", "LaggedTrackedPoseFrame", "LaggedPairedPoseFrame",
+           "ManeuveringPoseFrame")
+_SMOOTH = ("SequenceSmoother", "SmoothedSequence", "TrackHistory", "LagRecord", "ManeuverHistory", "jitter")
 _CALIBRATE = ("MeasurementRecord", "TrackingFit", "fit_tracking")
 
 

@@ -156,6 +156,8 @@ def search(evaluate, tracking, fit=FITTED, rounds=3):
             before, start_counts = costs[at] / max(int(counts[at, 5]), 1), tuple(int(c) for c in counts[at])
         values = dict(zip(FITTED, (float(v) for v in grid[best])))
         step = step ** 0.25
+    if tracking.maneuvers:                                  # two models: the single-model accel_psd fits neither, both stay as given
+        values["accel_psd"] = float(tracking.accel_psd)
     fitted = tracking._copy(**values)
     after = costs[best] / max(int(counts[best, 5]), 1)
     return TrackingFit(fitted, (float(before), float(after)), tuple(int(c) for c in counts[best]), (grid, costs), start_counts)
@@ -173,7 +175,9 @@ def fit_tracking(record, tracking, fit=FITTED, rounds=3):
     starting cost.  One host read-back per round.
     The fit is defined for the plain tracker's measurement, the arg-max peak: a ``tracking`` with ``candidates`` > 1, ``pair_swap`` or
     ``gate_on_presence`` is fitted as the plain tracker — one candidate, no partner rows, no presence flags — and the three fitted
-    numbers are carried over into the copy, whose other settings stay."""
+    numbers are carried over into the copy, whose other settings stay.  A ``tracking`` with ``accel_psd_moving`` is fitted as the
+    plain single-model tracker too, and only ``meas_std`` and ``heatmap_gain`` are carried over: ``accel_psd`` and
+    ``accel_psd_moving`` stay as given (fitting the two models by likelihood is not built)."""
     if not isinstance(record, MeasurementRecord):
         raise TrackingError("record must be a MeasurementRecord, got %r" % (record,))
     if record.ratio is None or record.extent is None:

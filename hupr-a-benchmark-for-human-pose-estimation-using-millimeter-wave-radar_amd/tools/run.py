@@ -160,6 +160,9 @@ class Runner(BaseRunner):
         every frame's measurements, and one more line follows: ``tracker fit:`` the maximum-likelihood ``accel_psd``, ``meas_std`` and
         ``heatmap_gain`` on them (``tools.calibrate.fit_tracking``), the cost per measurement at the configured and at the fitted
         values, and the fitted run's status counts.  Nothing is scored again: the values go under ``TEST.tracking`` for the next run.
+        With ``TEST.tracking.accel_psd_moving`` (``track`` only) the walk runs the two-model tracker, the filtered keypoints are the
+        mixture of its models, and one more line follows the jitter: ``Moving:`` the mean probability of the moving model over the
+        joints and frames with a live track.
         ``TEST.presence`` (``tools.stream.presence_setting``): the test set is walked as sequences in the same way, the CA-CFAR
         detector (``functional.cfar_ra``) runs on the horizontal mean planes of every sample's labelled frame (window position G / 2)
         and the presence gate across each sequence, and one more line is printed: ``Presence: <share> of <n> labelled frames present,
@@ -262,6 +265,8 @@ class Runner(BaseRunner):
                     print("MPJPE %s: %.3f px (n = %d)" % ((name,) + mean_position_error(gts, self.saveKeypoints([], kp, boxes, ids))[::2]))
                 for name, kp in list(tracks.items()) + [("truth", visited)]:
                     print("Jitter %s: %.3f px" % (name, jitter([kp[a:b] for a, b in walker.segments()])))
+                if temporal.tracking.maneuvers:     # TEST.tracking.accel_psd_moving: how much of the time the moving model carried the pose
+                    print("Moving: %.3f mean probability of the moving model (n = %d live joints)" % smoother.history.moving_mean())
                 if temporal.fit:                    # TEST.temporalFit: the values to put under TEST.tracking; nothing is scored again
                     print(smoother.fit_tracking().line())
             if blanked is not None:

@@ -114,6 +114,25 @@ class TrackHistory:
         return SmoothedSequence(kp, vel, cov, flag, b["filtered"].clone(), b["raw"].clone(), b["status"].clone(), b["scores"].clone())
 
 
+class ManeuverHistory(TrackHistory):
+    """The per-frame record of the two-model tracker (``PoseTracking.accel_psd_moving``): status, filtered and raw keypoints, maxima
+    and ``moving``, the probability of the moving model.  No states: the smoothers run over a single model's, so ``smooth`` raises."""
+    _FIELDS = TrackHistory._FIELDS[1:] + (("moving", (), torch.float32),)
+
+    def append(self, state, status, filtered, raw, scores, moving):
+        self._append((status, filtered, raw, scores, moving))
+
+    def smooth(self, tracking):
+        raise TrackingError("no smoothing with PoseTracking.accel_psd_moving: the Rauch-Tung-Striebel kernels smooth a single model's states")
+
+    def moving_mean(self):
+        """-> (the mean ``moving`` over the rows and frames with a live track (status not LOST), their number); synchronises."""
+        b = self._views()
+        live = b["status"] != F_.TRACK_LOST
+        n = int(live.sum().item())
+        return (float(b["moving"][live].double().mean().item()) if n else float("nan")), n
+
+
 class LagRecord(TrackHistory):
     """The fixed-lag answers of the frames of a ``TrackHistory``, position by position: ``append(tail)`` takes a new frame with the
     tail of its launch (``functional.pose_smooth_lag``) — the frame enters with tail slot 0, the filter's own pose, and the frame
@@ -150,7 +169,10 @@ class SequenceSmoother:
     from the tail of its last launch; ``new_sequence()`` takes them before it zeroes the lag state too.
     ``measurements=True``: ``track`` also launches ``functional.pose_measure`` on the frame's maps and files its measurements in
     ``record``, a ``MeasurementRecord`` (tools/calibrate.py) that ``fit_tracking`` reads; the frame after ``new_sequence()`` is marked
-    as a sequence's first.  The tracker's own launch and outputs are what they are without it."""
+    as a sequence's first.  The tracker's own launch and outputs are what they are without it.
+    With ``tracking.accel_psd_moving`` the tracker is the two-model one (csrc/pose_imm.hip) on a state of 32 floats per row: ``track``
+    returns its nine outputs, and ``history`` (a ``ManeuverHistory``) records keypoints, status, raw keypoints, scores and ``moving``;
+    ``lag``, ``smooth()`` and ``smooth_lagged()`` raise, because the smoothers run over a single model's states."""
 
     def __init__(self, tracking, rows, device, lag=None, measurements=False):
         if not isinstance(tracking, PoseTracking):
@@ -162,9 +184,11 @@ class SequenceSmoother:
         if tracking.pair_swap and (tracking.pairs is None or len(tracking.pairs) != rows):
             raise TrackingError("PoseTracking.pair_swap needs pairs for the %d rows of a frame (PoseTracking.for_joints), got %r"
                                 % (rows, tracking.pairs))
+        if tracking.maneuvers and lag is not None:
+            raise TrackingError("lag and PoseTracking.accel_psd_moving exclude each other: the smoother runs over a single model's states")
         self.tracking, self.rows, self.device = tracking, int(rows), torch.device(device)
-        self.state = F_.pose_track_state(self.rows, self.device)
-        self.history = TrackHistory((self.rows,), self.device)
+        self.state = (F_.pose_imm_state if tracking.maneuvers else F_.pose_track_state)(self.rows, self.device)
+        self.history = (ManeuverHistory if tracking.maneuvers else TrackHistory)((self.rows,), self.device)
         self.lag = None if lag is None else F_.check_lag(lag, "SequenceSmoother: lag")
         if self.lag is not None:
             self.lag_state = F_.pose_lag_state(self.rows, self.lag, self.device)
@@ -181,7 +205,7 @@ class SequenceSmoother:
     def track(self, heat, ratio, refine=True):
         out = F_.pose_track(heat, ratio, refine=refine, track_state=self.state, tracking=self.tracking)
         mx, raw, kp, status = out[1], out[2], out[3], out[7]
-        self.history.append(self.state, status, kp, raw, mx)
+        self.history.append(self.state, status, kp, raw, mx, *out[8:9] if self.tracking.maneuvers else ())
         if self.record is not None:
             self.record.ratio, self.record.extent = float(ratio), (heat.shape[-1] * float(ratio), heat.shape[-2] * float(ratio))
             self.record.append(F_.pose_measure(heat, ratio, refine=refine)[3], start=self._first)
@@ -276,7 +300,9 @@ def temporal_setting(cfg):
     ``rts`` or ``lag`` (the tracker's measurement is the sub-pixel decode's, as in the live stream), raises here, where the config is
     read.  ``TEST.temporalFit`` (no key of the reference's YAML either): absent or ``false`` is off; ``true`` needs ``temporal`` to be
     something other than ``off`` and makes ``Runner.eval`` fit ``accel_psd``, ``meas_std`` and ``heatmap_gain`` to the walked frames'
-    measurements and print them (``tools.calibrate.fit_tracking``); anything but a bool raises here."""
+    measurements and print them (``tools.calibrate.fit_tracking``); anything but a bool raises here.  ``tracking.accel_psd_moving``
+    (with ``switch_prob`` and ``moving_prior``) turns the two-model tracker on: ``temporal: track`` scores it, ``rts`` and ``lag``
+    beside it raise here."""
     from ..misc.metrics import decode_setting
     test = getattr(cfg, "TEST", None)
     mode = getattr(test, "temporal", "off")
@@ -297,7 +323,7 @@ def temporal_setting(cfg):
         if not hasattr(kw, "__dict__") or isinstance(kw, type):
             raise ValueError("TEST.tracking must be a mapping of PoseTracking arguments, got %r" % (kw,))
         kw = vars(kw)
-    known = tuple(k for k in PoseTracking.ARGUMENTS + PoseTracking.PAIR_ARGUMENTS if k != "rate_hz")
+    known = tuple(k for k in PoseTracking.ARGUMENTS + PoseTracking.PAIR_ARGUMENTS + PoseTracking.MANEUVER_ARGUMENTS if k != "rate_hz")
     for k in kw:
         if k not in known:
             raise ValueError("TEST.tracking.%s is no PoseTracking argument (%s; the rate is TEST.temporalRate)" % (k, ", ".join(known)))
@@ -317,6 +343,9 @@ def temporal_setting(cfg):
     if decode_setting(cfg) == "integral":
         raise ValueError("TEST.temporal: %s and TEST.decode: integral exclude each other: the tracker's measurement is the sub-pixel "
                          "decode's" % mode)
+    if tracking.maneuvers and mode in ("rts", "lag"):
+        raise ValueError("TEST.temporal: %s and TEST.tracking.accel_psd_moving exclude each other: the smoothers run over a single "
+                         "model's states; TEST.temporal: track scores the two-model tracker" % mode)
     return TemporalSetting(mode, tracking, int(lag), fit)
 
 

@@ -24,6 +24,8 @@ outliers are gated, drop-outs coast on the track's velocity, every joint carries
 strongest (csrc/pose_assoc.hip, one launch in the tracker's place), and ``gate_on_presence=True`` takes the measurement away where the
 presence gate sees nobody.  ``PoseTracking(pair_swap=True)`` assigns the left / right partners of the skeleton jointly, each pair
 sharing the peaks of both its maps (csrc/pose_pairs.hip, one launch likewise): a left / right exchange by the network is followed.
+``PoseTracking(accel_psd_moving=Q)`` runs a still and a moving model per joint and mixes them, the interacting-multiple-model
+estimator (csrc/pose_imm.hip, one launch likewise): a joint that rests and reaches gets the right process noise in both regimes.
 ``decode="integral"`` decodes the mass centroid of the window of ``decode_radius`` pixels around the peak (default: the targets' patch
 radius; 0: the whole map) — what the integral coordinate loss trains — in one launch of csrc/pose_integral.hip in place of the two,
 ``smooth`` included; it does not combine with ``track``, whose measurement is pinned to the sub-pixel decode.
@@ -33,7 +35,8 @@ radius; 0: the whole map) — what the integral coordinate loss trains — in on
                                     [--decode argmax|subpixel|integral [--decode-radius N]] [--smooth --rate FPS]
                                     [--track --rate FPS [--predict-now] [--accel-psd Q] [--gate D2] [--max-coast N] [--rts]
                                      [--track-candidates N] [--track-separation N] [--track-peak-ratio X] [--track-on-presence]
-                                     [--track-pairs [--track-swap-cost X]] [--track-lag N]]
+                                     [--track-pairs [--track-swap-cost X]] [--track-lag N]
+                                     [--track-moving-psd Q [--track-switch-prob P] [--track-moving-prior M]]]
                                     [--presence [--pfa X] [--cfar-guard N] [--cfar-train N] [--min-cells N] [--confirm N] [--hold N]]
 
 ``presence=PresenceGate(...)`` / ``--presence``: scene occupancy.  A CA-CFAR detector on the centre frame's horizontal mean planes and a
@@ -160,6 +163,12 @@ class _PairFields(_AssociationFields):
     __slots__ = ("pair_swap", "swap_cost", "pairs")
 
 
+class _ManeuverFields(_PairFields):
+    """The three settings ``PoseTracking`` gained with the second, "moving" motion model (a base class of their own, for the same
+    reason; ``PoseTracking.MANEUVER_ARGUMENTS`` lists them)."""
+    __slots__ = ("accel_psd_moving", "switch_prob", "moving_prior")
+
+
 def check_pairs(pairs, joints=None):
     """A partner table: a sequence of 1..``F_.MAX_GROUP_ROWS`` integers (no bools), entry j the partner of joint j or j itself, its own
     inverse, and ``joints`` long where that is given -> the table as a tuple of ints.  Anything else is a TrackingError."""
@@ -177,7 +186,7 @@ def check_pairs(pairs, joints=None):
     return tuple(int(q) for q in table)
 
 
-class PoseTracking(_PairFields):
+class PoseTracking(_ManeuverFields):
     """Kalman tracker settings of a session (a constant-velocity filter per joint; the rule is stated beside hupr_pose_track_f32 in
     include/hupr.h): ``rate_hz`` the frame rate of the stream; ``accel_psd`` (pixel^2 / s^3) the power of the white acceleration that
     drives the process noise; the measurement noise is ``heatmap_gain`` times the spread of the heat-map around its peak plus
@@ -200,14 +209,24 @@ class PoseTracking(_PairFields):
     ``R_*`` names of ``DATASET.idxToJoints`` (``tools.augment.mirror_pairs``).  ``swap_cost`` (>= 0) is added to the cost of a peak
     from the partner's map: 0 follows a swap at once, but two partners that pass close to each other then take each other's peak now
     and then; a larger value keeps those apart and follows a real swap late (PAPERS.md has the numbers).  Hence off by default; a good
-    ``swap_cost`` for real captures is unmeasured.  It composes with ``candidates`` and ``gate_on_presence``."""
+    ``swap_cost`` for real captures is unmeasured.  It composes with ``candidates`` and ``gate_on_presence``.
+    ``accel_psd_moving`` (None = off, else finite and >= ``accel_psd``): two filters per joint instead of one, the interacting-multiple-
+    model estimator (csrc/pose_imm.hip; the rule is stated beside hupr_pose_track_imm_f32): a "still" model with ``accel_psd`` and a
+    "moving" one with ``accel_psd_moving`` run on the same measurement, a Markov chain that changes model with probability
+    ``switch_prob`` (in [0, 0.5]) per frame couples them, the likelihood of each filter's innovation updates their probabilities, and
+    the pose is their mixture; a new track gives the moving model ``moving_prior`` (in [0, 1]).  For joints that rest, reach and rest
+    again, where one ``accel_psd`` is wrong for one of the two regimes (PAPERS.md has the numbers, on a synthetic scenario).  The
+    defaults of the three are guesses, unmeasured on real captures, and the default ``accel_psd`` of 200 is too high for a still
+    model: lower it beside ``accel_psd_moving``.  The measurement is the arg-max: not with ``candidates`` > 1 or ``pair_swap``;
+    ``gate_on_presence`` composes."""
     __slots__ = ("rate_hz", "accel_psd", "meas_std", "heatmap_gain", "gate", "max_coast", "init_speed_std", "min_score", "horizon_s")
     ARGUMENTS = __slots__ + _AssociationFields.__slots__
     PAIR_ARGUMENTS = _PairFields.__slots__
+    MANEUVER_ARGUMENTS = _ManeuverFields.__slots__
 
     def __init__(self, rate_hz, accel_psd=200.0, meas_std=1.0, heatmap_gain=1.0, gate=13.816, max_coast=5, init_speed_std=50.0,
                  min_score=0.0, horizon_s=0.0, candidates=1, min_separation=3, peak_ratio=0.25, gate_on_presence=False, pair_swap=False,
-                 swap_cost=0.0, pairs=None):
+                 swap_cost=0.0, pairs=None, accel_psd_moving=None, switch_prob=0.05, moving_prior=0.5):
         vals = dict(rate_hz=rate_hz, accel_psd=accel_psd, meas_std=meas_std, heatmap_gain=heatmap_gain, gate=gate,
                     init_speed_std=init_speed_std, min_score=min_score, horizon_s=horizon_s, peak_ratio=peak_ratio, swap_cost=swap_cost)
         vals = {k: _finite(TrackingError, "PoseTracking." + k, v) for k, v in vals.items()}
@@ -233,19 +252,40 @@ class PoseTracking(_PairFields):
         self.gate_on_presence = gate_on_presence
         for k, v in vals.items():
             setattr(self, k, float(v))
+        self.switch_prob = float(_finite(TrackingError, "PoseTracking.switch_prob", switch_prob))
+        self.moving_prior = float(_finite(TrackingError, "PoseTracking.moving_prior", moving_prior))
+        if not 0 <= self.switch_prob <= 0.5:
+            raise TrackingError("PoseTracking.switch_prob must be in [0, 0.5], got %r" % (switch_prob,))
+        if not 0 <= self.moving_prior <= 1:
+            raise TrackingError("PoseTracking.moving_prior must be in [0, 1], got %r" % (moving_prior,))
+        self.accel_psd_moving = None
+        if accel_psd_moving is not None:
+            self.accel_psd_moving = float(_finite(TrackingError, "PoseTracking.accel_psd_moving", accel_psd_moving))
+            if self.accel_psd_moving < self.accel_psd:
+                raise TrackingError("PoseTracking.accel_psd_moving must not be below accel_psd %r, got %r" % (self.accel_psd, accel_psd_moving))
+            if self.candidates > 1 or self.pair_swap:
+                raise TrackingError("PoseTracking.accel_psd_moving excludes candidates > 1 and pair_swap: the two models run on the "
+                                    "arg-max measurement")
 
     def __repr__(self):
         shown = self.ARGUMENTS + (self.PAIR_ARGUMENTS if self.pair_swap else ())        # without the option: what it always printed
+        shown += self.MANEUVER_ARGUMENTS if self.maneuvers else ()
         return "PoseTracking(%s)" % ", ".join("%s=%r" % (k, getattr(self, k)) for k in shown)
 
     @property
     def associates(self):
         """Whether a session with these settings launches an associating tracker (csrc/pose_assoc.hip, or csrc/pose_pairs.hip with
         ``pair_swap``) instead of the plain one."""
-        return self.candidates > 1 or self.gate_on_presence or self.pair_swap
+        return (self.candidates > 1 or self.gate_on_presence or self.pair_swap) and not self.maneuvers
+
+    @property
+    def maneuvers(self):
+        """Whether a session with these settings launches the two-model tracker (csrc/pose_imm.hip) instead of the plain one."""
+        return self.accel_psd_moving is not None
 
     def _copy(self, **changed):
-        return PoseTracking(**dict({k: getattr(self, k) for k in self.ARGUMENTS + self.PAIR_ARGUMENTS}, **changed))
+        return PoseTracking(**dict({k: getattr(self, k) for k in self.ARGUMENTS + self.PAIR_ARGUMENTS + self.MANEUVER_ARGUMENTS},
+                                   **changed))
 
     def with_horizon(self, horizon_s):
         """A copy that forecasts ``horizon_s`` seconds ahead."""
@@ -532,6 +572,18 @@ class PairedPoseFrame(TrackedPoseFrame):
         self.source = source
 
 
+class ManeuveringPoseFrame(TrackedPoseFrame):
+    """What a tracking session with ``PoseTracking(accel_psd_moving=...)`` emits: a ``TrackedPoseFrame`` — keypoints, velocity,
+    covariance and forecast are the mixture of the still and the moving model — with ``moving`` (lanes, K), the probability of the
+    moving model, 0 for a joint without a live track.  (A class of its own, so that the fields of a ``TrackedPoseFrame`` are what they
+    always were.)"""
+    __slots__ = ("moving",)
+
+    def __init__(self, *fields, moving=None, **more):
+        super().__init__(*fields, **more)
+        self.moving = moving
+
+
 class LaggedPose:
     """The fixed-lag smoothed pose that falls due with an emitted frame of a session with ``lag=L`` (csrc/pose_lag.hip; the rule is
     stated beside hupr_pose_smooth_lag_f32 in include/hupr.h): the pose of ``frame`` = the emitted centre - L, smoothed backwards
@@ -582,6 +634,8 @@ def check_lag(lag, track):
         return None
     if track is None:
         raise TrackingError("lag needs track: the fixed-lag smoother runs over the tracker's states")
+    if track.maneuvers:
+        raise TrackingError("lag and PoseTracking.accel_psd_moving exclude each other: the smoother runs over a single model's states")
     try:
         return F_.check_lag(lag, "PoseStream: lag")
     except ValueError as e:
@@ -645,7 +699,13 @@ class PoseStream:
     ``MeasurementRecord`` (tools/calibrate.py).  ``fit_tracking()`` then returns the maximum-likelihood ``accel_psd``, ``meas_std`` and
     ``heatmap_gain`` over everything recorded (``tools.calibrate.fit_tracking``); ``reset()`` keeps the record and marks the next
     pose as a sequence's first.  It reports only: the tracker's outputs are those of a session without it, bit for bit.  The default,
-    False, adds nothing."""
+    False, adds nothing.
+    ``track=PoseTracking(..., accel_psd_moving=Q)``: two motion models per joint, a still and a moving one (csrc/pose_imm.hip: one
+    launch in the tracker's place likewise, inside the same graph replay, on a 32-float state per joint that ``reset()`` clears); the
+    session emits ``ManeuveringPoseFrame``s, whose keypoints, velocity, covariance and forecast are the mixture of the two models and
+    which carry ``moving``.  ``gate_on_presence`` and ``measurements`` compose (``fit_tracking()`` fits the single-model filter as
+    ever and leaves both acceleration PSDs as they are); ``lag`` and ``history`` do not: their smoothers run over a single model's
+    states.  Off by default: see ``PoseTracking``."""
 
     def __init__(self, model, cfg, lanes=1, lookahead=None, graph=True, device=None, decode="argmax", smooth=None, track=None,
                  predict_now=False, decode_radius=None, tdm_compensation=False, history=False, presence=None, interference=None,
@@ -664,6 +724,8 @@ class PoseStream:
             raise StreamError("history must be True or False, got %r" % (history,))
         if history and track is None:
             raise TrackingError("history needs track: it records the tracker's states for smoothed()")
+        if history and track.maneuvers:
+            raise TrackingError("history and PoseTracking.accel_psd_moving exclude each other: smoothed() runs over a single model's states")
         self.lag = check_lag(lag, track)
         if not isinstance(measurements, bool):
             raise StreamError("measurements must be True or False, got %r" % (measurements,))
@@ -717,7 +779,7 @@ class PoseStream:
                 self._raw, self._vel, self._fc = torch.empty_like(self._kp), torch.empty_like(self._kp), torch.empty_like(self._kp)
                 self._cov = torch.empty((lanes, self.K, 3), dtype=torch.float32, device=dev)
                 self._status = torch.empty((lanes, self.K), dtype=torch.int32, device=dev)
-                self._tstate = F_.pose_track_state(lanes * self.K, dev)
+                self._tstate = (F_.pose_imm_state if track.maneuvers else F_.pose_track_state)(lanes * self.K, dev)
             # the associating tracker (csrc/pose_assoc.hip) in its place: the candidates it chose among and its choice
             self._cxy = self._cscore = self._ccount = self._chosen = None
             if track is not None and track.associates:
@@ -728,6 +790,8 @@ class PoseStream:
                 self._chosen = torch.full((lanes, self.K), -1, dtype=torch.int32, device=dev)
             # with pair_swap (csrc/pose_pairs.hip in its place): the map every choice came from
             self._source = torch.full((lanes, self.K), -1, dtype=torch.int32, device=dev) if track is not None and track.pair_swap else None
+            # with accel_psd_moving (csrc/pose_imm.hip in its place): the probability of the moving model
+            self._moving = torch.zeros((lanes, self.K), dtype=torch.float32, device=dev) if track is not None and track.maneuvers else None
             # the fixed-lag smoother behind it (csrc/pose_lag.hip): its ring and counters, and the tail of the last launch
             self._lstate = self._tail = None
             if self.lag is not None:
@@ -810,6 +874,7 @@ class PoseStream:
         if t is not None:                              # the presence launches of _front precede this one on the same stream
             out += (self._cov, self._fc, self._status) + ((self._cxy, self._cscore, self._ccount, self._chosen) if t.associates else ())
             out += (self._source,) if t.pair_swap else ()
+            out += (self._moving,) if t.maneuvers else ()
             F_.pose_track(maps, self.ratio, refine, self._tstate, t, self._present if t.gate_on_presence else None, out=out)
             if self.lag is not None:                   # reads what the tracker left, writes its own ring and tail only
                 F_.pose_smooth_lag(self._tstate, self._status, self._kp, self._raw, self._mx, self._lstate, t, self.lag, out=self._tail)
@@ -854,6 +919,8 @@ class PoseStream:
             return PoseFrame(**fields)
         fields.update(covariance=self._cov, forecast=self._fc, status=self._status, candidates=self._cxy, candidate_scores=self._cscore,
                       candidate_count=self._ccount, chosen=self._chosen)
+        if self._moving is not None:
+            return ManeuveringPoseFrame(moving=self._moving, **fields)
         if self.lag is None:
             return TrackedPoseFrame(**fields) if self._source is None else PairedPoseFrame(source=self._source, **fields)
         lagged = self._lagged(center, self.lag) if center >= self.lag else None
@@ -997,6 +1064,13 @@ def parse(argv=None):
                    "right exchange by the network is followed; every record gains candidates, chosen and source")
     p.add_argument("--track-swap-cost", type=float, default=None, help="with --track-pairs: cost added to a peak from the partner's "
                    "heat-map (default 0)")
+    p.add_argument("--track-moving-psd", type=float, default=None, help="with --track: a second, moving model per joint with this "
+                   "white-acceleration power (>= --accel-psd), mixed with the still one (interacting multiple models); every record "
+                   "gains moving")
+    p.add_argument("--track-switch-prob", type=float, default=None, help="with --track-moving-psd: probability per frame of changing "
+                   "between the two models, in [0, 0.5] (default 0.05)")
+    p.add_argument("--track-moving-prior", type=float, default=None, help="with --track-moving-psd: probability of the moving model in "
+                   "a new track, in [0, 1] (default 0.5)")
     p.add_argument("--track-lag", type=int, default=None, help="with --track: fixed-lag smoothing over this many frames, 1..64; every "
                    "record gains lagged, lagged_velocity, lagged_covariance and lagged_flag, N frames after its own pose")
     p.add_argument("--rts", action="store_true", help="with --track: after the flush, smooth the whole recording backwards (Rauch-Tung-"
@@ -1041,6 +1115,11 @@ def parse(argv=None):
         p.error("--track-on-presence needs --presence")
     if args.track_swap_cost is not None and not args.track_pairs:
         p.error("--track-swap-cost needs --track-pairs")
+    for flag, dest in (("--track-switch-prob", "track_switch_prob"), ("--track-moving-prior", "track_moving_prior")):
+        if getattr(args, dest) is not None and args.track_moving_psd is None:
+            p.error("%s needs --track-moving-psd" % flag)
+    if args.track_moving_psd is not None and (args.rts or args.track_lag is not None):
+        p.error("--track-moving-psd excludes --rts and --track-lag: the smoothers run over a single model's states")
     if args.track_lag is not None and not 1 <= args.track_lag <= F_.MAX_LAG:
         p.error("--track-lag must be an integer in 1..%d frames" % F_.MAX_LAG)
     # a dependent flag (given: neither None nor False) needs its switch; with the switch the settings object must build
@@ -1063,7 +1142,8 @@ TRACK_FLAGS = (("--predict-now", "predict_now"), ("--accel-psd", "accel_psd"), (
                ("--rts", "rts"), ("--track-candidates", "track_candidates"), ("--track-separation", "track_separation"),
                ("--track-peak-ratio", "track_peak_ratio"), ("--track-on-presence", "track_on_presence"),
                ("--track-pairs", "track_pairs"), ("--track-swap-cost", "track_swap_cost"), ("--track-lag", "track_lag"),
-               ("--fit-tracker", "fit_tracker"))
+               ("--fit-tracker", "fit_tracker"), ("--track-moving-psd", "track_moving_psd"),
+               ("--track-switch-prob", "track_switch_prob"), ("--track-moving-prior", "track_moving_prior"))
 INTERFERENCE_FLAGS = (("--interference-threshold", "interference_threshold"), ("--interference-guard", "interference_guard"),
                       ("--interference-fill", "interference_fill"))
 
@@ -1098,7 +1178,8 @@ def tracking_from_args(args):
         return None
     kw = {k: getattr(args, k) for k in ("accel_psd", "gate", "max_coast") if getattr(args, k) is not None}
     for dest, k in (("track_candidates", "candidates"), ("track_separation", "min_separation"), ("track_peak_ratio", "peak_ratio"),
-                    ("track_swap_cost", "swap_cost")):
+                    ("track_swap_cost", "swap_cost"), ("track_moving_psd", "accel_psd_moving"), ("track_switch_prob", "switch_prob"),
+                    ("track_moving_prior", "moving_prior")):
         if getattr(args, dest) is not None:
             kw[k] = getattr(args, dest)
     return PoseTracking(args.rate, gate_on_presence=args.track_on_presence, pair_swap=args.track_pairs, **kw)
@@ -1209,6 +1290,8 @@ def main(argv=None):
                 records[-1]["chosen"] = [int(c) for c in pf.chosen.cpu().numpy()[0]]
             if pf.source is not None:
                 records[-1]["source"] = [int(c) for c in pf.source.cpu().numpy()[0]]
+            if isinstance(pf, ManeuveringPoseFrame):
+                records[-1]["moving"] = [float(v) for v in pf.moving.cpu().numpy()[0]]
         if pf.present is not None:
             records[-1]["present"] = int(pf.present.cpu().numpy()[0])
             records[-1]["occupancy"] = [float(v) for v in pf.occupancy.cpu().numpy()[0]]

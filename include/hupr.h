@@ -538,6 +538,48 @@ int hupr_pose_track_pairs_f32(const float* heat, long rows, int H, int W, float 
                               float* maxval, float* raw_keypoints, float* keypoints, float* velocity, float* covariance,
                               float* forecast, int* status, float* cand_xy, float* cand_score, int* cand_count, int* chosen,
                               int* source, hupr_stream_t stream);
+/* hupr_pose_track_f32 with two motion models per row (csrc/pose_imm.hip): the interacting-multiple-model estimator (Blom & Bar-Shalom,
+ * IEEE TAC 33(8), 1988; Bar-Shalom, Li & Kirubarajan 2001, section 11.6) for joints that rest, reach and rest again.  Model 0 ("still")
+ * filters with accel_psd, model 1 ("moving") with accel_psd_moving; everything else of the nine tracker parameters is shared.  New, no
+ * reference counterpart.  One 64-lane wave per row, no scratch, no LDS, no atomics: the same maps and the same state give the same
+ * bits.  Everything not said here is hupr_pose_track_f32's: the arguments up to horizon_s, the decode (idx, maxval and raw_keypoints
+ * are hupr_pose_decode_f32's bits), the measurement z with its covariance R and the usable rule, F, Q, the gate quantities, the Joseph
+ * update, coasting and the status codes.  Predict, gate, update, coast and start are the same device functions, run once per model.
+ * state : float [rows][32] = (model 0's x, y, vx, vy, P00, P01, P02, P03, P11, P12, P13, P22, P23, P33; model 1's same 14; mu0, mu1;
+ *   live, coast): floats 0..13 in the order of hupr_pose_track_f32's state, mu_j the probability of model j, one live / coast shared by
+ *   both models.  hupr_pose_track_imm_state_bytes(rows) bytes, 16-byte aligned; all zero = never seen.  It advances with every launch.
+ * A live row, with p = switch_prob and the Markov chain pi = [[1 - p, p], [p, 1 - p]]:
+ *   1. Mixing.  c_j = sum_i pi_ij mu_i;  w_{i|j} = pi_ij mu_i / c_j;  x0_j = sum_i w_{i|j} x_i (computed as x_0 + w_{1|j} (x_1 - x_0));
+ *      P0_j = sum_i w_{i|j} (P_i + (x_i - x0_j)(x_i - x0_j)^T), all 4 x 4.  With switch_prob == 0 the step is skipped: c = mu, and
+ *      every model goes on from its own estimate.
+ *   2. Predict.  Each model as in hupr_pose_track_f32 from (x0_j, P0_j), with its own accel_psd in Q.
+ *   3. Gate.  Each model j gets nu_j, S_j, det S_j and d2_j against z; its gate is valid when z is usable and det S_j > 0 and finite.
+ *      The frame's measurement is accepted iff some model with c_j > 0 has a valid gate and d2_j <= gate.
+ *   4. Accepted.  Every model with a valid gate takes the Joseph update (whatever its d2_j and c_j); one whose gate is not valid keeps
+ *      its prediction.  l_j = d2_j + ln det S_j (minus twice the log-likelihood of nu_j up to a constant, the cost of
+ *      hupr_pose_track_assoc_f32);  m = min l_j over the models with a valid gate and c_j > 0;  w_j = c_j exp(-(l_j - m) / 2) for those
+ *      models and 0 for the others;  mu_j = w_j / (w_0 + w_1).  coast = 0; status HUPR_TRACK_UPDATED.
+ *   5. Not accepted.  mu = c; both models keep their predictions; the shared counter coasts or the track ends exactly as in
+ *      hupr_pose_track_f32: HUPR_TRACK_COASTED_GATED if z is usable, else HUPR_TRACK_COASTED_MISSING, and past max_coast the track ends.
+ * No live track (also one that ended in this frame): a usable z starts both models as hupr_pose_track_f32 starts its one, with
+ *   mu = (1 - moving_prior, moving_prior), status HUPR_TRACK_STARTED; otherwise the whole state is zero, status HUPR_TRACK_LOST.
+ * Outputs: the moment-matched mixture.  x = x_0 + mu_1 (x_1 - x_0) for all four components; keypoints = its position, velocity its
+ *   velocity; covariance (P00, P01, P11) of sum_j mu_j (P_j + d_j d_j^T), d_j = x_j - x; forecast = keypoints + horizon_s velocity.
+ *   LOST: keypoints = forecast = z, velocity and covariance 0.  moving [rows] = mu_1, 0 without a live track.
+ * With switch_prob = 0 and moving_prior = 0 model 1 never has a say: the eight outputs, state floats 0..13 and live / coast are those of
+ *   hupr_pose_track_f32 (state floats 0..15) bit for bit, and moving is 0.
+ * present_or_null, rows_per_group : the presence flags of hupr_pose_track_assoc_f32: int [rows / rows_per_group]; where the flag is 0
+ *   the rows of the group have no usable measurement in this frame.  NULL: no coupling, rows_per_group is not read.
+ * Returns -1 (HUPR_ERR_ARG) before any launch for hupr_pose_track_f32's errors, a null moving, accel_psd_moving not finite or below
+ * accel_psd, switch_prob outside [0, 0.5], moving_prior outside [0, 1] (NaN included) and, with present_or_null, rows_per_group < 1 or
+ * rows no multiple of it.  rows == 0 is a no-op. */
+size_t hupr_pose_track_imm_state_bytes(long rows);
+int hupr_pose_track_imm_f32(const float* heat, long rows, int H, int W, float ratio, int refine, float* state, float rate_hz,
+                            float accel_psd, float meas_std, float heatmap_gain, float gate, int max_coast, float init_speed_std,
+                            float min_score, float horizon_s, float accel_psd_moving, float switch_prob, float moving_prior,
+                            const int* present_or_null, int rows_per_group, int* idx, float* maxval, float* raw_keypoints,
+                            float* keypoints, float* velocity, float* covariance, float* forecast, int* status, float* moving,
+                            hupr_stream_t stream);
 /* Fixed-interval Rauch-Tung-Striebel smoother over a recorded run of hupr_pose_track_f32 in one launch (csrc/pose_smooth.hip; Rauch,
  * Tung & Striebel 1965): the backward pass over the states the filter left behind, so that the answer for frame k uses the frames
  * after it too.  New, no reference counterpart.  One thread per row, sequential in the frame: a latency-bound recurrence of T
