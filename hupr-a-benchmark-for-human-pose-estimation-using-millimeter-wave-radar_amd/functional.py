@@ -2491,3 +2491,47 @@ def adc_interference(adc, K=32, guard=2, fill="clutter", out=None, want_mask=Fal
         rt.check(rt.lib().hupr_adc_interference_i16(rt.ptr(adc), rt.ptr(out), n, K, guard, FILLS[fill], rt.ptr(mask), rt.ptr(groups), rt.stream()))
         rt.check(rt.lib().hupr_adc_interference_stats(rt.ptr(groups), n, rt.ptr(frames), rt.stream()))
     return out, stats or InterferenceStats(frames, groups), mask
+
+
+# ---- radar scene simulator: moving scatterers -> the raw ADC cube of one sensor (csrc/radar_scene.hip) ------------------------------------
+def _host_f64(name, a, shape):
+    a = np.ascontiguousarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a, dtype=np.float64)
+    if a.shape != shape:
+        raise ValueError("radar_scene: %s must have shape %r, got %r" % (name, shape, a.shape))
+    return a
+
+
+def radar_scene(pos, vel, amp, tx, rx, wavelength, range_bin_m, chirp_period_s, add=None, out_dtype=torch.int16):
+    """The raw ADC cube of one sensor for ``frames`` frames of S moving point scatterers, in one launch (the model and its arithmetic
+    are stated beside hupr_radar_scene_i16 in include/hupr.h).  ``pos``, ``vel``: fp64 GPU tensors (frames, S, 3), metres and metres
+    per second at the start of each frame's burst; ``amp``: fp32 (frames, S), 0 or NaN hides a scatterer for that frame; ``tx`` (3, 3)
+    and ``rx`` (4, 3): the antenna positions, anything ``np.asarray`` takes (they travel with the launch); ``add``: fp32
+    (frames, 4, 192, 256, 2) added to the sums, or None.  -> (frames, 4, 192, 256, 2), int16 (rounded to nearest even, clipped) or, with
+    ``out_dtype=torch.float32``, the fp32 sums.  Device tensor, no sync."""
+    if out_dtype not in (torch.int16, torch.float32):
+        raise ValueError("radar_scene: out_dtype must be torch.int16 or torch.float32, got %r" % (out_dtype,))
+    for name, t, dt in (("pos", pos, torch.float64), ("vel", vel, torch.float64), ("amp", amp, torch.float32)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt:
+            raise ValueError("radar_scene: %s must be a %s tensor, got %s" % (name, dt, getattr(t, "dtype", type(t).__name__)))
+    if pos.dim() != 3 or pos.shape[2] != 3 or pos.shape[1] < 1 or vel.shape != pos.shape or tuple(amp.shape) != tuple(pos.shape[:2]):
+        raise ValueError("radar_scene: pos and vel must be (frames, S >= 1, 3) and amp (frames, S), got %r, %r, %r"
+                         % (tuple(pos.shape), tuple(vel.shape), tuple(amp.shape)))
+    frames, S = int(pos.shape[0]), int(pos.shape[1])
+    cube = (frames, 4, 192, 256, 2)
+    if add is not None and (not isinstance(add, torch.Tensor) or add.dtype != torch.float32 or tuple(add.shape) != cube):
+        raise ValueError("radar_scene: add must be an fp32 tensor %r or None, got %s %r"
+                         % (cube, getattr(add, "dtype", type(add).__name__), tuple(getattr(add, "shape", ()))))
+    txh, rxh = _host_f64("tx", tx, (3, 3)), _host_f64("rx", rx, (4, 3))
+    if not pos.is_cuda:
+        raise rt.HuprError("radar_scene needs GPU tensors (no CPU fallback), got %s" % pos.device)
+    for name, t in (("vel", vel), ("amp", amp), ("add", add)):
+        if t is not None and t.device != pos.device:
+            raise ValueError("radar_scene: %s is on %s, pos on %s" % (name, t.device, pos.device))
+    f64p = ctypes.POINTER(ctypes.c_double)
+    with torch.cuda.device(pos.device):
+        out = torch.empty(cube, dtype=out_dtype, device=pos.device)
+        fn = rt.lib().hupr_radar_scene_i16 if out_dtype == torch.int16 else rt.lib().hupr_radar_scene_f32
+        rt.check(fn(rt.ptr(_c(pos)), rt.ptr(_c(vel)), rt.ptr(_c(amp)), txh.ctypes.data_as(f64p), rxh.ctypes.data_as(f64p), frames, S,
+                    float(wavelength), float(range_bin_m), float(chirp_period_s), rt.ptr(None if add is None else _c(add)), rt.ptr(out),
+                    rt.stream()))
+    return out

@@ -241,6 +241,11 @@ SIGNATURES = {
     # interference blanking of the raw cube in front of the FFT chain (csrc/interference.hip)
     "hupr_adc_interference_i16": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "hupr_adc_interference_stats": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
+    # radar scene simulator: moving scatterers -> the raw ADC cube (csrc/radar_scene.hip); tx and rx are host memory
+    "hupr_radar_scene_i16": (c_int, [c_void_p] * 3 + [ctypes.POINTER(ctypes.c_double)] * 2 + [c_int, c_int] + [ctypes.c_double] * 3 +
+                             [c_void_p] * 3),
+    "hupr_radar_scene_f32": (c_int, [c_void_p] * 3 + [ctypes.POINTER(ctypes.c_double)] * 2 + [c_int, c_int] + [ctypes.c_double] * 3 +
+                             [c_void_p] * 3),
     # bf16-activation variants (same argument lists as their fp32-activation counterparts)
     "hupr_conv3x3_halo_bf16act": (c_int, [c_void_p] * 5 + [c_int] * 10 + [c_void_p]),
     "hupr_conv3x3_halo_splitk_ws_bytes": (c_size_t, [c_int] * 7),

@@ -1203,6 +1203,47 @@ int hupr_adc_interference_i16(const void* adc, void* out, int n_sf, int K, int g
  * One small launch.  stats does not overlap group_counts. */
 int hupr_adc_interference_stats(const int* group_counts, int n_sf, int* stats, hupr_stream_t stream);
 
+/* (a16) Radar scene simulator: moving point scatterers -> the raw ADC cube of one sensor (csrc/radar_scene.hip; hupr_amd.simulate,
+ * `python -m hupr_amd.tools.simulate`).  New, no reference counterpart: the reference only reads recorded captures.  NOT real data:
+ * isotropic points of fixed amplitude, no multipath, no occlusion, no antenna pattern.
+ *
+ * The model.  A scene holds `frames` frames of S scatterers; per frame f and scatterer s a position p0 = pos[f][s][0..2] (metres), a
+ * velocity v = vel[f][s][0..2] (metres per second), both at the start of that frame's burst, and an amplitude a = amp[f][s] >= 0.
+ * The sensor is three transmitter positions tx[0..2][3] and four receiver positions rx[0..3][3] (metres, same coordinates), and three
+ * scalars: wavelength (metres), range_bin_m (metres per bin of the 256-point range transform) and chirp_period_s.  Chirp c in 0..191
+ * fires at t = c * chirp_period_s from transmitter c % 3 (the reference's demultiplexing); within a chirp nothing
+ * moves (stop-and-hop).  For receiver r and sample n in 0..255:
+ *     p    = p0 + v * t
+ *     path = |p - tx[c % 3]| + |p - rx[r]|
+ *     value(r, c, n) = sum over s of  a / (|p - tx| * |p - rx|) * exp(2 pi i (path / wavelength + n * path / (2 * 256 * range_bin_m)))
+ * A receding scatterer's phase grows from chirp to chirp.  I is the real part, Q the imaginary part.
+ *
+ * The arithmetic.  In fp64, every operation rounded on its own (no fused multiply-add), in this order:
+ *     p[k] = p0[k] + v[k] * t,  t = (double)c * chirp_period_s;     d(q) = sqrt((dx * dx + dy * dy) + dz * dz), dk = p[k] - q[k];
+ *     path = d(tx) + d(rx);   u = path / wavelength;   w = path / (512.0 * range_bin_m);
+ *     phi0 = rint((u - floor(u)) * 2^32) mod 2^32,   dphi = rint((w - floor(w)) * 2^32) mod 2^32       (ties to even; uint32)
+ *     A    = (float)((double)a / (d(tx) * d(rx)))
+ * The phase of sample n is phi0 + n * dphi in wrapping uint32 arithmetic — a numerically controlled oscillator, so the reduction
+ * modulo one turn is exact.  Read as a signed int32 and converted to fp32 (nearest even), times 2^-32, it is a fraction x of a turn in
+ * [-0.5, 0.5]; cs = cos(2 pi x), sn = sin(2 pi x) in fp32 (at most 2 ulp); re = fmaf(A, cs, re), im = fmaf(A, sn, im) in fp32 from
+ * 0, in scatterer order.  add_or_null: fp32 in the cube's own layout [frames][4][192][256][2], added to (re, im) after the sum (the
+ * Python layer's seeded receiver noise; the entry stays a pure function of its arguments).  hupr_radar_scene_f32 stores (re, im);
+ * hupr_radar_scene_i16 stores rint (ties to even) clipped to [-32768, 32767] (a NaN, possible only through add, gives -32768).
+ *
+ * Hidden scatterers.  A scatterer contributes nothing to a (frame, chirp, receiver) — exactly: the bits are those of the scene
+ * without it — unless its amplitude is finite and > 0, its position and velocity are finite and both distances are non-zero.
+ *
+ * pos, vel: device fp64 [frames][S][3], amp: device fp32 [frames][S]; tx_host [3][3], rx_host [4][3]: HOST fp64, finite, they travel by
+ * value with the launch.  out: device, int16 or fp32 [frames][4][192][256][2].  One launch, one workgroup per (frame, chirp), no
+ * workspace, no atomics: the same inputs give the same bits.  S in [1, 4096]; frames in [0, 2^20], 0 is a no-op; the three scalars
+ * positive and finite.  Stream-ordered and capturable in a hipGraph.  9.4e6 complex exponentials per sensor-frame at S = 48. */
+int hupr_radar_scene_i16(const double* pos, const double* vel, const float* amp, const double* tx_host, const double* rx_host, int frames,
+                         int S, double wavelength, double range_bin_m, double chirp_period_s, const float* add_or_null, void* out,
+                         hupr_stream_t stream);
+int hupr_radar_scene_f32(const double* pos, const double* vel, const float* amp, const double* tx_host, const double* rx_host, int frames,
+                         int S, double wavelength, double range_bin_m, double chirp_period_s, const float* add_or_null, float* out,
+                         hupr_stream_t stream);
+
 /* ---- bf16-activation variants ("bf16act") -------------------------------------------------------------
  * Same operators with the ACTIVATION tensors (x, y, dy, dx, residual) stored as bf16 in HBM; parameters,
  * statistics, weight gradients and all arithmetic stay fp32 (fp32 accumulate on the matrix pipe).  The
