@@ -2535,3 +2535,104 @@ def radar_scene(pos, vel, amp, tx, rx, wavelength, range_bin_m, chirp_period_s, 
                     float(wavelength), float(range_bin_m), float(chirp_period_s), rt.ptr(None if add is None else _c(add)), rt.ptr(out),
                     rt.stream()))
     return out
+
+
+# ---- radar point cloud: CFAR peaks to sub-cell points, two sensors fused to metres (csrc/radar_points.hip) -------------------------------
+PEAK_FIELDS = ("range", "azimuth", "doppler", "power", "snr", "cell")
+CLOUD_FIELDS = ("x", "y", "z", "velocity", "snr_h", "snr_v", "row_h", "row_v")
+
+
+class RadarPeaks:
+    """What ``radar_peaks`` returns.  ``points`` (..., max_points, 6) fp32, the fields of ``PEAK_FIELDS`` (also as attributes:
+    ``result.range`` is ``points[..., 0]``), sorted by descending power, unused rows (0, 0, 0, 0, 0, -1); ``counts`` int32 (..., 2) =
+    (points written, peaks found), also ``result.count`` and ``result.found``; ``max_points``, ``sep_range``, ``sep_azimuth`` the
+    settings of the run.  Device tensors."""
+    __slots__ = ("points", "counts", "max_points", "sep_range", "sep_azimuth")
+
+    def __init__(self, points, counts, max_points, sep_range, sep_azimuth):
+        self.points, self.counts, self.max_points, self.sep_range, self.sep_azimuth = points, counts, max_points, sep_range, sep_azimuth
+
+    def __getattr__(self, name):
+        if name in PEAK_FIELDS:
+            return self.points[..., PEAK_FIELDS.index(name)]
+        if name in ("count", "found"):
+            return self.counts[..., ("count", "found").index(name)]
+        raise AttributeError(name)
+
+
+class RadarCloud:
+    """What ``radar_points_fuse`` returns.  ``cloud`` (..., max_points, 8) fp32, the fields of ``CLOUD_FIELDS`` (also as attributes;
+    ``xyz`` is ``cloud[..., :3]``): metres, metres per second (receding positive), both sensors' SNR and the rows of the two points in
+    their lists; unused rows (0, 0, 0, 0, 0, 0, -1, -1).  ``counts`` int32 (...,): the points of each frame.  ``peaks_h``, ``peaks_v``:
+    the ``RadarPeaks`` it was made of.  Device tensors."""
+    __slots__ = ("cloud", "counts", "peaks_h", "peaks_v")
+
+    def __init__(self, cloud, counts, peaks_h, peaks_v):
+        self.cloud, self.counts, self.peaks_h, self.peaks_v = cloud, counts, peaks_h, peaks_v
+
+    def __getattr__(self, name):
+        if name in CLOUD_FIELDS:
+            return self.cloud[..., CLOUD_FIELDS.index(name)]
+        if name == "xyz":
+            return self.cloud[..., :3]
+        raise AttributeError(name)
+
+
+def radar_peaks(planes, mask, snr=None, max_points=64, sep_range=1, sep_azimuth=4):
+    """The detections of ``cfar_ra`` thinned to local power maxima and refined to sub-cell points, one launch (csrc/radar_points.hip; the
+    rule is stated beside hupr_radar_peaks_f32 in include/hupr.h).  ``planes`` (..., 16, 64, 64) fp32 GPU, ``mask`` uint8 and ``snr``
+    fp32 or None, (..., 8, 64, 64) each -> ``RadarPeaks``.  Device tensors, no sync."""
+    from .preprocessing.points import check_points
+    s = check_points(max_points=max_points, sep_range=sep_range, sep_azimuth=sep_azimuth)
+    max_points, sep_range, sep_azimuth = s["max_points"], s["sep_range"], s["sep_azimuth"]
+    if not isinstance(planes, torch.Tensor) or planes.dtype != torch.float32 or planes.dim() < 3 or tuple(planes.shape[-3:]) != (16, 64, 64):
+        raise ValueError("radar_peaks needs fp32 planes (..., 16, 64, 64), got %s %r" % (getattr(planes, "dtype", type(planes).__name__),
+                                                                                       tuple(getattr(planes, "shape", ()))))
+    lead = tuple(planes.shape[:-3])
+    for name, t, dt in (("mask", mask, torch.uint8), ("snr", snr, torch.float32)):
+        if t is None and name == "snr":
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != dt or tuple(t.shape) != lead + (8, 64, 64):
+            raise ValueError("radar_peaks needs a %s %s %r, got %s %r" % (dt, name, lead + (8, 64, 64), getattr(t, "dtype", type(t).__name__),
+                                                                          tuple(getattr(t, "shape", ()))))
+    if not planes.is_cuda:
+        raise rt.HuprError("radar_peaks needs GPU planes (no CPU fallback), got %s" % planes.device)
+    for name, t in (("mask", mask), ("snr", snr)):
+        if t is not None and t.device != planes.device:
+            raise ValueError("radar_peaks: %s is on %s, planes on %s" % (name, t.device, planes.device))
+    n, dev = int(np.prod(lead, dtype=np.int64)), planes.device
+    with torch.cuda.device(dev):
+        points = torch.empty(lead + (max_points, 6), dtype=torch.float32, device=dev)
+        counts = torch.empty(lead + (2,), dtype=torch.int32, device=dev)
+        rt.check(rt.lib().hupr_radar_peaks_f32(rt.ptr(_c(planes)), rt.ptr(_c(mask)), rt.ptr(None if snr is None else _c(snr)), n, max_points,
+                                               sep_range, sep_azimuth, rt.ptr(points), rt.ptr(counts), rt.stream()))
+    return RadarPeaks(points, counts, max_points, sep_range, sep_azimuth)
+
+
+def radar_points_fuse(peaks_h, peaks_v, geometry, range_gate=1.5, doppler_gate=1):
+    """The two sensors' points of the same frames paired and turned into metres, one launch (the rule is stated beside
+    hupr_radar_points_fuse_f32 in include/hupr.h).  ``peaks_h``, ``peaks_v``: the ``RadarPeaks`` of the horizontal and the vertical sensor;
+    ``geometry``: ``preprocessing.points.radar_geometry(model)`` = (range_bin_m, doppler_mps_per_bin, a_h, o_h, a_v, o_v) -> ``RadarCloud``
+    with as many rows as ``peaks_h``.  Device tensors, no sync."""
+    from .preprocessing.points import check_points, geometry_vector
+    s = check_points(range_gate=range_gate, doppler_gate=doppler_gate)
+    geo = geometry_vector(geometry)
+    for name, p in (("peaks_h", peaks_h), ("peaks_v", peaks_v)):
+        if not isinstance(p, RadarPeaks):
+            raise ValueError("radar_points_fuse: %s must be a RadarPeaks, got %s" % (name, type(p).__name__))
+    lead = tuple(peaks_h.counts.shape[:-1])
+    if tuple(peaks_v.counts.shape[:-1]) != lead:
+        raise ValueError("radar_points_fuse: the sensors' frames differ: %r and %r" % (lead, tuple(peaks_v.counts.shape[:-1])))
+    if not peaks_h.points.is_cuda:
+        raise rt.HuprError("radar_points_fuse needs GPU points (no CPU fallback), got %s" % peaks_h.points.device)
+    dev = peaks_h.points.device
+    if peaks_v.points.device != dev:
+        raise ValueError("radar_points_fuse: peaks_v is on %s, peaks_h on %s" % (peaks_v.points.device, dev))
+    n, mh, mv = int(np.prod(lead, dtype=np.int64)), int(peaks_h.points.shape[-2]), int(peaks_v.points.shape[-2])
+    with torch.cuda.device(dev):
+        cloud = torch.empty(lead + (mh, 8), dtype=torch.float32, device=dev)
+        counts = torch.empty(lead, dtype=torch.int32, device=dev)
+        rt.check(rt.lib().hupr_radar_points_fuse_f32(rt.ptr(_c(peaks_h.points)), rt.ptr(_c(peaks_h.counts)), mh, rt.ptr(_c(peaks_v.points)),
+                                                     rt.ptr(_c(peaks_v.counts)), mv, n, geo.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                                     s["range_gate"], s["doppler_gate"], rt.ptr(cloud), rt.ptr(counts), rt.stream()))
+    return RadarCloud(cloud, counts, peaks_h, peaks_v)

@@ -246,6 +246,10 @@ SIGNATURES = {
                              [c_void_p] * 3),
     "hupr_radar_scene_f32": (c_int, [c_void_p] * 3 + [ctypes.POINTER(ctypes.c_double)] * 2 + [c_int, c_int] + [ctypes.c_double] * 3 +
                              [c_void_p] * 3),
+    # radar point cloud: CFAR peaks to sub-cell points, two sensors fused to metres (csrc/radar_points.hip); the geometry is host memory
+    "hupr_radar_peaks_f32": (c_int, [c_void_p] * 3 + [c_int] * 4 + [c_void_p] * 3),
+    "hupr_radar_points_fuse_f32": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, ctypes.POINTER(ctypes.c_double),
+                                           ctypes.c_double, c_int, c_void_p, c_void_p, c_void_p]),
     # bf16-activation variants (same argument lists as their fp32-activation counterparts)
     "hupr_conv3x3_halo_bf16act": (c_int, [c_void_p] * 5 + [c_int] * 10 + [c_void_p]),
     "hupr_conv3x3_halo_splitk_ws_bytes": (c_size_t, [c_int] * 7),

@@ -750,6 +750,63 @@ int hupr_cfar_ra_stream_f32(const float* ring, const void* stream_state, int loo
                             float* summary, hupr_stream_t stream);
 int hupr_presence_update(const float* summary, int lanes, int min_cells, int confirm, int hold, int* gate_state, int* present_out,
                          hupr_stream_t stream);
+/* Radar point cloud, one sensor (csrc/radar_points.hip): the detections of hupr_cfar_ra_f32 thinned to local power maxima and refined to
+ * sub-cell (range, azimuth) points (Rohling 1983; Jacobsen & Kootsookos 2007 for the range estimator; Richards ch. 6).  New, no
+ * reference counterpart.  One workgroup per frame, 49 KB of LDS, no atomics, a block prefix scan and fixed orders: every output is
+ * bit-identical from run to run.
+ * planes : float [n][16][64][64] and mask : unsigned char [n][8][64][64], what hupr_cfar_ra_f32 reads and writes.
+ * Power.   p_f[r][a] = fmaf(x[2f], x[2f], x[2f+1] * x[2f+1]) in fp32, the rounding of the CFAR kernel.  Slot 4 is never read.
+ * Peak.    Cell c = (f, r, a) is a point iff mask[c] == 1 and p[c] dominates its box.  The box: the slots f' with |f' - f| <= 1, slot 4
+ *          and slots outside 0..7 left out; in each, the cells with |r' - r| <= sep_range and |a' - a| <= sep_azimuth inside the map
+ *          (no axis wraps).  Every cell of the box counts, detected or not.  p[c] dominates when p[c] > p[c'] for every c' of the box
+ *          below c in (f, r, a) order and p[c] >= p[c'] for every c' above it: a plateau yields its lowest cell, once.  A NaN fails
+ *          every comparison: a NaN power is no point, and no cell with a NaN in its box is one.
+ *          0 <= sep_range <= 4, 0 <= sep_azimuth <= 8; the Python layer's defaults are 1 and 4 (half the 8-antenna main lobe).
+ * Refinement, in fp32, every operation rounded on its own (sqrt and the divisions correctly rounded; log is evaluated in fp64 and
+ *          rounded to fp32, so it is the correctly rounded fp32 logarithm but for a double rounding):
+ *          range.   A0 = sqrt(p[c]), A- = sqrt(p at (f, r - 1, a)), A+ = sqrt(p at (f, r + 1, a)); a neighbour outside the map or
+ *                   NaN counts as 0.  range = A+ >= A- ? r + A+ / (A0 + A+) : r - A- / (A0 + A-)  — the two-point amplitude
+ *                   estimator of an unwindowed, unpadded DFT.  Against exact arithmetic on the same fp32 powers the error is at most
+ *                   2^-24 (4 |range - r| + |range|): one rounding in each root, one in the sum, one in the quotient, one in the
+ *                   last sum.
+ *          azimuth. l = log(p) at (f, r, a - 1), c and (f, r, a + 1); den = (l- - 2 l0) + l+;
+ *                   azimuth = a + clip(0.5 * ((l- - l+) / den), -0.5, 0.5), the three-point parabola of a zero-padded transform's
+ *                   lobe; the offset is 0 for a = 0 or 63, where a neighbour's power is not > 0, or where den is not < 0.  The
+ *                   quotient cancels where the lobe is flat (|den| small): no bound is stated.
+ *          Doppler is not refined: d = f - 4.
+ * points : float [n][max_points][6] = (range index, azimuth index, signed Doppler bin d, power p[c], snr, cell), cell = (f * 64 + r) *
+ *          64 + a as a float; snr = snr_or_null[c] (float [n][8][64][64], what hupr_cfar_ra_f32 writes) or 0 without it.  Sorted by
+ *          descending power, ties to the lower cell.  The rows beyond the points written hold (0, 0, 0, 0, 0, -1).
+ * counts : int [n][2] = (points written, peaks found).  The first 4096 peaks of a frame in (f, r, a) order are staged and ranked; a
+ *          frame with more ranks those and still reports the true number found, so the caller sees found > 4096.
+ * max_points in 1..256.  Returns -1 (HUPR_ERR_ARG) before any launch for a bad count or separation, n < 0 or beyond 2^20 and null
+ * pointers (snr_or_null may be null); n == 0 is a no-op.
+ *
+ * Two sensors to metres: hupr_radar_points_fuse_f32 pairs the horizontal sensor's points of a frame with the vertical sensor's and
+ * solves for the position.  One wave per frame, no atomics, fixed orders.
+ * points_h [n][max_h][6], counts_h [n][2], points_v [n][max_v][6], counts_v [n][2] : the outputs of hupr_radar_peaks_f32 for the same
+ *          frames of the two sensors (of counts only "points written" is read, clamped to the list).
+ * geometry_host : HOST double [14] = (range_bin_m, doppler_mps_per_bin, a_h[3], o_h[3], a_v[3], o_v[3]): metres per range bin, metres
+ *          per second per Doppler bin, and per sensor the unit vector a_s along its array and its origin o_s (metres; x right, y
+ *          boresight, z up).  |a_s| = 1 and a_h . a_v = 0 to 1e-9, all values finite, both scalars positive, and b = a_v x a_h must
+ *          have a y component (b is signed so that b . y > 0).
+ * Association.  The horizontal points are walked in their order (strongest first).  Each takes, among the vertical points not yet
+ *          taken whose Doppler bin differs by at most doppler_gate (0..7) and whose range index differs by at most range_gate
+ *          (|r_h - r_v| <= range_gate, the difference exact in fp64), the one with the smallest |r_h - r_v|, ties to the lower row.  A
+ *          horizontal point without a partner is not emitted.
+ * Geometry, fp64, stored as fp32.  R_s = (94 - range index) * range_bin_m, u_s = (31 - azimuth index) / 32 (the index conventions of
+ *          the FFT chain).  c_h = o_h . a_h + R_h u_h, c_v = o_v . a_v + R_v u_v,
+ *          c_b = o_h . b + sqrt(R_h^2 - (c_h - o_h . a_h)^2 - (c_v - o_h . a_v)^2); position = c_h a_h + c_v a_v + c_b b.  A radicand
+ *          that is negative (or NaN) drops the pair; its vertical point stays taken.
+ * cloud : float [n][max_h][8] = (x, y, z, radial velocity = d_h * doppler_mps_per_bin in m/s, receding positive, snr_h, snr_v, row_h,
+ *          row_v): eight fields, 32-byte rows, in the order of the horizontal points.  The rows beyond the pairs written hold
+ *          (0, 0, 0, 0, 0, 0, -1, -1).  cloud_counts : int [n].
+ * max_h, max_v in 1..256.  Returns -1 before any launch for a refused geometry, gate or count and null pointers; n == 0 is a no-op. */
+int hupr_radar_peaks_f32(const float* planes, const unsigned char* mask, const float* snr_or_null, int n, int max_points, int sep_range,
+                         int sep_azimuth, float* points, int* counts, hupr_stream_t stream);
+int hupr_radar_points_fuse_f32(const float* points_h, const int* counts_h, int max_h, const float* points_v, const int* counts_v, int max_v,
+                               int n, const double* geometry_host, double range_gate, int doppler_gate, float* cloud, int* cloud_counts,
+                               hupr_stream_t stream);
 
 /* tri-/bilinear align_corners=True resampling (models/layers.py:84,89,199,204; gcn_networks.py:49,63) */
 int hupr_interp_linear_fwd_f32(const float* x, float* y, int Bn, int Di, int Hi, int Wi, int Do, int Ho, int Wo,
